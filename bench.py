@@ -251,7 +251,7 @@ def parity_bf16(model, x):
 def parity_vs_reference(dev):
     """the benchmark's precision scored against the REFERENCE'S OWN outputs: BASELINE config 1 = the shipped
     YAML at full width on 64 x 64 images, bs 2, parameters regenerated from synth (tests/golden/dqvae_c1.npz holds what the reference
-    model of /root/reference returned for them -- tools/gen_golden.py).  `spread`: a codebook with score gaps far above rounding (the
+    model of the reference returned for them -- tools/gen_golden.py).  `spread`: a codebook with score gaps far above rounding (the
     reference's indices are reproducible); `refinit`: the reference's U(+-1/K) initialisation (every gap at fp32 rounding level).
     north_star bar: indices exact, reconstruction 1e-3 relative."""
     from dynamicvectorquantization_amd import config as cfg
@@ -293,6 +293,35 @@ def parity_vs_reference(dev):
             res[variant] = r
             del model
         out[tag] = res
+    return out
+
+
+DUMP_SAMPLE_PER_TENSOR = 16384      # elements taken from each larger state tensor by --dump-outputs (9.4 MB in all; the limit is 64 MB)
+
+
+def trainer_snapshot(trainer):
+    """everything a training step reads (weights, buffers, optimizer moments and counters, schedules) as a copy that
+    Trainer.load_state_dict puts back in place -- the recorded step keeps its addresses"""
+    snap = trainer.state_dict()
+    snap["state_dict"] = {k: v.detach().clone() for k, v in snap["state_dict"].items()}
+    return snap
+
+
+def step_outputs(model, losses):
+    """what one step of the timed path handed back, as host arrays (--dump-outputs): the losses it returned (one per optimizer),
+    the codebook it left behind, and the state it updated -- every state_dict tensor in key order, whole up to DUMP_SAMPLE_PER_TENSOR
+    elements, otherwise that many elements at fixed positions (a seeded draw that depends only on the tensor's size)"""
+    out = {"losses": torch.stack([l.detach().reshape(()).double() for l in losses]).cpu().numpy(),
+           "codebook": model.quantize.codebook._codebook().detach().float().cpu().numpy()}
+    parts = []
+    for v in model.state_dict().values():
+        flat = v.detach().reshape(-1)
+        n = flat.numel()
+        if n > DUMP_SAMPLE_PER_TENSOR:
+            pos = np.sort(np.random.default_rng(n).choice(n, DUMP_SAMPLE_PER_TENSOR, replace=False))
+            flat = flat[torch.from_numpy(pos).to(flat.device)]
+        parts.append(flat.float())
+    out["state_sample"] = torch.cat(parts).cpu().numpy()
     return out
 
 
@@ -424,6 +453,9 @@ def main():
     ap.add_argument("--no-extras", action="store_true", help="skip the compact BASELINE config 4 / 5 blocks (bench_extra.py workloads)")
     ap.add_argument("--extras-budget", type=float, default=150.0, help="seconds the extra workloads may take in all")
     ap.add_argument("--vq-only", action="store_true", help="only the VQ-argmin micro-benchmark (kernel iteration); prints its JSON")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, run the timed step once more (same kernels, launched eagerly) on the last timed step's batch "
+                         "from the seeded initial state and write what it computed to DIR/<name>.npy (see step_outputs)")
     ap.add_argument("--dry-run", action="store_true",
                     help="CPU check of the launch contract only: gloo ranks, barrier + timed loop of no-op steps, one JSON line; no GPU work")
     args = ap.parse_args()
@@ -467,9 +499,11 @@ def main():
             dist.barrier()
         torch.cuda.synchronize()
 
-    def run(objective, steps, warmup, profile, no_graph=args.no_graph):
+    def run(objective, steps, warmup, profile, no_graph=args.no_graph, dump=False):
         """build the model + trainer for `objective`, W untimed + K timed steps; -> (seconds [max over ranks], host issue
-        seconds, per-kernel profile of the last timed step, model)"""
+        seconds, per-kernel profile of the last timed step, model); dump: model._step_outputs = step_outputs() of one step of the timed
+        path from the initial state (the state the timed steps reached differs from run to run: their fp32 atomic reductions do
+        not add in a fixed order, and 20+ training steps -- codebook restarts, Adam -- amplify that)"""
         torch.manual_seed(0)       # identical initial weights on every rank
         model = instantiate_from_config(full_config(objective, args.bs)).to(dev)
         model.reuse_generator_forward = bool(args.reuse_forward)
@@ -480,6 +514,7 @@ def main():
         model.train()
         GRAPH_AFTER = 3
         trainer = Trainer(model, max_steps=steps, use_graph=not no_graph, graph_after=GRAPH_AFTER)
+        initial = trainer_snapshot(trainer) if dump else None
         # untimed initialisation before the W warmup steps: kernel code-object loading, allocator growth, packed-weight
         # tables (the first steps of a process are host-bound on these one-off costs), then the step is recorded as a
         # hipGraph (Trainer step capture) and the recording is replayed once
@@ -596,10 +631,36 @@ def main():
             dist.all_reduce(tmax, op=dist.ReduceOp.MAX)
             dt = float(tmax.item())
         trainer.drop_graph()
+        if dump:
+            # the timed step once more, on the last timed step's batch, from the seeded initial state, with the kernels the timed
+            # steps run (default reductions).  The state the timed steps reached cannot serve: it differs from run to run (fp32
+            # atomic reductions add in no fixed order, and 20+ training steps amplify that).  The step is launched eagerly: a replay
+            # of the recording re-issues this same launch sequence, but does not start from the restored state (replays after the
+            # restore differed between runs by up to 8 % on the generator loss, eager steps by 1.4e-6: profiles/dump_outputs_repeat.txt).  Then the run's state is
+            # put back -- weights, buffers, optimizer, schedules, the restart-row generators and the dropout seed counter -- so that
+            # the blocks reported after this one are computed as without --dump-outputs
+            reached = trainer_snapshot(trainer)
+            gens = [(m, m._rng_state.clone()) for m in model.modules() if getattr(m, "_rng_state", None) is not None]
+            seeds = rt._seed_counter[0]
+            trainer.load_state_dict(initial)
+            i = steps - 1
+            model._step_outputs = step_outputs(model, trainer.train_step(batches[i % nb], SETUP + warmup + i))
+            trainer.load_state_dict(reached)
+            for m, st in gens:
+                m._rng_state.copy_(st)
+            rt._seed_counter[0] = seeds
+            model._logged = {}
+            del initial, reached
         model._graph_info = graph_info
         return dt, host, prof, model
 
-    dt_, host_issue, prof, model = run(args.objective, args.steps, args.warmup, True)
+    dt_, host_issue, prof, model = run(args.objective, args.steps, args.warmup, True, dump=bool(args.dump_outputs))
+    if rank == 0 and args.dump_outputs:
+        assert sum(a.nbytes for a in model._step_outputs.values()) <= 64 << 20
+        os.makedirs(args.dump_outputs, exist_ok=True)
+        for name, arr in model._step_outputs.items():
+            np.save(os.path.join(args.dump_outputs, name + ".npy"), arr)
+        del model._step_outputs
     ratio = model._graph_info.pop("fine_ratio")
     graph_info, vq_seen = model._graph_info, getattr(model, "_vq_seen", None)
     parity = None

@@ -1,6 +1,6 @@
 """Entropy-threshold calibration and evaluation inputs (n3, parts of n1 / n4).
 
-  * threshold_table      the percentile rule of /root/reference/scripts/tools/calculate_entropy_thresholds.py:99-110
+  * threshold_table      the percentile rule of reference/scripts/tools/calculate_entropy_thresholds.py:99-110
                          (sorted entropies, entry "i" = sorted[(size * i) // 100], i = 1..99) -- the JSON that
                          DualGrainFixedEntropyRouter reads (RouterDual.py:49-51)
   * patch_entropies      all patch entropies of an image set on the fused HIP kernel (dvq_patch_entropy_gate[_range]).

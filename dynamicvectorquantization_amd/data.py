@@ -1,6 +1,6 @@
 """Input pipeline with the image transforms on the GPU.
 
-Mirrors /root/reference/data/imagenet_base.py:8-64 (ImagePaths: torchvision transforms on PIL images) and
+Mirrors reference/data/imagenet_base.py:8-64 (ImagePaths: torchvision transforms on PIL images) and
 data/build.py:16-90 (DataModuleFromConfig) for the batch dict {"image": fp32 [B,3,S,S] in [-1,1], "class_label": int64 [B], ...}:
 
     train:  Resize(256) -> RandomCrop(256) -> RandomHorizontalFlip(0.5) -> ToTensor -> Normalize(0.5, 0.5)

@@ -1,11 +1,11 @@
 """Host-side mirror of the DQ-VAE model family on libdvq_hip kernels.
 
 Mirrors (same class names, constructor kwargs, parameter names/shapes, call signatures):
-  * Entropy, DualGrainVQModel      /root/reference/models/stage1_dynamic/dqvae_dual_entropy.py:13-262
-  * DualGrainFixedEntropyRouter    /root/reference/modules/dynamic_modules/RouterDual.py:46-57
-  * DualGrainEncoder               /root/reference/modules/dynamic_modules/EncoderDual.py:16-156
-  * Decoder, PositionEmbedding2DLearned  /root/reference/modules/dynamic_modules/DecoderPositional.py:13-146
-  * FourierPositionEmbedding       /root/reference/modules/dynamic_modules/fourier_embedding.py:7-55
+  * Entropy, DualGrainVQModel      reference/models/stage1_dynamic/dqvae_dual_entropy.py:13-262
+  * DualGrainFixedEntropyRouter    reference/modules/dynamic_modules/RouterDual.py:46-57
+  * DualGrainEncoder               reference/modules/dynamic_modules/EncoderDual.py:16-156
+  * Decoder, PositionEmbedding2DLearned  reference/modules/dynamic_modules/DecoderPositional.py:13-146
+  * FourierPositionEmbedding       reference/modules/dynamic_modules/fourier_embedding.py:7-55
 
 Data layout: images stay NCHW fp32 at the API (the reference's batch format); inside the model every
 activation is NHWC in the runtime compute dtype, 3-channel images are zero-padded to one 16-byte

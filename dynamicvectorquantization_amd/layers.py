@@ -1,6 +1,6 @@
 """Host-side mirror of the reference's CNN building blocks, running on libdvq_hip kernels.
 
-Mirrors /root/reference/modules/diffusionmodules/model.py:29-192 -- same class names, constructor
+Mirrors reference/modules/diffusionmodules/model.py:29-192 -- same class names, constructor
 arguments, parameter names/shapes (state_dict compatible) and call signatures -- but the compute is
 hand-written HIP: every module has
 

@@ -1,6 +1,6 @@
 """Host-side mirror of the DQ-VAE training losses.
 
-Mirrors /root/reference/modules/losses/vqperceptual_multidisc.py:25-194 (hinge losses, adaptive weight,
+Mirrors reference/modules/losses/vqperceptual_multidisc.py:25-194 (hinge losses, adaptive weight,
 VQLPIPSWithDiscriminator), modules/losses/vqperceptual.py:9-11 (DummyLoss) and
 modules/dynamic_modules/budget.py:4-60.  The L1 term runs on dvq_l1_loss; scalar bookkeeping is host-side.
 
@@ -648,6 +648,13 @@ class _DiscLossFn(torch.autograd.Function):
         return (None,) * (5 + ctx.n)
 
 
+def _sq(d):
+    """d ** 2, same value and same gradient (2 * g * d is exact either way).  The backward of `d ** 2` evaluates d.pow(1), which
+    ATen runs as a tensor copy: a memcpy node in a recorded training step, and launch lists (csrc/cmdlist.hip) re-issue kernel
+    nodes only"""
+    return d * d
+
+
 class BudgetConstraint_RatioMSE_DualGrain(nn.Module):
     """budget.py:4-28 (incl. calculate_all returning loss_last + loss_last)."""
 
@@ -662,9 +669,9 @@ class BudgetConstraint_RatioMSE_DualGrain(nn.Module):
         beta = 1.0 * gate[:, 0, :, :] + 4.0 * gate[:, 1, :, :]
         beta = (beta.sum() / gate.size(0)) - self.const
         budget_ratio = beta / self.max_const
-        loss_budget = self.gamma * (budget_ratio - self.target_ratio) ** 2
+        loss_budget = self.gamma * _sq(budget_ratio - self.target_ratio)
         if self.calculate_all:
-            loss_budget_last = self.gamma * ((1 - budget_ratio) - (1 - self.target_ratio)) ** 2
+            loss_budget_last = self.gamma * _sq((1 - budget_ratio) - (1 - self.target_ratio))
             return loss_budget_last + loss_budget_last
         return loss_budget
 
@@ -685,8 +692,8 @@ class BudgetConstraint_NormedSeperateRatioMSE_TripleGrain(nn.Module):
         gate = gate.float()
         beta_median = 1.0 * gate[:, 0] + 4.0 * gate[:, 1] + 1.0 * gate[:, 2]
         ratio_median = ((beta_median.sum() / gate.size(0)) - self.min_const) / self.median_const
-        loss_median = (ratio_median - self.target_median_ratio) ** 2
+        loss_median = _sq(ratio_median - self.target_median_ratio)
         beta_fine = 1.0 * gate[:, 0] + 16.0 * gate[:, 2] + 1.0 * gate[:, 1]
         ratio_fine = ((beta_fine.sum() / gate.size(0)) - self.min_const) / self.max_const
-        loss_fine = self.gamma * (ratio_fine - self.target_fine_ratio) ** 2
+        loss_fine = self.gamma * _sq(ratio_fine - self.target_fine_ratio)
         return loss_fine + loss_median

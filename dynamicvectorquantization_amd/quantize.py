@@ -1,4 +1,4 @@
-"""Host-side mirror of /root/reference/modules/vector_quantization/quantize2_mask.py
+"""Host-side mirror of reference/modules/vector_quantization/quantize2_mask.py
 (VQEmbedding :10-132, VectorQuantize2 :135-210) on the libdvq_hip VQ kernels.
 
 Same constructor kwargs, buffers (`cluster_size_ema`, `embed_ema`), parameter (`weight` [K+1, D], row K =

@@ -1,6 +1,6 @@
 """Feature-routed (Gumbel) grain selection on the HIP kernels.
 
-Mirrors /root/reference/modules/dynamic_modules/RouterDual.py:6-43 (DualGrainFeatureRouter),
+Mirrors reference/modules/dynamic_modules/RouterDual.py:6-43 (DualGrainFeatureRouter),
 RouterTriple.py:6-56 (TripleGrainFeatureRouter) and the routing tail of EncoderDual.py:130-156 /
 EncoderTriple.py:143-183 (gumbel_softmax(hard) -> argmax -> nearest-upsampled select -> gate_grad scaling ->
 codebook mask).

@@ -1,6 +1,6 @@
 """StackGPT (stacked position / content transformers of the DQ-Transformer) on libdvq_hip kernels.
 
-Mirrors /root/reference/modules/dynamic_modules/stackgpt.py:7-339: same constructor arguments, parameter / buffer names
+Mirrors reference/modules/dynamic_modules/stackgpt.py:7-339: same constructor arguments, parameter / buffer names
 (`content_emb.weight`, `pos_emb`, `position_transformer.3.attn.key.weight`, `content_head.1.weight`, ...) and
 forward() contract (training: dict of the four losses; otherwise the two logit tensors).
 

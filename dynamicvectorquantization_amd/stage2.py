@@ -1,6 +1,6 @@
 """Stage-2 (DQ-Transformer) input plumbing on the HIP path: code maps <-> sequences.
 
-Mirrors /root/reference/modules/dynamic_modules/permuter.py:6-135 (DualGrainSeperatePermuter) and
+Mirrors reference/modules/dynamic_modules/permuter.py:6-135 (DualGrainSeperatePermuter) and
 modules/dynamic_modules/label_provider.py:4-92 (SOS providers).  The permutation is integer compaction / scatter work done
 by dvq_permute_dual / dvq_permute_dual_back (one workgroup per image); results are bit-exact with the reference, including
 its sequential edge semantics (missing EOS, duplicate positions).  The transformer itself (`stackgpt.StackGPT`: fused causal

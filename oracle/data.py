@@ -1,6 +1,6 @@
 """Oracle: the reference's image transforms (numpy).  TEST INFRASTRUCTURE -- never imported by the product package.
 
-Restates what /root/reference/data/imagenet_base.py:16-32 does to a decoded image through torchvision 0.14 / Pillow 9.4
+Restates what reference/data/imagenet_base.py:16-32 does to a decoded image through torchvision 0.14 / Pillow 9.4
 (both pinned in the reference's environment.yml):
   Resize(256): shorter side -> 256, longer side -> int(256 * long / short); PIL `Image.resize(..., BILINEAR)` = antialiased
   separable resampling in 8-bit fixed point (Pillow src/libImaging/Resample.c); Random/CenterCrop(256); optional horizontal

@@ -1,7 +1,7 @@
 """Oracle: the DQ-VAE CNN blocks, dual-grain encoder, positional decoder and whole-model
 forward, as pure functions of a state_dict (torch-CPU fp32).
 
-Follows (behaviour, not code), all under /root/reference:
+Follows (behaviour, not code), all in the reference project:
   * nonlinearity / Normalize / Upsample / Downsample / ResnetBlock / AttnBlock
         modules/diffusionmodules/model.py:29-192
   * DualGrainEncoder.forward            modules/dynamic_modules/EncoderDual.py:89-156

@@ -1,6 +1,6 @@
 """Oracle: one teacher-forced stage-2 forward (numpy / torch-CPU).  TEST INFRASTRUCTURE -- never imported by the product package.
 
-Restates /root/reference/models/stage2_dynamic/dqtransformer_uncond_entropy.py:166-215 (`encode_to_z`, `forward`) and the
+Restates reference/models/stage2_dynamic/dqtransformer_uncond_entropy.py:166-215 (`encode_to_z`, `forward`) and the
 class-conditional start tokens of modules/dynamic_modules/label_provider.py:94-128 on top of the other oracles: frozen DQ-VAE
 (oracle.dqvae) -> code map + grain map -> sequences (oracle.permuter) -> start tokens -> StackGPT losses (oracle.stackgpt).
 Pinned against the reference's own `training_step` in tests/test_oracle_golden.py (tests/golden/dualformer.npz).

@@ -1,8 +1,8 @@
 """Oracle: per-patch soft-histogram entropy and the fixed-entropy router gate.
 
 Follows (behaviour, not code):
-  * Entropy.forward / .entropy   /root/reference/models/stage1_dynamic/dqvae_dual_entropy.py:25-63
-  * DualGrainFixedEntropyRouter   /root/reference/modules/dynamic_modules/RouterDual.py:46-57
+  * Entropy.forward / .entropy   reference/models/stage1_dynamic/dqvae_dual_entropy.py:25-63
+  * DualGrainFixedEntropyRouter   reference/modules/dynamic_modules/RouterDual.py:46-57
 
 Math: gray = .2989 R + .5870 G + .1140 B; non-overlapping p x p patches; 32 bins on
 linspace(-1,1,32); k(v,b) = exp(-.5 ((v-b)/sigma)^2), sigma = 0.01; pdf_b = mean_v k;
@@ -55,7 +55,7 @@ def entropy_gate(entropy: np.ndarray, threshold: float) -> np.ndarray:
 
 
 def threshold_table(entropies: np.ndarray) -> dict:
-    """The percentile table of /root/reference/scripts/tools/calculate_entropy_thresholds.py:99-110: sort all patch
+    """The percentile table of reference/scripts/tools/calculate_entropy_thresholds.py:99-110: sort all patch
     entropies ascending; entry "i" (i = 1..99) = sorted[(size * i) // 100] as a Python float."""
     e = np.sort(np.asarray(entropies, dtype=np.float32).reshape(-1))
     size = e.shape[0]

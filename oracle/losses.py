@@ -1,7 +1,7 @@
 """Oracle: the training-loss networks of the DQ-VAE step (torch-CPU fp32, autograd for the gradients).
 TEST INFRASTRUCTURE -- never imported by the product package.
 
-Follows (behaviour, not code), all under /root/reference:
+Follows (behaviour, not code), all in the reference project:
   * NLayerDiscriminator (PatchGAN)          modules/discriminator/model.py:17-67
   * LPIPS, ScalingLayer, NetLinLayer, vgg16 modules/losses/lpips.py:11-122   (torchvision VGG16 "D" feature stack:
                                             3x3 convs 64,64,M,128,128,M,256x3,M,512x3,M,512x3 with ReLU, taps after

@@ -1,7 +1,7 @@
 """Oracle: dual-grain code map <-> sequence permutation (numpy, integer, sequential like the reference).
 TEST INFRASTRUCTURE -- never imported by the product package.
 
-Follows (behaviour, not code) /root/reference/modules/dynamic_modules/permuter.py:50-135: `forward` builds the
+Follows (behaviour, not code) reference/modules/dynamic_modules/permuter.py:50-135: `forward` builds the
 EOS-terminated / PAD-filled coarse and fine content + position rows ("region-first": fine cells one after the other,
 "row-first": raster order of the fine grid), `forward_back` scatters them back sequentially.
 """

@@ -1,7 +1,7 @@
 """Oracle: feature-routed (Gumbel) dual / triple grain encoders and models (torch-CPU fp32, autograd-differentiable).
 TEST INFRASTRUCTURE -- never imported by the product package.
 
-Follows (behaviour, not code), all under /root/reference:
+Follows (behaviour, not code), all in the reference project:
   * DualGrainFeatureRouter / TripleGrainFeatureRouter    modules/dynamic_modules/RouterDual.py:6-43, RouterTriple.py:6-56
   * routing tail of the encoders                         EncoderDual.py:130-156, EncoderTriple.py:143-183
   * torch.nn.functional.gumbel_softmax(hard=True)        restated with INJECTED Exp(1) noise (the device RNG draw is

@@ -1,7 +1,7 @@
 """Oracle: StackGPT teacher-forced forward + losses (torch-CPU fp32, functional over a state_dict, autograd-differentiable).
 TEST INFRASTRUCTURE -- never imported by the product package.
 
-Follows (behaviour, not code) /root/reference/modules/dynamic_modules/stackgpt.py:44-96 (attention / block) and :175-232
+Follows (behaviour, not code) reference/modules/dynamic_modules/stackgpt.py:44-96 (attention / block) and :175-232
 (StackGPT.forward).  Dropout probabilities are taken as 0 (device RNG: "parity unpinned").
 """
 from __future__ import annotations

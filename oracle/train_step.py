@@ -7,7 +7,7 @@ torch.optim.Adam, both LambdaLR schedules) for several steps and aborts unless `
 quantity; tests/test_oracle_golden.py::test_oracle_train_step_matches_reference repeats the check against the committed fixture
 (tests/golden/train_step_*.npz).
 
-What one step is (all under /root/reference):
+What one step is (all in the reference project):
   * Lightning's automatic optimization with two optimizers = per batch, for i in (0, 1): toggle_optimizer(i),
     training_step(batch, idx, i), zero_grad, backward, optimizer_i.step(); then both `interval: step` schedulers step.
   * models/stage1_dynamic/dqvae_dual_entropy.py:154-183  training_step: a FULL autoencoder forward for each optimizer index --

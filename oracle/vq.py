@@ -2,7 +2,7 @@
 
 Follows (behaviour, not code):
   * VQEmbedding.compute_distances / find_nearest_embedding
-      /root/reference/modules/vector_quantization/quantize2_mask.py:29-55
+      reference/modules/vector_quantization/quantize2_mask.py:29-55
   * VQEmbedding._update_buffers / _update_embedding   ... quantize2_mask.py:66-115
   * VectorQuantize2.forward                            ... quantize2_mask.py:157-191
 

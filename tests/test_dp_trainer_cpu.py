@@ -7,7 +7,9 @@ import os
 import socket
 import subprocess
 import sys
+import warnings
 
+import numpy as np
 import pytest
 import torch
 import torch.distributed as dist
@@ -197,3 +199,24 @@ def test_bench_spawns_its_own_ranks_dry_run():
     assert rec["n_gpus"] == 2 and rec["steps"] == 3 and rec["warmup"] == 1 and rec["dry_run"] is True
     assert rec["config"]["parallelism"] == "dp2" and rec["config"]["global_batch"] == 128 and rec["value"] > 0
     assert rec["config"]["learning_rate"] == pytest.approx(2 * 64 * 4.5e-6)
+
+
+def test_bench_step_outputs_are_fixed_and_bounded():
+    """bench.py --dump-outputs: the arrays taken from the benchmark's model are float32 / float64, sit at the same positions in
+    every call (so two builds can be compared element for element), and stay under the 64 MB the dump may take"""
+    sys.path.insert(0, REPO)
+    import bench
+    from dynamicvectorquantization_amd.config import instantiate_from_config
+    torch.manual_seed(0)
+    with warnings.catch_warnings():
+        warnings.simplefilter("ignore")        # (no pretrained LPIPS weights: the random-VGG warning)
+        model = instantiate_from_config(bench.full_config("full", 64))
+    losses = [torch.tensor(0.25), torch.tensor(-1.5)]
+    a, b = bench.step_outputs(model, losses), bench.step_outputs(model, losses)
+    assert sorted(a) == ["codebook", "losses", "state_sample"]
+    assert a["losses"].tolist() == [0.25, -1.5]
+    assert all(v.dtype in (np.float32, np.float64) and np.array_equal(v, b[k]) for k, v in a.items())
+    assert sum(v.nbytes for v in a.values()) <= 64 << 20
+    with torch.no_grad():
+        model.encoder.conv_in.weight.add_(1.0)     # an updated weight shows up in the sample
+    assert not np.array_equal(bench.step_outputs(model, losses)["state_sample"], a["state_sample"])

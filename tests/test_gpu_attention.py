@@ -1,5 +1,5 @@
 """GPU parity of the fused causal attention kernels (csrc/attention.hip: bf16, head size 64 / 128) against an fp32 torch
-restatement of CausalSelfAttention.forward (/root/reference/modules/dynamic_modules/stackgpt.py:41-69) and against the
+restatement of CausalSelfAttention.forward (reference/modules/dynamic_modules/stackgpt.py:41-69) and against the
 package's own unfused per-head GEMM path; head sizes 64 and 128 (the shipped p6c18 configs use 8 heads of 128).  Tolerance: rel-to-max 2e-2 (bf16 operands, fp32 accumulation)."""
 import math
 import os

@@ -100,7 +100,7 @@ def test_vq_argmin_exact_while_gpu_is_shared(dev, tmp_path):
 def test_two_rank_rccl_on_two_devices(dev, tmp_path):
     """the SAME two-rank checks over the real `nccl` (= RCCL) backend, one device per rank -- runs whenever the box shows >= 2 GPUs
     (the builder's boxes have one: skipped there; the first multi-GPU box exercises RCCL without anyone remembering to).
-    Reference: /root/reference/train.py:227-230 (DDPPlugin), quantize2_mask.py:86-88,99-100 (all-reduce + broadcast)."""
+    Reference: reference/train.py:227-230 (DDPPlugin), quantize2_mask.py:86-88,99-100 (all-reduce + broadcast)."""
     import torch
     if torch.cuda.device_count() < 2:
         pytest.skip("needs >= 2 visible GPUs (RCCL refuses two ranks on one device)")

@@ -193,6 +193,8 @@ def test_config4_triple_k8192_full_size_properties(dev):
         n0 = cb.cluster_size_ema.clone()
         losses = [[float(l) for l in tr.train_step({"image": xs[i % 2]}, i)] for i in range(4)]
         assert np.isfinite(np.array(losses)).all() and tr.graph_replays == 2, (losses, tr.graph_replays)
+        # the whole step re-issues as one launch list: no segment left to hipGraphLaunch (a memcpy node, e.g. from the budget loss)
+        assert [k for k, _ in tr._graph["sg"].items] == ["list"]
         out = model._last
         codes, grain, mask = out["codes"], out["grain"], out["mask"]
         assert tuple(codes.shape) == (bs, 32, 32) and int(codes.min()) >= 0 and int(codes.max()) < 8192

@@ -19,7 +19,6 @@ import os
 import re
 import subprocess
 import sys
-import tempfile
 
 REPO = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, REPO)
@@ -51,7 +50,9 @@ FUNC = re.compile(r"^(_Z\w+):")
 
 
 def asm_of(src):
-    out = os.path.join(tempfile.gettempdir(), "dvq_lint_" + src.replace(".hip", ".s"))
+    # next to this checkout's objects: a shared temp directory would hand one checkout (or user) another one's assembly
+    out = os.path.join(B.OBJ, "lint", src.replace(".hip", ".s"))
+    os.makedirs(os.path.dirname(out), exist_ok=True)
     s = os.path.join(B.CSRC, src)
     if not os.path.exists(out) or os.path.getmtime(out) < max(os.path.getmtime(s), os.path.getmtime(os.path.join(B.CSRC, "dvq_common.h"))):
         cmd = [B._hipcc()] + B.FLAGS + B.EXTRA_FLAGS.get(src, []) + ["--cuda-device-only", "-S", s, "-o", out]
