@@ -1186,3 +1186,42 @@ def sample_constrained(logits2d, temperature, pad_code, state, forbid_idx=None, 
                                        int(pad_code), _p(fin), int(top_k or 0), float(top_p or 0.0), int(bool(sample)), _p(state), _p(out),
                                        _s()), "dvq_sample_constrained")
     return out
+
+
+# ---------------------------------------------------------------------------------------------
+# reconstruction evaluation (csrc/metrics.hip)
+# ---------------------------------------------------------------------------------------------
+def recon_metrics_workspace(b, h, w, device):
+    """uint8 workspace of dvq_recon_metrics_workspace_bytes(b, h, w) bytes (per-tile partial sums)"""
+    return torch.empty(int(lib().dvq_recon_metrics_workspace_bytes(b, h, w)), dtype=torch.uint8, device=device)
+
+
+def recon_metrics(x, y, quantize_u8=False, ws=None, out=None):
+    """x (target), y (reconstruction) NCHW fp32 [B,3,H,W] in [-1, 1] -> (mse, l1, ssim), fp64 [B] each (definitions:
+    include/dvq_hip.h, dvq_recon_metrics).  ws: recon_metrics_workspace(B, H, W) or None (allocated here); out: three fp64 [B]
+    tensors to write into, or None"""
+    b, c, h, w = x.shape
+    assert c == 3 and x.dtype == torch.float32 and y.dtype == torch.float32 and tuple(y.shape) == tuple(x.shape)
+    if ws is None:
+        ws = recon_metrics_workspace(b, h, w, x.device)
+    mse, l1, ssim = out if out is not None else [torch.empty(b, dtype=torch.float64, device=x.device) for _ in range(3)]
+    check(lib().dvq_recon_metrics(_p(x), _p(y), b, h, w, int(bool(quantize_u8)), _p(mse), _p(l1), _p(ssim), _p(ws), ws.numel(), _s()),
+          "dvq_recon_metrics")
+    return mse, l1, ssim
+
+
+def code_histogram(codes, grain, n_codes, n_grains, counts, invalid, tokens=None):
+    """codes int64 [B,Hf,Wf], grain int64 [B,hg,wg] or None (n_grains = 1); counts int64 [n_grains, n_codes] and invalid int64 [1]
+    are ACCUMULATED (zero them once).  -> tokens int64 [B] (tokens per image by the grain's alignment rule, include/dvq_hip.h)"""
+    b, hf, wf = codes.shape
+    assert codes.dtype == torch.int64 and counts.dtype == torch.int64 and invalid.dtype == torch.int64
+    assert tuple(counts.shape) == (n_grains, n_codes) and invalid.numel() >= 1
+    hg = wg = 0
+    if grain is not None:
+        assert grain.dtype == torch.int64 and grain.shape[0] == b
+        hg, wg = grain.shape[1], grain.shape[2]
+    if tokens is None:
+        tokens = torch.empty(b, dtype=torch.int64, device=codes.device)
+    check(lib().dvq_code_histogram(_p(codes), _p(grain), b, hf, wf, hg, wg, int(n_codes), int(n_grains), _p(counts), _p(tokens),
+                                   _p(invalid), _s()), "dvq_code_histogram")
+    return tokens

@@ -42,7 +42,8 @@ enum { DVQ_F32 = 0, DVQ_BF16 = 1 };
 enum { DVQ_OK = 0, DVQ_EINVAL = -1, DVQ_ESHAPE = -2, DVQ_EARCH = -3, DVQ_ELAUNCH = -4, DVQ_EWORKSPACE = -5 };
 
 const char* dvq_last_error(void);
-int dvq_version(void);     /* 109: round 5 (dvq_conv2d_fwd_x3 / dvq_conv2d_dgrad_x3: fp32x3 3 x 3 convolutions on the halo kernel, fp32 output);
+int dvq_version(void);     /* 110: dvq_recon_metrics (+ _workspace_bytes), dvq_code_histogram (reconstruction evaluation);
+                            * 109: round 5 (dvq_conv2d_fwd_x3 / dvq_conv2d_dgrad_x3: fp32x3 3 x 3 convolutions on the halo kernel, fp32 output);
                             * 108: round 5 (dvq_split_bf16_planes, dvq_conv2d_wgrad_oihw_x3: fp32x3 weight gradients on the bf16 kernels);
                             * 107: round 5 (dvq_lpips_head_drop; probe modes compiled out of the product library: -DDVQ_PROBES);
                             * 106: round 4 (launch lists dvq_cmdlist_*, dvq_add_uniform, dvq_decode_stack_status + 64 sequences, drop_mask argument
@@ -597,6 +598,29 @@ int dvq_fill_f32(float* p, float v, int64_t n, dvq_stream_t stream);
 size_t dvq_image_desc_bytes(void);
 int dvq_image_batch_transform(const uint8_t* src, const void* desc, const int32_t* tables, uint8_t* tmp, int64_t B, int S,
                               int max_rows, float* out, dvq_stream_t stream);
+
+/* ---- reconstruction evaluation (no reference kernel: its codebook-usage tool collects codes on the host,
+ * scripts/tools/codebook_usage_dqvae.py:52-69; SSIM as Wang et al. 2004) -----------------------------------------------------------
+ * dvq_recon_metrics: x (target), y (reconstruction) NCHW fp32 [B][3][H][W] in [-1, 1]; per image fp64 outputs
+ *   mse[b]  = mean over 3 H W of (x01 - y01)^2, v01 = clamp(v * 0.5 + 0.5, 0, 1), with quantize_u8 = 1 then floor(v01 * 255 + 0.5) / 255
+ *             (the value a saved 8-bit PNG holds);
+ *   l1[b]   = mean of |x - y| on the raw inputs ([-1, 1] units, the units of the training loss's L1 term; neither clamped nor quantised);
+ *   ssim[b] = mean over the 3 channels and the (H - 10) x (W - 10) "valid" positions of the SSIM map of x01 / y01: 11 x 11 Gaussian
+ *             window (sigma 1.5, normalised), C1 = 0.01^2, C2 = 0.03^2, population (biased) variances.
+ * H < 11 or W < 11: DVQ_ESHAPE.  ws: dvq_recon_metrics_workspace_bytes(B, H, W) bytes (per-tile partial sums; ws_bytes smaller:
+ * DVQ_EWORKSPACE).  Partials are folded per image in a fixed order (no float atomics): the outputs are bitwise reproducible and
+ * independent of how images are grouped into batches.
+ * dvq_code_histogram: idx int64 [B][Hf][Wf] (VectorQuantize2's code map), grain int64 [B][hg][wg] (0 = coarsest) or NULL with G = 1.
+ *   Position (i, j) is a token iff i % s == 0 && j % s == 0, s = (Hf / hg) >> grain[i / (Hf / hg)][j / (Wf / wg)], with
+ *   Hf / hg == Wf / wg == 2^(G-1) (else DVQ_ESHAPE): a cell of grain g spends 4^g tokens; grain = NULL: every position is a token.
+ *   counts int64 [G][K] += tokens per (grain, code) (the caller zeroes it once; accumulates over calls); tokens int64 [B] = tokens per
+ *   image (overwritten; a token whose code is out of range still counts); invalid int64 [1] += codes outside [0, K) at token positions
+ *   + grain cells whose value is outside [0, G) (such a cell spends no token).  Integer atomics only: exact and deterministic. */
+size_t dvq_recon_metrics_workspace_bytes(int64_t B, int64_t H, int64_t W);
+int dvq_recon_metrics(const float* x, const float* y, int64_t B, int64_t H, int64_t W, int quantize_u8, double* mse, double* l1,
+                      double* ssim, void* ws, size_t ws_bytes, dvq_stream_t stream);
+int dvq_code_histogram(const int64_t* idx, const int64_t* grain, int64_t B, int64_t Hf, int64_t Wf, int64_t hg, int64_t wg, int64_t K,
+                       int G, int64_t* counts, int64_t* tokens, int64_t* invalid, dvq_stream_t stream);
 
 #ifdef __cplusplus
 }
