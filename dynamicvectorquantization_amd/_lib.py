@@ -165,6 +165,8 @@ SIGNATURES = {
     "dvq_sample_rows": (i32, [vp, i64, i64, vp, vp]),
     "dvq_add_uniform": (i32, [vp, i64, f32, vp, vp]),
     "dvq_sample_constrained": (i32, [vp, i32, i64, i64, i64, f32, vp, i64, i64, i64, vp, i64, i64, i64, vp, i32, f32, i32, vp, vp, vp]),
+    "dvq_sample_guided": (i32, [vp, i32, i64, i64, i64, f32, f32, vp, i64, i64, i64, vp, i64, i64, i64, vp, i32, f32, i32, vp, vp, vp]),
+    "dvq_label_dropout": (i32, [vp, i64, f32, i64, C.c_uint64, vp, vp]),
     "dvq_recon_metrics_workspace_bytes": (sz, [i64, i64, i64]),
     "dvq_recon_metrics": (i32, [vp, vp, i64, i64, i64, i32, vp, vp, vp, vp, sz, vp]),
     "dvq_code_histogram": (i32, [vp, vp, i64, i64, i64, i64, i64, i64, i32, vp, vp, vp, vp]),

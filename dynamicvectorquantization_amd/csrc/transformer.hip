@@ -501,6 +501,17 @@ __global__ __launch_bounds__(256) void dropout_kernel(const T* __restrict__ x, i
     }
 }
 
+// classifier-free-guidance training: out[i] = null_label where dropout_kernel's hash would DROP element i (same seed convention),
+// else labels[i].  The threshold is 64-bit so that p == 1 drops every label.
+__global__ __launch_bounds__(256) void label_dropout_kernel(const int64_t* __restrict__ labels, int64_t n, unsigned long long thr,
+                                                            int64_t null_label, unsigned rm, unsigned ra, int64_t* __restrict__ out) {
+    for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < n; i += (int64_t)gridDim.x * 256) {
+        const unsigned long long u = (unsigned long long)i;
+        const unsigned h = dvq_hash32((unsigned)u * rm + ra + (unsigned)(u >> 32) * 0x9E3779B1u);
+        out[i] = (unsigned long long)h < thr ? null_label : labels[i];
+    }
+}
+
 // y = x + dropout(a) (same decisions as dropout_kernel for the same seed and element index); p == 0: a plain add
 template <typename T>
 __global__ __launch_bounds__(256) void dropout_add_kernel(const T* __restrict__ x, const T* __restrict__ a, int64_t n8, float p, unsigned rm,
@@ -683,6 +694,16 @@ int dvq_dropout(const void* x, int dtype, int64_t n, float p, uint64_t seed, voi
     return DVQ_OK;
 }
 
+int dvq_label_dropout(const int64_t* labels, int64_t B, float p, int64_t null_label, uint64_t seed, int64_t* out, dvq_stream_t stream) {
+    DVQ_REQUIRE(labels && out && B > 0 && p >= 0.f && p <= 1.f, DVQ_EINVAL, "dvq_label_dropout: bad arguments (0 <= p <= 1)");
+    unsigned rm, ra;
+    dvq_dropout_seed(seed, &rm, &ra);
+    label_dropout_kernel<<<dim3(nblk(B, 256)), dim3(256), 0, (hipStream_t)stream>>>(labels, B, (unsigned long long)((double)p * 4294967296.0),
+                                                                                     null_label, rm, ra, out);
+    DVQ_CHECK_LAUNCH("label_dropout");
+    return DVQ_OK;
+}
+
 }  // extern "C"
 
 // ---- single-query attention over a K/V cache (sampling with a cache: one new row per step) ----------------------------
@@ -858,6 +879,7 @@ struct SampleParams {
     int top_k;
     float top_p;
     int sample;
+    float guidance;                 // GUIDED only (sits in what was padding: the other members keep their offsets)
     const uint64_t* state;
     int64_t* out;
 };
@@ -866,7 +888,10 @@ __device__ __forceinline__ bool sample_before(float va, int ia, float vb, int ib
     return va > vb || (va == vb && ia < ib);
 }
 
-template <typename T>
+// GUIDED (dvq_sample_guided): one workgroup per PAIR; logits rows [0, B) are conditional (c), rows [B, 2B) unconditional (u), B =
+// gridDim.x.  The pipeline runs on g = fmaf(1 - s, u, s * c) (s = 1: exactly c; s = 0: exactly u); the token goes to out[row] and
+// out[row + B].  forbid_idx / finished / the uniform use the pair's row index.
+template <typename T, bool GUIDED>
 __global__ __launch_bounds__(1024) void sample_constrained_kernel(SampleParams p) {
     extern __shared__ __attribute__((aligned(16))) char smem[];
     float* sv = reinterpret_cast<float*>(smem);             // [N] values, then probabilities
@@ -891,7 +916,13 @@ __global__ __launch_bounds__(1024) void sample_constrained_kernel(SampleParams p
     for (int c = tid; c < N; c += nth) {
         float v = -INFINITY;
         if (c < V) {
-            const float x = ElemIO<T>::load(lg + c) * p.inv_temperature;
+            float x;
+            if constexpr (GUIDED) {
+                const float s = p.guidance, uv = ElemIO<T>::load(lg + (int64_t)gridDim.x * p.ldl + c);
+                x = fmaf(1.f - s, uv, s * ElemIO<T>::load(lg + c)) * p.inv_temperature;
+            } else {
+                x = ElemIO<T>::load(lg + c) * p.inv_temperature;
+            }
             bool masked;
             if (fin) {
                 masked = c != p.pad_code;
@@ -1024,11 +1055,43 @@ __global__ __launch_bounds__(1024) void sample_constrained_kernel(SampleParams p
         }
         pick = max(best, 0);
     }
-    if (tid == 0) p.out[row] = (int64_t)si[pick];
+    if (tid == 0) {
+        p.out[row] = (int64_t)si[pick];
+        if constexpr (GUIDED) p.out[row + gridDim.x] = (int64_t)si[pick];
+    }
 }
 
 __global__ void sample_bump_kernel(uint64_t* state) {
     if (threadIdx.x == 0) state[1] += 1;
+}
+
+// the shared host side of dvq_sample_constrained / dvq_sample_guided: B rows (GUIDED: B pairs over 2 B logits rows)
+template <bool GUIDED>
+int sample_constrained_launch(const void* logits, int dtype, int64_t B, int64_t V, int64_t ldl, float temperature, float guidance,
+                              const int64_t* forbid_idx, int64_t n_forbid, int64_t forbid_ld, int64_t forbid_from,
+                              const int64_t* forbid_codes4, int64_t keep_code, int64_t late_forbid_code, int64_t pad_code,
+                              const float* finished, int top_k, float top_p, int sample, uint64_t* state, int64_t* out,
+                              dvq_stream_t stream) {
+    SampleParams p{};
+    p.logits = logits; p.ldl = ldl; p.V = (int)V;
+    int n = 256;
+    while (n < V) n <<= 1;
+    p.N = n;
+    p.inv_temperature = 1.f / temperature;
+    p.forbid_idx = forbid_idx; p.forbid_ld = forbid_ld; p.n_forbid = forbid_idx ? (int)n_forbid : 0;
+    p.forbid_from = (int)(forbid_from < 0 || forbid_from > V ? V : forbid_from);
+    for (int i = 0; i < 4; ++i) p.codes[i] = forbid_codes4 ? (int)forbid_codes4[i] : -1;
+    p.keep_code = (int)keep_code; p.late_forbid_code = (int)late_forbid_code; p.pad_code = (int)pad_code;
+    p.finished = finished; p.top_k = top_k; p.top_p = top_p; p.sample = sample; p.guidance = guidance; p.state = state; p.out = out;
+    const int lds = n * (4 + 4 + 4 + 1);
+    const unsigned nthreads = (unsigned)(n / 2 < 256 ? 256 : n / 2 > 1024 ? 1024 : n / 2);
+    DVQ_DISPATCH_DTYPE(dtype, TT, sample_constrained_kernel<TT, GUIDED><<<dim3((unsigned)B), dim3(nthreads), lds, (hipStream_t)stream>>>(p););
+    DVQ_CHECK_LAUNCH(GUIDED ? "sample_guided" : "sample_constrained");
+    if (sample) {
+        sample_bump_kernel<<<dim3(1), dim3(64), 0, (hipStream_t)stream>>>(state);
+        DVQ_CHECK_LAUNCH("sample_bump");
+    }
+    return DVQ_OK;
 }
 
 }  // namespace
@@ -1041,24 +1104,21 @@ extern "C" int dvq_sample_constrained(const void* logits, int dtype, int64_t B, 
     DVQ_REQUIRE(logits && out && B > 0 && V > 0 && V <= 2048 && ldl >= V && temperature > 0.f && (!sample || state != nullptr) &&
                     (forbid_idx == nullptr || (n_forbid >= 0 && forbid_ld >= n_forbid)) && pad_code >= 0 && pad_code < V && top_k >= 0,
                 DVQ_EINVAL, "dvq_sample_constrained: bad arguments (V <= 2048)");
-    SampleParams p{};
-    p.logits = logits; p.ldl = ldl; p.V = (int)V;
-    int n = 256;
-    while (n < V) n <<= 1;
-    p.N = n;
-    p.inv_temperature = 1.f / temperature;
-    p.forbid_idx = forbid_idx; p.forbid_ld = forbid_ld; p.n_forbid = forbid_idx ? (int)n_forbid : 0;
-    p.forbid_from = (int)(forbid_from < 0 || forbid_from > V ? V : forbid_from);
-    for (int i = 0; i < 4; ++i) p.codes[i] = forbid_codes4 ? (int)forbid_codes4[i] : -1;
-    p.keep_code = (int)keep_code; p.late_forbid_code = (int)late_forbid_code; p.pad_code = (int)pad_code;
-    p.finished = finished; p.top_k = top_k; p.top_p = top_p; p.sample = sample; p.state = state; p.out = out;
-    const int lds = n * (4 + 4 + 4 + 1);
-    const unsigned nthreads = (unsigned)(n / 2 < 256 ? 256 : n / 2 > 1024 ? 1024 : n / 2);
-    DVQ_DISPATCH_DTYPE(dtype, TT, sample_constrained_kernel<TT><<<dim3((unsigned)B), dim3(nthreads), lds, (hipStream_t)stream>>>(p););
-    DVQ_CHECK_LAUNCH("sample_constrained");
-    if (sample) {
-        sample_bump_kernel<<<dim3(1), dim3(64), 0, (hipStream_t)stream>>>(state);
-        DVQ_CHECK_LAUNCH("sample_bump");
-    }
-    return DVQ_OK;
+    return sample_constrained_launch<false>(logits, dtype, B, V, ldl, temperature, 0.f, forbid_idx, n_forbid, forbid_ld, forbid_from,
+                                            forbid_codes4, keep_code, late_forbid_code, pad_code, finished, top_k, top_p, sample, state,
+                                            out, stream);
+}
+
+extern "C" int dvq_sample_guided(const void* logits, int dtype, int64_t B, int64_t V, int64_t ldl, float guidance, float temperature,
+                                 const int64_t* forbid_idx, int64_t n_forbid, int64_t forbid_ld, int64_t forbid_from,
+                                 const int64_t* forbid_codes4, int64_t keep_code, int64_t late_forbid_code, int64_t pad_code,
+                                 const float* finished, int top_k, float top_p, int sample, uint64_t* state, int64_t* out,
+                                 dvq_stream_t stream) {
+    DVQ_REQUIRE(logits && out && B > 0 && V > 0 && V <= 2048 && ldl >= V && temperature > 0.f && (!sample || state != nullptr) &&
+                    (forbid_idx == nullptr || (n_forbid >= 0 && forbid_ld >= n_forbid)) && pad_code >= 0 && pad_code < V && top_k >= 0 &&
+                    std::isfinite(guidance),
+                DVQ_EINVAL, "dvq_sample_guided: bad arguments (V <= 2048, finite guidance)");
+    return sample_constrained_launch<true>(logits, dtype, B, V, ldl, temperature, guidance, forbid_idx, n_forbid, forbid_ld, forbid_from,
+                                           forbid_codes4, keep_code, late_forbid_code, pad_code, finished, top_k, top_p, sample, state,
+                                           out, stream);
 }

@@ -1164,13 +1164,9 @@ def attn_decode(q, kcache, vcache, n_head, t, scale):
     return out
 
 
-def sample_constrained(logits2d, temperature, pad_code, state, forbid_idx=None, forbid_from=None, forbid_codes=(), keep_code=-1,
-                       late_forbid_code=-1, finished=None, top_k=None, top_p=None, sample=True):
-    """one token per row of logits2d [B, V] (V <= 2048) under Dualformer's constraint rules, top-k / top-p, multinomial or top-1:
-    ONE launch (csrc/transformer.hip: dvq_sample_constrained).  forbid_idx int64 [B, L] lists columns to mask per row; finished fp32
-    [B] (non-zero: the row only keeps pad_code); state = int64 [2] device generator state (key, counter).  -> int64 [B, 1]"""
-    b, v = logits2d.shape
-    out = torch.empty(b, 1, dtype=torch.int64, device=logits2d.device)
+def _sample_args(logits2d, forbid_idx, forbid_from, forbid_codes, finished):
+    """marshalled constraint arguments of dvq_sample_constrained / dvq_sample_guided"""
+    v = logits2d.shape[1]
     codes = (C.c_int64 * 4)(*([int(c) for c in forbid_codes] + [-1] * (4 - len(forbid_codes))))
     fi = None
     n_forbid = ld = 0
@@ -1181,11 +1177,48 @@ def sample_constrained(logits2d, temperature, pad_code, state, forbid_idx=None, 
     if finished is not None:
         fin = finished.reshape(-1).to(torch.float32).contiguous()
     assert logits2d.is_cuda and logits2d.stride(1) == 1, "row-major logits (a column slice of a padded matrix is fine)"
+    return fi, n_forbid, ld, v if forbid_from is None else int(forbid_from), codes, fin
+
+
+def sample_constrained(logits2d, temperature, pad_code, state, forbid_idx=None, forbid_from=None, forbid_codes=(), keep_code=-1,
+                       late_forbid_code=-1, finished=None, top_k=None, top_p=None, sample=True):
+    """one token per row of logits2d [B, V] (V <= 2048) under Dualformer's constraint rules, top-k / top-p, multinomial or top-1:
+    ONE launch (csrc/transformer.hip: dvq_sample_constrained).  forbid_idx int64 [B, L] lists columns to mask per row; finished fp32
+    [B] (non-zero: the row only keeps pad_code); state = int64 [2] device generator state (key, counter).  -> int64 [B, 1]"""
+    b, v = logits2d.shape
+    out = torch.empty(b, 1, dtype=torch.int64, device=logits2d.device)
+    fi, n_forbid, ld, ff, codes, fin = _sample_args(logits2d, forbid_idx, forbid_from, forbid_codes, finished)
     check(lib().dvq_sample_constrained(_praw(logits2d), dt(logits2d), b, v, logits2d.stride(0), float(temperature), _p(fi), n_forbid, ld,
-                                       v if forbid_from is None else int(forbid_from), codes, int(keep_code), int(late_forbid_code),
-                                       int(pad_code), _p(fin), int(top_k or 0), float(top_p or 0.0), int(bool(sample)), _p(state), _p(out),
-                                       _s()), "dvq_sample_constrained")
+                                       ff, codes, int(keep_code), int(late_forbid_code), int(pad_code), _p(fin), int(top_k or 0),
+                                       float(top_p or 0.0), int(bool(sample)), _p(state), _p(out), _s()), "dvq_sample_constrained")
     return out
+
+
+def sample_guided(logits2d, guidance, temperature, pad_code, state, forbid_idx=None, forbid_from=None, forbid_codes=(), keep_code=-1,
+                  late_forbid_code=-1, finished=None, top_k=None, top_p=None, sample=True):
+    """classifier-free-guided sample_constrained (csrc/transformer.hip: dvq_sample_guided): logits2d [2B, V], rows [0, B) conditional,
+    rows [B, 2B) unconditional; the pipeline runs on fmaf(1 - guidance, u, guidance * c) per pair.  forbid_idx / finished may be the
+    2B-row tensors (rows [0, B) are read).  -> int64 [2B, 1], the pair's token in row i and row i + B"""
+    b2, v = logits2d.shape
+    assert b2 % 2 == 0, "guided sampling takes [conditional ; unconditional] rows"
+    out = torch.empty(b2, 1, dtype=torch.int64, device=logits2d.device)
+    fi, n_forbid, ld, ff, codes, fin = _sample_args(logits2d, forbid_idx, forbid_from, forbid_codes, finished)
+    check(lib().dvq_sample_guided(_praw(logits2d), dt(logits2d), b2 // 2, v, logits2d.stride(0), float(guidance), float(temperature),
+                                  _p(fi), n_forbid, ld, ff, codes, int(keep_code), int(late_forbid_code), int(pad_code), _p(fin),
+                                  int(top_k or 0), float(top_p or 0.0), int(bool(sample)), _p(state), _p(out), _s()), "dvq_sample_guided")
+    return out
+
+
+def label_dropout(labels, p, null_label, seed):
+    """int64 [B] class labels -> labels with each replaced by null_label with probability p (dvq_label_dropout: dvq_dropout's hash of
+    (seed, element index), so a seed reproduces the decisions)"""
+    lab = labels.reshape(-1).to(torch.int64).contiguous()
+    out = torch.empty_like(lab)
+    if lab.numel() == 0:
+        return out.view(labels.shape)
+    check(lib().dvq_label_dropout(_p(lab), lab.numel(), float(p), int(null_label), int(seed) & 0xFFFFFFFFFFFFFFFF, _p(out), _s()),
+          "dvq_label_dropout")
+    return out.view(labels.shape)
 
 
 # ---------------------------------------------------------------------------------------------

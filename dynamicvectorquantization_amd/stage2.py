@@ -388,10 +388,12 @@ class _SamplerMixin:
     def transfer_sampled_coarse_position_to_remain_fine_position(self, coarse_position):
         return self._fine_positions_of(1 - self._coarse_cells_drawn(coarse_position), coarse_position)
 
-    def _draw_rule(self, logits2d, temperature, sample, k, p, rule):
+    def _draw_rule(self, logits2d, temperature, sample, k, p, rule, cfg=None):
         """one token per row under constraint `rule` = (kind, sampled positions or None, done flags): ONE fused launch
         (kernels.sample_constrained: mask rules + top-k / top-p + softmax + multinomial / top-1) when the logits are on the device;
-        DVQ_SAMPLER=torch (or a vocabulary beyond the kernel's 2048 columns) keeps the op-by-op path the golden tests pin"""
+        DVQ_SAMPLER=torch (or a vocabulary beyond the kernel's 2048 columns) keeps the op-by-op path the golden tests pin.
+        cfg = classifier-free-guidance scale or None: the rows are [conditional ; unconditional] pairs, each pair draws from the
+        guided logits (kernels.sample_guided) and its token is returned in both of its rows"""
         kind, sampled, done = rule
         if logits2d.is_cuda and logits2d.shape[1] <= 2048 and logits2d.dtype in (torch.float32, torch.bfloat16) and \
                 os.environ.get("DVQ_SAMPLER", "fused") != "torch":
@@ -415,11 +417,13 @@ class _SamplerMixin:
             kw = self._fused_rule(kind)
             if kind != "content":
                 kw["forbid_idx"] = sampled
+            if cfg is not None:
+                return K.sample_guided(logits2d, cfg, temperature, state=st, finished=done, top_k=k, top_p=p, sample=sample, **kw)
             return K.sample_constrained(logits2d, temperature, state=st, finished=done, top_k=k, top_p=p, sample=sample, **kw)
         fn = {"coarse_pos": lambda lg: self.avoid_repeat_or_enforce_pad_for_coarse_position(lg, sampled, done),
               "fine_pos": lambda lg: self.avoid_repeat_or_enforce_pad_for_fine_position(lg, sampled, done),
               "content": lambda lg: self.avoid_special_or_enforce_pad_for_content(lg, done)}[kind]
-        return self._draw(logits2d.unsqueeze(1), temperature, sample, k, p, fn)
+        return self._draw(logits2d.unsqueeze(1), temperature, sample, k, p, fn, cfg)
 
     def _fused_rule(self, kind):
         """the three mask rules (avoid_repeat_or_enforce_pad_for_* / avoid_special_or_enforce_pad_for_content above) as arguments of
@@ -433,18 +437,29 @@ class _SamplerMixin:
         return dict(pad_code=self.content_pad_code, forbid_codes=(self.content_pad_code, self.content_eos_code, self.content_sos_code))
 
     @staticmethod
-    def _draw(logits, temperature, sample, k, p, constrain):
-        logits = constrain(logits[:, -1, :] / temperature)
+    def _draw(logits, temperature, sample, k, p, constrain, cfg=None):
+        logits = logits[:, -1, :]
+        if cfg is not None:
+            # guided pairs (dvq_sample_guided restated in torch ops): g = (1 - s) u + s c in fp32, then in the logits' dtype like the
+            # rest of this path (s = 1: exactly c, s = 0: exactly u); masked with the rules of the conditional rows -- both halves
+            # carry the same history, so [g ; g] through the 2B-row rules gives them -- and the pair's token returned in both rows
+            b = logits.shape[0] // 2
+            c, u = logits[:b].float(), logits[b:].float()
+            g = (u * (1.0 - float(cfg)) + c * float(cfg)).to(logits.dtype)
+            logits = constrain(torch.cat([g, g]) / temperature)[:b]
+        else:
+            logits = constrain(logits / temperature)
         if k is not None:
             logits = top_k_logits(logits, k)
         probs = torch.softmax(logits, dim=-1)
         if p is not None:
             probs = top_p_logits(probs, p)
-        return torch.multinomial(probs, num_samples=1) if sample else torch.topk(probs, k=1, dim=-1)[1]
+        ix = torch.multinomial(probs, num_samples=1) if sample else torch.topk(probs, k=1, dim=-1)[1]
+        return torch.cat([ix, ix]) if cfg is not None else ix
 
     @torch.no_grad()
     def _sample_cached(self, c_coarse, c_fine, c_pos_coarse, c_pos_fine, c_seg_coarse, c_seg_fine, temperature, sample, top_k, top_p,
-                       top_k_pos, top_p_pos, fix_fine_position):
+                       top_k_pos, top_p_pos, fix_fine_position, cfg=None):
         """the same sampler with K/V caches: every step feeds ONE new row to each transformer instead of recomputing the whole
         prefix (the reference's O(T^2) schedule).  The content transformer's coarse rows are re-filled once when the fine
         stream starts, because the reference pairs them with different update positions in the two phases
@@ -476,11 +491,11 @@ class _SamplerMixin:
         done = torch.zeros(b, 1, device=dev)
         while not torch.all(done.bool()):
             pl = st.position_rows(x_c[:, -1:], x_pc[:, -1:], cpe, None, x_sc[:, -1:] if seg else None)
-            ix_pos = self._draw_rule(pl, temperature, sample, top_k_pos, top_p_pos, ("coarse_pos", x_pc, done))
+            ix_pos = self._draw_rule(pl, temperature, sample, top_k_pos, top_p_pos, ("coarse_pos", x_pc, done), cfg)
             x_pc = torch.cat((x_pc, ix_pos), dim=1)
             done = done + (ix_pos == self.coarse_position_eos_code)
             cl = st.content_rows(ix_pos, cpe)
-            ix = self._draw_rule(cl, temperature, sample, top_k, top_p, ("content", None, done))
+            ix = self._draw_rule(cl, temperature, sample, top_k, top_p, ("content", None, done), cfg)
             if seg:
                 x_sc = torch.cat([x_sc, zeros1], dim=1)
             x_c = torch.cat((x_c, ix), dim=1)
@@ -514,7 +529,7 @@ class _SamplerMixin:
                 ix_pos = plan[:, j].unsqueeze(-1)
                 j += 1
             else:
-                ix_pos = self._draw_rule(pl, temperature, sample, top_k_pos, top_p_pos, ("fine_pos", taken, done))
+                ix_pos = self._draw_rule(pl, temperature, sample, top_k_pos, top_p_pos, ("fine_pos", taken, done), cfg)
                 taken = torch.cat([taken, ix_pos], dim=1)
             x_pf = torch.cat((x_pf, ix_pos), dim=1)
             done = done + (ix_pos == self.fine_position_eos_code)
@@ -529,7 +544,7 @@ class _SamplerMixin:
             if cl is None:                                   # no fine <sos>: the first fine content comes from the last coarse row
                 st.reset_content()
                 cl = st.content_rows(x_pc[:, :n_coarse], cpe)
-            ix = self._draw_rule(cl, temperature, sample, top_k, top_p, ("content", None, done))
+            ix = self._draw_rule(cl, temperature, sample, top_k, top_p, ("content", None, done), cfg)
             x_f = torch.cat((x_f, ix), dim=1)
             if seg:
                 x_sf = torch.cat([x_sf, zeros1 + 1], dim=1)
@@ -617,10 +632,26 @@ class _SamplerMixin:
     @torch.no_grad()
     def sample_from_scratch(self, c_coarse, c_fine, c_pos_coarse, c_pos_fine, c_seg_coarse, c_seg_fine, temperature=1.0, sample=True,
                             top_k=None, top_p=None, top_k_pos=None, top_p_pos=None, process=True, fix_fine_position=False,
-                            kv_cache=True):
-        if kv_cache and not self.transformer.training:
-            return self._sample_cached(c_coarse, c_fine, c_pos_coarse, c_pos_fine, c_seg_coarse, c_seg_fine, temperature, sample,
-                                       top_k, top_p, top_k_pos, top_p_pos, fix_fine_position)
+                            kv_cache=True, cfg_scale=None):
+        """cfg_scale = None: plain sampling of the batch.  A float: classifier-free guidance with that scale for every position and
+        content draw -- the six conditioning tensors are [conditional ; unconditional] halves of an even batch
+        (ClassDualformer.guided_conditioning), every draw of pair i uses (1 - s) u_i + s c_i and writes its token to both rows, and
+        the conditional half (B of the 2B rows) is returned"""
+        if cfg_scale is not None:
+            cfg_scale = float(cfg_scale)
+            if c_coarse.size(0) % 2:
+                raise ValueError(f"guided sampling takes [conditional ; unconditional] halves: batch {c_coarse.size(0)} is odd")
+        args = (c_coarse, c_fine, c_pos_coarse, c_pos_fine, c_seg_coarse, c_seg_fine, temperature, sample, top_k, top_p, top_k_pos,
+                top_p_pos, fix_fine_position, cfg_scale)
+        res = self._sample_cached(*args) if kv_cache and not self.transformer.training else self._sample_full(*args)
+        if cfg_scale is not None:
+            res = tuple(r[:c_coarse.size(0) // 2] for r in res)
+        return res
+
+    @torch.no_grad()
+    def _sample_full(self, c_coarse, c_fine, c_pos_coarse, c_pos_fine, c_seg_coarse, c_seg_fine, temperature, sample, top_k, top_p,
+                     top_k_pos, top_p_pos, fix_fine_position, cfg=None):
+        """the reference's sampler: every step recomputes the whole prefix (kv_cache=False, or a transformer in training mode)"""
         tr = self.transformer
         x_c, x_pc, x_sc = c_coarse, c_pos_coarse, c_seg_coarse
         if self.activate_sos_for_fine_sequence:
@@ -634,11 +665,11 @@ class _SamplerMixin:
         while not torch.all(done.bool()):
             hidden, pl = tr.sample_coarse_position(coarse_content=x_c, coarse_position=x_pc, coarse_seg=x_sc)
             ix_pos = self._draw(pl, temperature, sample, top_k_pos, top_p_pos,
-                                lambda lg: self.avoid_repeat_or_enforce_pad_for_coarse_position(lg, x_pc, done))
+                                lambda lg: self.avoid_repeat_or_enforce_pad_for_coarse_position(lg, x_pc, done), cfg)
             x_pc = torch.cat((x_pc, ix_pos), dim=1)
             done = done + (ix_pos == self.coarse_position_eos_code)
             _, cl = tr.sample_coarse_content(coarse_content=None, coarse_position=x_pc, coarse_seg=None, position_hidden=hidden)
-            ix = self._draw(cl, temperature, sample, top_k, top_p, lambda lg: self.avoid_special_or_enforce_pad_for_content(lg, done))
+            ix = self._draw(cl, temperature, sample, top_k, top_p, lambda lg: self.avoid_special_or_enforce_pad_for_content(lg, done), cfg)
             if self.activate_segment:
                 x_sc = torch.cat([x_sc, zeros1], dim=1)
             x_c = torch.cat((x_c, ix), dim=1)
@@ -650,13 +681,13 @@ class _SamplerMixin:
                 hidden, pl = tr.sample_fine_position(coarse_content=x_c, fine_content=x_f, coarse_position=x_pc, fine_position=x_pf,
                                                      coarse_seg=x_sc, fine_seg=x_sf)
                 ix_pos = self._draw(pl, temperature, sample, top_k_pos, top_p_pos,
-                                    lambda lg: self.avoid_repeat_or_enforce_pad_for_fine_position(lg, taken, done))
+                                    lambda lg: self.avoid_repeat_or_enforce_pad_for_fine_position(lg, taken, done), cfg)
                 x_pf = torch.cat((x_pf, ix_pos), dim=1)
                 taken = torch.cat([taken, ix_pos], dim=1)
                 done = done + (ix_pos == self.fine_position_eos_code)
                 _, cl = tr.sample_fine_content(coarse_content=x_c, fine_content=x_f, coarse_position=x_pc, fine_position=x_pf,
                                                coarse_seg=x_sc, fine_seg=x_sf, position_hidden=hidden)
-                ix = self._draw(cl, temperature, sample, top_k, top_p, lambda lg: self.avoid_special_or_enforce_pad_for_content(lg, done))
+                ix = self._draw(cl, temperature, sample, top_k, top_p, lambda lg: self.avoid_special_or_enforce_pad_for_content(lg, done), cfg)
                 x_f = torch.cat((x_f, ix), dim=1)
                 if self.activate_segment:
                     x_sf = torch.cat([x_sf, zeros1 + 1], dim=1)
@@ -670,7 +701,7 @@ class _SamplerMixin:
                 done = done + (ix_pos == self.fine_position_eos_code)
                 _, cl = tr.sample_fine_content(coarse_content=x_c, fine_content=x_f, coarse_position=x_pc, fine_position=x_pf,
                                                coarse_seg=x_sc, fine_seg=x_sf, position_hidden=None)
-                ix = self._draw(cl, temperature, sample, top_k, top_p, lambda lg: self.avoid_special_or_enforce_pad_for_content(lg, done))
+                ix = self._draw(cl, temperature, sample, top_k, top_p, lambda lg: self.avoid_special_or_enforce_pad_for_content(lg, done), cfg)
                 x_f = torch.cat((x_f, ix), dim=1)
                 if self.activate_segment:
                     x_sf = torch.cat([x_sf, zeros1 + 1], dim=1)
@@ -685,16 +716,63 @@ for _name, _fn in list(vars(_SamplerMixin).items()):
         setattr(_SamplerMixinBase, _name, _fn)
 
 
+def null_label_table_errors(transformer_params, provider_params):
+    """the embedding tables that lack the null-label row of classifier-free guidance.  The null label is n_classes, so its start
+    tokens are threshold_* + n_classes (ClassAwareSOSProvider.encode); each table must be larger than that id.  -> list of
+    messages (empty: every table has the row)"""
+    n = int(provider_params["n_classes"])
+    checks = [("vocab_size", "threshold_content"), ("coarse_position_size", "threshold_coarse_position")]
+    if provider_params.get("fine_seg_sos") is not None:            # ClassAwareSOSProvider emits fine start tokens
+        checks.append(("fine_position_size", "threshold_fine_position"))
+    errors = []
+    for table, thr in checks:
+        size, need = int(transformer_params[table]), int(provider_params[thr]) + n + 1
+        if size < need:
+            errors.append(f"{table} = {size} has no null-label row ({thr} {provider_params[thr]} + n_classes {n} needs {table} >= {need})")
+    return errors
+
+
 class ClassDualformer(Dualformer):
     """models/stage2_dynamic/dqtransformer_class2_entropy.py: class-conditional variant.  The start tokens are the class
     label shifted above the code / position vocabularies (ClassAwareSOSProvider), so the sampler masks every id above
-    <eos> instead of a single <sos> id, and the transferred fine-position stream starts with the label's position token."""
+    <eos> instead of a single <sos> id, and the transferred fine-position stream starts with the label's position token.
 
-    def __init__(self, transformer_config, first_stage_config, class_cond_stage_config, permuter_config=None, **kw):
+    Classifier-free guidance (docs/design/14-guidance.md): the null label is n_classes.  cond_drop_prob > 0 replaces each training
+    label by it with that probability (kernels.label_dropout); guided_conditioning + sample_from_scratch(cfg_scale=s) sample with
+    guidance.  Both need one null row per table beyond the reference's sizes (null_label_table_errors)."""
+
+    def __init__(self, transformer_config, first_stage_config, class_cond_stage_config, permuter_config=None, cond_drop_prob=0.0, **kw):
         super().__init__(transformer_config, first_stage_config, uncond_stage_config=class_cond_stage_config,
                          permuter_config=permuter_config, **kw)
         self.cond_stage_key = "class_label"
         del self.content_sos_code, self.fine_position_sos_code
+        self.n_classes = int(class_cond_stage_config["params"]["n_classes"])
+        self.null_label = self.n_classes
+        self.cond_drop_prob = float(cond_drop_prob)
+        if not 0.0 <= self.cond_drop_prob <= 1.0:
+            raise ValueError(f"cond_drop_prob = {cond_drop_prob} is not a probability")
+        self._null_row_errors = null_label_table_errors(transformer_config["params"], class_cond_stage_config["params"])
+        if self.cond_drop_prob > 0.0:
+            self._require_null_rows("cond_drop_prob > 0")
+
+    def _require_null_rows(self, what):
+        if self._null_row_errors:
+            raise ValueError(f"{what} needs a null-label row in every embedding table: " + "; ".join(self._null_row_errors))
+
+    def training_step(self, batch, batch_idx):
+        if self.training and self.cond_drop_prob > 0.0:            # validation / eval never drop
+            from . import runtime as rt
+            batch = dict(batch)
+            batch[self.cond_stage_key] = K.label_dropout(batch[self.cond_stage_key], self.cond_drop_prob, self.null_label,
+                                                         rt.next_dropout_seed())
+        return super().training_step(batch, batch_idx)
+
+    @torch.no_grad()
+    def guided_conditioning(self, labels):
+        """the six start-token tensors of the 2B batch [labels ; null label] for sample_from_scratch(cfg_scale=...)"""
+        self._require_null_rows("guided sampling")
+        labels = labels.reshape(-1).long()
+        return self.encode_to_c(torch.cat([labels, torch.full_like(labels, self.null_label)]))
 
     def get_xc(self, batch, N=None):
         x, c = self.get_input(batch, self.first_stage_key), batch[self.cond_stage_key]

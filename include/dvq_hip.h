@@ -42,7 +42,8 @@ enum { DVQ_F32 = 0, DVQ_BF16 = 1 };
 enum { DVQ_OK = 0, DVQ_EINVAL = -1, DVQ_ESHAPE = -2, DVQ_EARCH = -3, DVQ_ELAUNCH = -4, DVQ_EWORKSPACE = -5 };
 
 const char* dvq_last_error(void);
-int dvq_version(void);     /* 110: dvq_recon_metrics (+ _workspace_bytes), dvq_code_histogram (reconstruction evaluation);
+int dvq_version(void);     /* 111: dvq_sample_guided (classifier-free-guided constrained draw), dvq_label_dropout (null-label dropout);
+                            * 110: dvq_recon_metrics (+ _workspace_bytes), dvq_code_histogram (reconstruction evaluation);
                             * 109: round 5 (dvq_conv2d_fwd_x3 / dvq_conv2d_dgrad_x3: fp32x3 3 x 3 convolutions on the halo kernel, fp32 output);
                             * 108: round 5 (dvq_split_bf16_planes, dvq_conv2d_wgrad_oihw_x3: fp32x3 weight gradients on the bf16 kernels);
                             * 107: round 5 (dvq_lpips_head_drop; probe modes compiled out of the product library: -DDVQ_PROBES);
@@ -486,6 +487,17 @@ int dvq_sample_constrained(const void* logits, int dtype, int64_t B, int64_t V, 
                            const int64_t* forbid_codes4, int64_t keep_code, int64_t late_forbid_code, int64_t pad_code,
                            const float* finished, int top_k, float top_p, int sample, uint64_t* state, int64_t* out,
                            dvq_stream_t stream);
+/* Classifier-free-guided form of dvq_sample_constrained: B is the number of PAIRS.  logits rows [0, B) are the conditional logits c,
+ * rows [B, 2B) the unconditional (null-class) logits u (row pitch ldl, V <= 2048).  Per pair and column, in fp32,
+ * g = fmaf(1 - guidance, u, guidance * c) (guidance = 1: exactly c; 0: exactly u); then dvq_sample_constrained's pipeline on g
+ * (x 1/temperature, mask rules, top-k, softmax, top-p, draw).  forbid_idx / finished are read for rows [0, B) only (pass the 2B-row
+ * arrays); the uniform of pair i is that of row i; the counter advances once per call.  The token is written to out[i] AND out[i + B]
+ * (out int64 [2B]): both halves of the batch carry the same history.  guidance must be finite. */
+int dvq_sample_guided(const void* logits, int dtype, int64_t B, int64_t V, int64_t ldl, float guidance, float temperature,
+                      const int64_t* forbid_idx, int64_t n_forbid, int64_t forbid_ld, int64_t forbid_from,
+                      const int64_t* forbid_codes4, int64_t keep_code, int64_t late_forbid_code, int64_t pad_code,
+                      const float* finished, int top_k, float top_p, int sample, uint64_t* state, int64_t* out,
+                      dvq_stream_t stream);
 /* Fused causal multi-head self-attention (bf16, head_dim 64 or 128) -- CausalSelfAttention.forward, stackgpt.py:41-69:
  *   out = attn_drop(softmax(causal_mask(q k^T * scale))) v      per (batch, head), scores never materialised.
  * q, k, v, out, dout, dq, dk, dv: [B*T][n_head*head_dim] row-major (head h = columns h*head_dim ..); T % 8 == 0;
@@ -571,6 +583,9 @@ int dvq_decode_stack(const void* layers_dev, int n_layers, int64_t B, int64_t C,
 int dvq_dropout(const void* x, int dtype, int64_t n, float p, uint64_t seed, void* y, dvq_stream_t stream);
 /* y = x + dropout(a), the decisions of dvq_dropout for the same seed (p = 0: y = x + a): residual add + resid_drop of a block in one pass */
 int dvq_dropout_add(const void* x, const void* a, int dtype, int64_t n, float p, uint64_t seed, void* y, dvq_stream_t stream);
+/* Label dropout of classifier-free-guidance training: out[i] = null_label where dvq_dropout's keep hash of (seed, element i) drops
+ * element i (probability p, 0 <= p <= 1; p = 1 drops every label), else labels[i].  labels, out: int64 [B] (may alias) */
+int dvq_label_dropout(const int64_t* labels, int64_t B, float p, int64_t null_label, uint64_t seed, int64_t* out, dvq_stream_t stream);
 
 /* AdamW step whose hyper-parameters are read from DEVICE memory (so that a step captured as a hipGraph follows the LR schedule):
  * hyper[8] = {lr / (1 - beta1^t), beta1, beta2, eps, 1 / sqrt(1 - beta2^t), 1 - lr * weight_decay, unused, unused}.
