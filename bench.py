@@ -12,6 +12,11 @@ two-optimizer step (L1 + LPIPS + adaptive hinge GAN + codebook on the autoencode
 forward and the PatchGAN hinge step -- exactly the work Lightning schedules for the reference); `--objective ae`
 times the autoencoder-only step (L1 + codebook) and says so in `config.objective`.
 Weak scaling: bs/GPU is fixed, value = global images / max-over-ranks time.
+
+A plain run sets up, warms up, times the K steps, writes `--dump-outputs` if asked and prints the result line.  `--full` adds
+everything else the record carries: per-kernel timing and roofline, host issue cost, the autoencoder-only step, the fp32 / fp32x3
+modes, bf16 parity (own weights and the reference goldens), the VQ-argmin micro-benchmark, the CPU baseline and the secondary
+workloads of bench_extra.py.
 """
 from __future__ import annotations
 
@@ -439,6 +444,10 @@ def main():
     ap.add_argument("--reuse-forward", action="store_true",
                     help="discriminator step reuses the generator step's reconstruction instead of a second autoencoder forward "
                          "(NOT the reference's schedule; reported in config.objective)")
+    ap.add_argument("--full", action="store_true",
+                    help="the complete record: besides the headline, per-kernel timing / roofline, host issue cost, the autoencoder-only "
+                         "step, fp32 / fp32x3 modes, parity blocks, VQ-argmin micro-benchmark, CPU baseline and secondary workloads "
+                         "(the --no-* options below switch single blocks of it off)")
     ap.add_argument("--no-ae-only", action="store_true", help="skip the secondary autoencoder-only measurement")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--no-parity", action="store_true", help="skip the bf16-vs-fp32 code-index mismatch block and the block that "
@@ -499,11 +508,13 @@ def main():
             dist.barrier()
         torch.cuda.synchronize()
 
-    def run(objective, steps, warmup, profile, no_graph=args.no_graph, dump=False):
+    def run(objective, steps, warmup, profile, no_graph=args.no_graph, dump=False, after=True):
         """build the model + trainer for `objective`, W untimed + K timed steps; -> (seconds [max over ranks], host issue
         seconds, per-kernel profile of the last timed step, model); dump: model._step_outputs = step_outputs() of one step of the timed
         path from the initial state (the state the timed steps reached differs from run to run: their fp32 atomic reductions do
-        not add in a fixed order, and 20+ training steps -- codebook restarts, Adam -- amplify that)"""
+        not add in a fixed order, and 20+ training steps -- codebook restarts, Adam -- amplify that); after: the untimed steps
+        behind the timed region that the --full figures take (host cost of one step on an idle queue, the per-kernel step when
+        `profile`, the exposed all-reduce time)"""
         torch.manual_seed(0)       # identical initial weights on every rank
         model = instantiate_from_config(full_config(objective, args.bs)).to(dev)
         model.reuse_generator_forward = bool(args.reuse_forward)
@@ -556,8 +567,10 @@ def main():
         for i in range(warmup):
             trainer.train_step(batches[i % nb], SETUP + i)
         if profile:
+            # HIP events for ONE step, created outside the timed region.  Without `after` nothing is timed with them, but the timed
+            # steps have always run beside this pool of a few thousand events, and without it they measure ~0.15 % faster
             barrier()
-            K.profile_prepare(n_launches + 16)          # HIP events for ONE step, created outside the timed region
+            K.profile_prepare(n_launches + 16)
         barrier()
         t0 = time.perf_counter()
         call_s = []
@@ -572,15 +585,23 @@ def main():
         host = sum(fast) / len(fast) * steps
         barrier()
         dt = time.perf_counter() - t0
-        # host cost of handing ONE step to an idle device (no waiting for queue space): outside the timed region
-        t_idle = time.perf_counter()
-        trainer.train_step(batches[0], SETUP + warmup + steps)
-        host_idle = time.perf_counter() - t_idle
-        torch.cuda.synchronize()
+        # The untimed steps behind the timed region run for the --full figures, and also for --dump-outputs alone: the codebook's
+        # restart-row generator advances on the device with every training forward and the state restore of the dump leaves it
+        # alone, so the dumped step draws its restart rows behind these steps, as it always has.
+        post = after or dump
+        host_idle = None
+        if post:
+            # host cost of handing ONE step to an idle device (no waiting for queue space): outside the timed region
+            t_idle = time.perf_counter()
+            trainer.train_step(batches[0], SETUP + warmup + steps)
+            host_idle = time.perf_counter() - t_idle if after else None
+            torch.cuda.synchronize()
         prof = {}
-        if profile:
+        if profile and post:
             # per-kernel HIP-event timing: ONE extra step right after the timed region, launched eagerly (events cannot be
-            # recorded inside a graph replay) -- the same kernels on the same shapes as the replayed steps
+            # recorded inside a graph replay) -- the same kernels on the same shapes as the replayed steps.  For --dump-outputs
+            # alone it runs the same way and reports nothing: the dumped step below is defined behind exactly this sequence (an
+            # untimed eager step in its place measurably widened the run-to-run spread of the dumped losses)
             vq_seen = {}
             orig_fwd = model.quantize.fwd
 
@@ -603,8 +624,10 @@ def main():
                 os.environ["DVQ_SIDE_WGRAD"] = prev_side
             model.quantize.fwd = orig_fwd
             model._vq_seen = (vq_seen["x"], vq_seen["cb"]) if "x" in vq_seen else None
+            if not after:
+                prof = {}
         exposed = None
-        if world > 1 or force_dp:
+        if (world > 1 or force_dp) and post:
             # how long the compute stream sits in the gradient-exchange waits of one step (events around GradBuckets.wait())
             for gb in trainer.buckets:
                 gb.measure = []
@@ -612,7 +635,7 @@ def main():
             trainer.use_graph = False
             trainer.train_step(batches[0], SETUP + warmup + steps + 1)
             torch.cuda.synchronize()
-            exposed = round(sum(a.elapsed_time(b) for gb in trainer.buckets for a, b in gb.measure), 3)
+            exposed = round(sum(a.elapsed_time(b) for gb in trainer.buckets for a, b in gb.measure), 3) if after else None
             for gb in trainer.buckets:
                 gb.measure = None
             trainer.use_graph = was
@@ -621,7 +644,7 @@ def main():
                       "host_enqueue_all_ms_per_step": round(enqueue_all / steps * 1e3, 2),
                       "segments": trainer._graph["sg"].n_segments() if trainer._graph is not None else 0,
                       "replay": rt.step_replay_mode() if trainer._graph is not None else None,
-                      "host_ms_one_step_idle_queue": round(host_idle * 1e3, 2),
+                      "host_ms_one_step_idle_queue": round(host_idle * 1e3, 2) if host_idle is not None else None,
                       "host_call_ms_fast_half": round(host / steps * 1e3, 2),
                       "launches_main_side_waits": trainer._graph["sg"].launch_counts() if trainer._graph is not None else None,
                       "fine_ratio": float(model._logged.get("train_fine_ratio", torch.tensor(float("nan"))))}
@@ -654,7 +677,9 @@ def main():
         model._graph_info = graph_info
         return dt, host, prof, model
 
-    dt_, host_issue, prof, model = run(args.objective, args.steps, args.warmup, True, dump=bool(args.dump_outputs))
+    # (a plain run counts the launches of set-up step 0 too: a counted step runs eagerly and outside the recording's count of
+    # steps with the same signature, so the set-up schedule -- and the recording the timed steps replay -- stays the one of --full)
+    dt_, host_issue, prof, model = run(args.objective, args.steps, args.warmup, True, dump=bool(args.dump_outputs), after=args.full)
     if rank == 0 and args.dump_outputs:
         assert sum(a.nbytes for a in model._step_outputs.values()) <= 64 << 20
         os.makedirs(args.dump_outputs, exist_ok=True)
@@ -664,21 +689,21 @@ def main():
     ratio = model._graph_info.pop("fine_ratio")
     graph_info, vq_seen = model._graph_info, getattr(model, "_vq_seen", None)
     parity = None
-    if rank == 0 and not args.no_parity:
+    if rank == 0 and args.full and not args.no_parity:
         try:
             parity = parity_bf16(model, torch.from_numpy(synth.half_flat_images(args.bs, 256, seed=4321)).to(dev))
         except Exception as e:          # evidence block: never costs the headline line
             parity = {"failed": f"{type(e).__name__}: {str(e)[:160]}"}
 
     parity_ref = None
-    if rank == 0 and not args.no_parity:
+    if rank == 0 and args.full and not args.no_parity:
         try:
             parity_ref = parity_vs_reference(dev)
         except Exception as e:
             parity_ref = {"failed": f"{type(e).__name__}: {str(e)[:160]}"}
 
     ae_only = None
-    if args.objective == "full" and not args.no_ae_only:
+    if args.full and args.objective == "full" and not args.no_ae_only:
         # SURVEY 8d asks for both accountings: the autoencoder-only step (L1 + codebook) beside the complete objective
         del model
         gc.collect()              # (model <-> tape closures are reference cycles: free the first model's saved activations now)
@@ -691,7 +716,7 @@ def main():
         del m2
         gc.collect()
     fp32_mode = fp32x3_mode = None
-    if args.objective == "full" and args.dtype == "bf16" and world == 1 and not args.no_fp32_mode:
+    if args.full and args.objective == "full" and args.dtype == "bf16" and world == 1 and not args.no_fp32_mode:
         # the precisions that meet north_star's tolerance (index-exact, 1e-3) get a throughput and a roofline.
         #   fp32   : every kernel instantiated for fp32 operands, products on v_mfma_f32_32x32x2_f32 (roofline: the fp32 matrix peak)
         #   fp32x3 : the same fp32 tensors, products as three bf16 MFMA passes on two-plane operands (~2^-17 per product; round 5)
@@ -795,18 +820,18 @@ def main():
             "allreduce_exposed_ms": graph_info.get("allreduce_exposed_ms"),
             "roofline": roofline,
             "kernel_families": {k: {"launches": v["launches"], "ms_per_step": round(v["ms"], 3),
-                                    "TFLOPs": round(v["TFLOPs"], 2)} for k, v in fam.items()},
+                                    "TFLOPs": round(v["TFLOPs"], 2)} for k, v in fam.items()} if args.full else None,
         }
         out["ae_only"] = ae_only
         out["parity_bf16"] = parity
         out["parity_bf16_vs_reference"] = parity_ref
         out["fp32_mode"] = fp32_mode
         out["fp32x3_mode"] = fp32x3_mode
-        if not args.no_vq_microbench:
+        if args.full and not args.no_vq_microbench:
             out["vq_argmin"] = vq_microbench(dev, in_training=vq_seen)
-        if world == 1 and not args.no_cpu_baseline:
+        if args.full and world == 1 and not args.no_cpu_baseline:
             out["cpu_baseline"] = cpu_baseline(args.objective)
-        if world == 1 and not args.no_extras and args.objective == "full" and args.bs == 64:
+        if args.full and world == 1 and not args.no_extras and args.objective == "full" and args.bs == 64:
             # BASELINE configs 4 / 5 in the same driver command (compact blocks; bench_extra.py prints the full lines): each runs in
             # its own process after this one has released its memory, inside a time budget
             model = None                           # (already released when the autoencoder-only measurement ran)

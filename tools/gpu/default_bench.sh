@@ -1,11 +1,11 @@
 #!/bin/bash
-# the driver's default command, with its wall time
-cd "${GRAFT_REPO_ROOT:-/root/repo}"; mkdir -p gpurun_out
+# the benchmark's complete record (bench.py --full) with its wall time; the JSON line goes to logs/full_bench.json
+cd "$(dirname "$0")/../.."; mkdir -p logs
 t0=$(date +%s)
-timeout 1500 python bench.py > gpurun_out/default_bench.json 2> gpurun_out/default_bench.err; echo "exit $? wall $(( $(date +%s) - t0 )) s"
+timeout 1500 python bench.py --full > logs/full_bench.json 2> logs/full_bench.err; echo "exit $? wall $(( $(date +%s) - t0 )) s"
 python - <<'P'
 import json
-for l in open("gpurun_out/default_bench.json"):
+for l in open("logs/full_bench.json"):
     if l.startswith("{"):
         d = json.loads(l)
         print(d["value"], d["ms_per_step"], d["steps"], d["warmup"], d["roofline"]["frac"], d["roofline"]["traffic_source"][-110:])
