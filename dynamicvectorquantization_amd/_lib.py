@@ -170,6 +170,8 @@ SIGNATURES = {
     "dvq_recon_metrics_workspace_bytes": (sz, [i64, i64, i64]),
     "dvq_recon_metrics": (i32, [vp, vp, i64, i64, i64, i32, vp, vp, vp, vp, sz, vp]),
     "dvq_code_histogram": (i32, [vp, vp, i64, i64, i64, i64, i64, i64, i32, vp, vp, vp, vp]),
+    "dvq_token_nll": (i32, [vp, i32, i64, i64, i64, vp, i64, vp, vp, vp]),
+    "dvq_nll_segment_sums": (i32, [vp, vp, i64, i64, i64, vp, vp]),
 }
 
 

@@ -1,11 +1,16 @@
 """Reconstruction evaluation of a DQ-VAE: PSNR / SSIM / L1 (+ LPIPS when pretrained weights exist), codebook usage, perplexity
-and tokens per image (docs/design/13-evaluation.md).
+and tokens per image (docs/design/13-evaluation.md); likelihood evaluation of a DQ-Transformer: nats per token, perplexity, top-1 /
+top-5 accuracy per token stream, bits per image and per pixel (docs/design/15-likelihood.md).
 
   * ReconstructionMeter      accumulates batches on the device (csrc/metrics.hip: dvq_recon_metrics, dvq_code_histogram); nothing is
                              copied to the host until summary(), which aggregates in fp64
   * aggregate                the host aggregation of per-image values and code counts (pure numpy: testable without a GPU)
   * evaluate_reconstruction  one model.ae_fwd(x, None) per batch in eval mode under no_grad: reconstruction, code map and grain map
                              of entropy-routed and feature-routed dual / triple grain models from one pass; no EMA update
+
+  * LikelihoodMeter          accumulates Dualformer.score blocks ([B, 4, 4] fp64) on the device, one host copy in summary()
+  * aggregate_likelihood     host aggregation of the per-image stream sums (pure numpy)
+  * evaluate_likelihood      one model.score per batch (teacher forcing, eval mode, no gradient)
 
 `reference_usage` reproduces what the reference's scripts/tools/codebook_usage_dqvae.py:69 prints under the label "usage":
 1 - codes_used / K, i.e. the UNUSED fraction of the codebook.
@@ -162,6 +167,159 @@ def evaluate_reconstruction(model, batches, quantize_u8: bool = True, lpips=None
     s["ema_dead_codes"] = int((ema.detach().cpu().numpy() < 1.0).sum()) if ema is not None else None
     s["dtype"] = dtype_name()
     return s
+
+
+# ---- stage 2: teacher-forced likelihood of a DQ-Transformer (docs/design/15-likelihood.md) ------------------------------------------------
+LIKELIHOOD_STREAMS = ("content_coarse", "content_fine", "position_coarse", "position_fine")     # = StackGPT.SCORE_STREAMS
+_LN2 = float(np.log(2.0))
+
+
+def _div(a, b):
+    return float(a / b) if b > 0 else None
+
+
+def step_losses(sums, content_loss_weight=1.0, position_loss_weight=1.0) -> dict:
+    """the losses Dualformer._step logs for ONE batch, from that batch's [4, 4] stream sums (rows LIKELIHOOD_STREAMS, columns nll
+    sum / tokens / ...): each loss is the mean over the batch's non-ignored targets (F.cross_entropy's reduction), position =
+    (coarse + fine) / 2, loss = content_loss_weight * content + position_loss_weight * position.  A loss without a target is None (the
+    training step would log NaN), and so is everything built on it."""
+    sums = np.asarray(sums, dtype=np.float64)
+    content = _div(sums[0, 0] + sums[1, 0], sums[0, 1] + sums[1, 1])
+    coarse, fine = _div(sums[2, 0], sums[2, 1]), _div(sums[3, 0], sums[3, 1])
+    position = (coarse + fine) / 2 if coarse is not None and fine is not None else None
+    loss = content_loss_weight * content + position_loss_weight * position if content is not None and position is not None else None
+    return {"content_loss": content, "position_loss": position, "coarse_position_loss": coarse, "fine_position_loss": fine, "loss": loss}
+
+
+def aggregate_likelihood(per_image, pixels_per_image=None, content_loss_weight=1.0, position_loss_weight=1.0, batch_sizes=None) -> dict:
+    """host aggregation (fp64, pure numpy) of per-image stream sums [N, 4, 4]: axis 1 = LIKELIHOOD_STREAMS, axis 2 = (sum of the
+    tokens' negative log-likelihoods in nats, tokens, top-1 hits, top-5 hits).
+
+    streams[name]:    nats_per_token = sum / tokens, perplexity = exp(sum / tokens), top1 / top5 = hits / tokens (all None for a stream
+                      without tokens), tokens, tokens_per_image {mean, min, max}
+    nats_per_image:   all four streams' sums / N; bits_per_image = nats / ln 2; bits_per_pixel = bits_per_image / pixels_per_image
+                      (H * W * 3; None when pixels_per_image is not given)
+    loss:             step_losses of the WHOLE set taken as one batch
+    loss_batch_mean:  with batch_sizes (how the N images were grouped, in order): the unweighted mean over batches of each batch's
+                      step_losses -- what an epoch average of the logged validation losses is for equal batch sizes; None for a loss
+                      that some batch lacks"""
+    a = np.asarray(per_image, dtype=np.float64)
+    if a.ndim != 3 or a.shape[1:] != (4, 4):
+        raise ValueError(f"per-image likelihood sums must be [N, 4, 4], got {a.shape}")
+    n = a.shape[0]
+    tot = a.sum(axis=0)
+    streams = {}
+    for i, name in enumerate(LIKELIHOOD_STREAMS):
+        npt = _div(tot[i, 0], tot[i, 1])
+        tok = a[:, i, 1]
+        with np.errstate(over="ignore"):
+            streams[name] = {"nats_per_token": npt, "perplexity": float(np.exp(npt)) if npt is not None else None,
+                             "top1": _div(tot[i, 2], tot[i, 1]), "top5": _div(tot[i, 3], tot[i, 1]), "tokens": int(tot[i, 1]),
+                             "tokens_per_image": {"mean": float(tok.mean()) if n else None, "min": int(tok.min()) if n else None,
+                                                  "max": int(tok.max()) if n else None}}
+    nats = _div(tot[:, 0].sum(), n)
+    bits = nats / _LN2 if nats is not None else None
+    all_tok = a[:, :, 1].sum(axis=1)
+    out = {"n_images": int(n), "streams": streams, "nats_per_image": nats, "bits_per_image": bits,
+           "bits_per_pixel": bits / float(pixels_per_image) if bits is not None and pixels_per_image else None,
+           "pixels_per_image": int(pixels_per_image) if pixels_per_image else None,
+           "tokens_per_image": {"mean": float(all_tok.mean()) if n else None, "min": int(all_tok.min()) if n else None,
+                                "max": int(all_tok.max()) if n else None},
+           "content_loss_weight": float(content_loss_weight), "position_loss_weight": float(position_loss_weight),
+           "loss": step_losses(tot, content_loss_weight, position_loss_weight), "loss_batch_mean": None}
+    if batch_sizes is not None:
+        sizes = [int(b) for b in batch_sizes]
+        if sum(sizes) != n or any(b <= 0 for b in sizes):
+            raise ValueError(f"batch_sizes {sizes} do not partition {n} images")
+        per_batch, i0 = [], 0
+        for b in sizes:
+            per_batch.append(step_losses(a[i0:i0 + b].sum(axis=0), content_loss_weight, position_loss_weight))
+            i0 += b
+        out["loss_batch_mean"] = {k: (float(np.mean([p[k] for p in per_batch])) if all(p[k] is not None for p in per_batch) else None)
+                                  for k in per_batch[0]} if per_batch else None
+    return out
+
+
+class LikelihoodMeter:
+    """Accumulates the [B, 4, 4] blocks of Dualformer.score on the device; summary() makes the one host copy and aggregates in fp64."""
+
+    def __init__(self, content_loss_weight=1.0, position_loss_weight=1.0):
+        self.content_loss_weight, self.position_loss_weight = float(content_loss_weight), float(position_loss_weight)
+        self._blocks = []
+        self.pixels_per_image = None
+
+    def update(self, block, pixels_per_image=None):
+        if block.dim() != 3 or tuple(block.shape[1:]) != (4, 4):
+            raise ValueError(f"LikelihoodMeter.update: expected [B, 4, 4], got {tuple(block.shape)}")
+        self._blocks.append(block)
+        if pixels_per_image is not None:
+            if self.pixels_per_image not in (None, int(pixels_per_image)):
+                raise ValueError("images of different sizes in one likelihood evaluation")
+            self.pixels_per_image = int(pixels_per_image)
+
+    def per_image(self):
+        """[N, 4, 4] fp64 on the host (one copy)"""
+        if not self._blocks:
+            raise ValueError("LikelihoodMeter: no batch was added")
+        return torch.cat(self._blocks, dim=0).cpu().numpy().astype(np.float64)
+
+    def summary(self, per_image: bool = False) -> dict:
+        a = self.per_image()
+        out = aggregate_likelihood(a, self.pixels_per_image, self.content_loss_weight, self.position_loss_weight,
+                                   batch_sizes=[int(b.shape[0]) for b in self._blocks])
+        if per_image:
+            out["per_image"] = a
+        return out
+
+
+def evaluate_likelihood(model, batches, per_image: bool = False) -> dict:
+    """Teacher-forced likelihood of images under a Dualformer / ClassDualformer: one model.score per batch (frozen DQ-VAE -> codes ->
+    permuter -> StackGPT in eval mode, no dropout, no gradient), blocks kept on the device, one host copy at the end.  batches: dicts
+    for model.get_xc ({"image": ..., "class_label": ...}), or bare image tensors for an unconditional model.  Keys: see
+    aggregate_likelihood(), plus dtype; per_image=True adds "per_image", the [N, 4, 4] fp64 array."""
+    meter = LikelihoodMeter(model.content_loss_weight, model.position_loss_weight)
+    with torch.no_grad():
+        for batch in batches:
+            if isinstance(batch, dict):
+                x, c = model.get_xc(batch)
+            elif model.cond_stage_key == model.first_stage_key:
+                x = c = model.get_input({model.first_stage_key: batch}, model.first_stage_key)
+            else:
+                raise ValueError(f"a conditional model needs dict batches with '{model.cond_stage_key}'")
+            meter.update(model.score(x, c), pixels_per_image=int(x.shape[-2]) * int(x.shape[-1]) * 3)
+    s = meter.summary(per_image=per_image)
+    s["dtype"] = dtype_name()
+    return s
+
+
+def load_stage2_model(yaml_path: str, model_path: str = "", device="cuda", seed: int = 0):
+    """the Dualformer of a stage-2 YAML, weights from a checkpoint when given, in eval mode on `device` (seeded initialisation, like
+    load_model).  Returns (model, image size of its first stage)."""
+    from . import config as cfg
+    conf = cfg.load_yaml(yaml_path)
+    torch.manual_seed(seed)
+    model = cfg.instantiate_from_config(conf.model)
+    if not hasattr(model, "score"):
+        raise ValueError(f"{yaml_path}: not a stage-2 (DQ-Transformer) model")
+    if model_path:
+        sd = torch.load(model_path, map_location="cpu")
+        model.load_state_dict(sd["state_dict"] if "state_dict" in sd else sd, strict=False)
+    fs = conf.model.params.first_stage_config.params
+    size = fs.get("image_size") or fs.encoderconfig.params.resolution
+    return model.eval().to(device), int(size)
+
+
+def read_labels(path: str):
+    """int64 class labels, one per image in image order: a .npy array, or a text file of whitespace / comma separated integers"""
+    if path.endswith(".npy"):
+        lab = np.load(path)
+    else:
+        with open(path, "r", encoding="utf-8") as f:
+            lab = np.array([int(v) for v in f.read().replace(",", " ").split()], dtype=np.int64)
+    lab = np.asarray(lab)
+    if lab.ndim != 1 or not np.issubdtype(lab.dtype, np.integer):
+        raise ValueError(f"{path}: expected a 1-d integer array of labels, got {lab.dtype} {lab.shape}")
+    return lab.astype(np.int64)
 
 
 # ---- inputs of the evaluation scripts (scripts/tools/eval_reconstruction.py, codebook_usage_dqvae.py) ---------------------------------

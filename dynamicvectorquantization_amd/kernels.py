@@ -971,6 +971,26 @@ def cross_entropy(logits2d, v, target, ignore_index, loss_sum, count, gscale=Non
     return dl
 
 
+def token_nll(logits2d, v, target, ignore_index):
+    """per-row negative log-likelihood (fp32, natural log) and rank of the target among the first v columns of logits2d [rows, ldl]
+    (fp32 or bf16); ignored rows: nll 0, rank -1 (include/dvq_hip.h, dvq_token_nll).  -> (nll fp32 [rows], rank int32 [rows])"""
+    rows, ldl = logits2d.shape
+    nll = torch.empty(rows, dtype=torch.float32, device=logits2d.device)
+    rank = torch.empty(rows, dtype=torch.int32, device=logits2d.device)
+    check(lib().dvq_token_nll(_p(logits2d), dt(logits2d), rows, v, ldl, _p(target), ignore_index, _p(nll), _p(rank), _s()), "dvq_token_nll")
+    return nll, rank
+
+
+def nll_segment_sums(nll, rank, b, tp, split):
+    """fp64 [b, 2, 4]: (nll sum, tokens, top-1 hits, top-5 hits) of rows [0, split) and [split, tp) of every image, rows laid out
+    [b, tp]; fixed summation order (dvq_nll_segment_sums)"""
+    if nll.numel() != b * tp or rank.numel() != b * tp:
+        raise _lib.DvqError(f"nll_segment_sums: {nll.numel()} / {rank.numel()} rows for [{b}, {tp}]")
+    out = torch.empty(b, 2, 4, dtype=torch.float64, device=nll.device)
+    check(lib().dvq_nll_segment_sums(_p(nll), _p(rank), b, tp, split, _p(out), _s()), "dvq_nll_segment_sums")
+    return out
+
+
 def dropout_add(x, a, p, seed):
     """x + dropout(a) in one pass (p = 0: x + a); same decisions as dropout(a, p, seed)"""
     y = torch.empty_like(x)

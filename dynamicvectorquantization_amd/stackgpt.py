@@ -822,6 +822,28 @@ class StackGPT(nn.Module):
             tfp[:, lc:t] = fine_position_target
         return (tc.view(-1), ign_c), (tcp.view(-1), self.coarse_position_pad_code), (tfp.view(-1), self.fine_position_pad_code)
 
+    # ---- teacher-forced likelihood scoring (docs/design/15-likelihood.md) -----------------------------------------------------------
+    SCORE_STREAMS = ("content_coarse", "content_fine", "position_coarse", "position_fine")
+
+    @torch.no_grad()
+    def score(self, coarse_content, fine_content, coarse_position, fine_position, coarse_seg, fine_seg, content_target,
+              coarse_position_target, fine_position_target, **ignorekwargs):
+        """the arguments of the with-loss forward -> fp64 device tensor [B, 4, 4]: per image and stream (SCORE_STREAMS order) the
+        (sum of the tokens' negative log-likelihoods in nats, tokens, top-1 hits, top-5 hits).  Same forward and same targets /
+        ignore rules (_targets) as the training loss; dropout follows self.training like every forward.  No atomics anywhere behind
+        the logits: the same logits give the same bits."""
+        pl, cl, b, t, tp = self.fwd(coarse_content, fine_content, coarse_position, fine_position, coarse_seg, fine_seg, None)
+        tg = self._targets(b, t, tp, coarse_position.shape[1], content_target, coarse_position_target, fine_position_target, pl.device)
+        vp, vc = self.config.fine_position_size, self.config.vocab_size
+        # content_target = cat(coarse_content, fine_content)[:, 1:] (teacher_forcing_inputs) sits in rows [0, t) of the content target
+        # vector: its first coarse_content.shape[1] - 1 rows are coarse tokens, the fine stream's tokens (its <sos> included) follow
+        split = coarse_content.shape[1] - 1
+        con = K.nll_segment_sums(*K.token_nll(cl, vc, tg[0][0], tg[0][1]), b, tp, split)
+        # the two position losses share the logits and differ in the target vector: each is one segment over all rows
+        cpo = K.nll_segment_sums(*K.token_nll(pl, vp, tg[1][0], tg[1][1]), b, tp, tp)[:, 0]
+        fpo = K.nll_segment_sums(*K.token_nll(pl, vp, tg[2][0], tg[2][1]), b, tp, 0)[:, 1]
+        return torch.stack([con[:, 0], con[:, 1], cpo, fpo], dim=1)
+
 
 class _StackGPTLossFn(torch.autograd.Function):
     """teacher-forced forward + the three cross entropies as one autograd node"""

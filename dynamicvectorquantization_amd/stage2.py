@@ -286,6 +286,22 @@ class Dualformer(_SamplerMixinBase, nn.Module):
         _, z_out = self.encode_to_z(x)
         return self.transformer(**self.teacher_forcing_inputs(z_out, self.encode_to_c(c)))
 
+    @torch.no_grad()
+    def score(self, x, c):
+        """teacher-forced likelihood of the images x under conditioning c (what get_xc returns): fp64 device tensor [B, 4, 4], per
+        image and stream (StackGPT.SCORE_STREAMS) the (nll sum in nats, tokens, top-1 hits, top-5 hits) -- StackGPT.score.  The
+        transformer runs in eval mode (no dropout) whatever mode it is in; every module's training flag is put back as found."""
+        _, z_out = self.encode_to_z(x)
+        inputs = self.teacher_forcing_inputs(z_out, self.encode_to_c(c))
+        on = [m for m in self.transformer.modules() if m.training]        # (already in eval mode, the usual case: nothing to switch)
+        for m in on:
+            m.training = False
+        try:
+            return self.transformer.score(**inputs)
+        finally:
+            for m in on:
+                m.training = True
+
     def shared_step(self, batch, batch_idx):
         x, c = self.get_xc(batch)
         return self(x, c)

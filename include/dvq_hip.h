@@ -42,7 +42,8 @@ enum { DVQ_F32 = 0, DVQ_BF16 = 1 };
 enum { DVQ_OK = 0, DVQ_EINVAL = -1, DVQ_ESHAPE = -2, DVQ_EARCH = -3, DVQ_ELAUNCH = -4, DVQ_EWORKSPACE = -5 };
 
 const char* dvq_last_error(void);
-int dvq_version(void);     /* 111: dvq_sample_guided (classifier-free-guided constrained draw), dvq_label_dropout (null-label dropout);
+int dvq_version(void);     /* 112: dvq_token_nll, dvq_nll_segment_sums (teacher-forced likelihood scoring);
+                            * 111: dvq_sample_guided (classifier-free-guided constrained draw), dvq_label_dropout (null-label dropout);
                             * 110: dvq_recon_metrics (+ _workspace_bytes), dvq_code_histogram (reconstruction evaluation);
                             * 109: round 5 (dvq_conv2d_fwd_x3 / dvq_conv2d_dgrad_x3: fp32x3 3 x 3 convolutions on the halo kernel, fp32 output);
                             * 108: round 5 (dvq_split_bf16_planes, dvq_conv2d_wgrad_oihw_x3: fp32x3 weight gradients on the bf16 kernels);
@@ -636,6 +637,22 @@ int dvq_recon_metrics(const float* x, const float* y, int64_t B, int64_t H, int6
                       double* ssim, void* ws, size_t ws_bytes, dvq_stream_t stream);
 int dvq_code_histogram(const int64_t* idx, const int64_t* grain, int64_t B, int64_t Hf, int64_t Wf, int64_t hg, int64_t wg, int64_t K,
                        int G, int64_t* counts, int64_t* tokens, int64_t* invalid, dvq_stream_t stream);
+
+/* ---- likelihood scoring of the DQ-Transformer (docs/design/15-likelihood.md; no reference kernel: it logs batch-mean losses only) ------
+ * dvq_token_nll: logits [rows][ldl] of `dtype`, the first V columns are used (columns V .. ldl are padding and never enter a result);
+ *   target int64 [rows].  Per row, in fp32 with the maximum subtracted and the natural logarithm:
+ *   nll[r]  = log(sum_{c < V} exp(x[c] - max)) - (x[target] - max);
+ *   rank[r] = #{c < V : x[c] > x[target]} + #{c < target : x[c] == x[target]}  (0 = the target is the top-1 guess; ties go to the
+ *             lower column index, the order of a stable descending sort);
+ *   target[r] == ignore_index: nll = 0, rank = -1.  Any other target outside [0, V): nll = NaN, rank = V (no column is read for it).
+ *   -inf logits in other columns contribute 0.  Each row is read once (plus one re-read of x[target] when the rows are not 16-byte
+ *   aligned or V > 2048) and written by one lane: no atomics, no [rows, V] temporary, bitwise reproducible.  Any V >= 1.
+ * dvq_nll_segment_sums: rows laid out [B][Tp]; out fp64 [B][2][4] = (sum of nll, tokens, top-1 hits (rank == 0), top-5 hits
+ *   (rank < 5)) over the rows with rank >= 0 of segment 0 = [0, split) and segment 1 = [split, Tp), 0 <= split <= Tp.  One workgroup per
+ *   (image, segment), fixed summation order in fp64: two launches on the same input give the same bits. */
+int dvq_token_nll(const void* logits, int dtype, int64_t rows, int64_t V, int64_t ldl, const int64_t* target, int64_t ignore_index,
+                  float* nll, int32_t* rank, dvq_stream_t stream);
+int dvq_nll_segment_sums(const float* nll, const int32_t* rank, int64_t B, int64_t Tp, int64_t split, double* out, dvq_stream_t stream);
 
 #ifdef __cplusplus
 }
