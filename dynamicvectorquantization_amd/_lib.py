@@ -40,6 +40,7 @@ class PackEntry(C.Structure):
 # name -> (restype, argtypes); mirrors include/dvq_hip.h one to one
 SIGNATURES = {
     "dvq_last_error": (C.c_char_p, []),
+    "dvq_last_kernel": (C.c_char_p, []),
     "dvq_version": (i32, []),
     "dvq_check_device": (i32, []),
     "dvq_set_deterministic": (i32, [i32]),
@@ -141,18 +142,21 @@ SIGNATURES = {
     "dvq_embed_scatter_add": (i32, [vp, i64, vp, i32, i64, i64, i64, i64, i64, i64, i64, vp, vp]),
     "dvq_cross_entropy": (i32, [vp, i32, i64, i64, i64, vp, i64, vp, vp, vp, vp, vp]),
     "dvq_attn_decode": (i32, [vp, vp, vp, i32, i64, i64, i64, i64, i64, f32, vp, vp]),
+    "dvq_attn_causal_ok": (i32, [i32, i64, i64, i32, i32]),
     "dvq_attn_causal_scratch_bytes": (i64, [i64, i64, i32, i32, i32]),
     "dvq_attn_causal_mask_bytes": (i64, [i64, i64, i32]),
     "dvq_attn_causal_fwd": (i32, [vp, vp, vp, i32, i64, i64, i32, i32, f32, f32, C.c_uint64, vp, vp, vp, vp, vp]),
     "dvq_attn_causal_bwd": (i32, [vp, vp, vp, vp, vp, vp, i32, i64, i64, i32, i32, f32, f32, C.c_uint64, vp, vp, vp, vp, vp, vp]),
     "dvq_attn_causal_fwd_ld": (i32, [vp, vp, vp, i64, i32, i64, i64, i32, i32, f32, f32, C.c_uint64, vp, vp, vp, vp]),
     "dvq_attn_causal_bwd_ld": (i32, [vp, vp, vp, i64, vp, vp, vp, i32, i64, i64, i32, i32, f32, f32, C.c_uint64, vp, vp, vp, vp, vp, vp]),
+    "dvq_attn_full_ok": (i32, [i32, i64, i64, i32]),
     "dvq_attn_full_scratch_bytes": (i64, [i64, i64, i32, i32]),
     "dvq_attn_full_fwd": (i32, [vp, vp, vp, i32, i64, i64, i32, f32, vp, vp, vp, vp]),
     "dvq_attn_full_bwd": (i32, [vp, vp, vp, vp, vp, vp, i32, i64, i64, i32, f32, vp, vp, vp, vp, vp]),
     "dvq_attn_decode_dev": (i32, [vp, vp, vp, vp, vp, i32, i64, i64, i64, vp, i64, f32, vp, vp]),
     "dvq_rows_dev": (i32, [vp, vp, i32, i64, i64, i64, vp, i32, vp]),
     "dvq_decode_stack_scratch_bytes": (sz, [i64, i64, i64]),
+    "dvq_decode_stack_ok": (i32, [i64, i64, i32, i64, i64]),
     "dvq_decode_stack_status": (i32, [vp, i64, i64, i64, i32, vp]),
     "dvq_decode_stack": (i32, [vp, i32, i64, i64, i32, i64, i64, vp, C.c_float, vp, vp, i32, vp, vp]),
     "dvq_dropout": (i32, [vp, i32, i64, f32, C.c_uint64, vp, vp]),

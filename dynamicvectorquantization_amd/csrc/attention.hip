@@ -665,16 +665,27 @@ int launch_bwd(const AttnParams& p, dim3 grid, int64_t rows, hipStream_t stream)
     return launch_bwd_m<HS, false>(p, grid, rows, stream);
 }
 
+// geometry the fused kernels take, stated once: fill_params (every entry point) and the exported predicates dvq_attn_causal_ok /
+// dvq_attn_full_ok ask it.  nullptr = accepted, else the refusal's format (one %s: the entry point).  Full attention (!causal) has no
+// dropout path: attention2.hip launches nothing for it.
+const char* attn_refusal(int dtype, int64_t B, int64_t T, int n_head, int head_dim, float p_drop, int causal) {
+    if (!(dtype == DVQ_BF16 && (causal ? head_dim == 64 || head_dim == 128 : head_dim == 256)))
+        return "%s: bf16 with head size 64 or 128 (causal) / 256 (full attention) only (use the GEMM path otherwise)";
+    if (!(causal || T % 32 == 0)) return "%s: full attention needs T %% 32 == 0";
+    if (!(B > 0 && T > 0 && T % 8 == 0 && n_head > 0 && B * n_head <= 65535 && p_drop >= 0.f && p_drop < 1.f && (causal || p_drop == 0.f)))
+        return "%s: bad geometry (T %% 8 == 0, B * n_head <= 65535)";
+    if (!((double)B * n_head * (double)T * (double)T < 4294967296.0))
+        return "%s: B * n_head * T * T must stay below 2^32 (dropout element index)";
+    return nullptr;
+}
+
 int fill_params(AttnParams& p, const char* who, int dtype, int64_t B, int64_t T, int n_head, int head_dim, float scale, float p_drop,
                 uint64_t seed, int causal = 1) {
-    DVQ_REQUIRE(dtype == DVQ_BF16 && (head_dim == 64 || head_dim == 128 || (head_dim == 256 && !causal)), DVQ_ESHAPE,
-                "%s: bf16 with head size 64 or 128 (causal) / 256 (full attention) only (use the GEMM path otherwise)", who);
-    DVQ_REQUIRE(causal || T % 32 == 0, DVQ_ESHAPE, "%s: full attention needs T %% 32 == 0", who);
+    if (const char* why = attn_refusal(dtype, B, T, n_head, head_dim, p_drop, causal)) {
+        dvq_set_error(why, who);
+        return DVQ_ESHAPE;
+    }
     p.causal = causal;
-    DVQ_REQUIRE(B > 0 && T > 0 && T % 8 == 0 && n_head > 0 && B * n_head <= 65535 && p_drop >= 0.f && p_drop < 1.f, DVQ_ESHAPE,
-                "%s: bad geometry (T %% 8 == 0, B * n_head <= 65535)", who);
-    DVQ_REQUIRE((double)B * n_head * (double)T * (double)T < 4294967296.0, DVQ_ESHAPE,
-                "%s: B * n_head * T * T must stay below 2^32 (dropout element index)", who);
     p.T = (int)T; p.nh = n_head; p.C = n_head * head_dim;
     p.scale = scale;
     p.inv_keep = 1.f / (1.f - p_drop);
@@ -710,6 +721,11 @@ Attn2Args v2_args(const AttnParams& p, int64_t B) {
 }  // namespace
 
 extern "C" {
+
+int dvq_attn_causal_ok(int dtype, int64_t B, int64_t T, int n_head, int head_dim) {
+    return attn_refusal(dtype, B, T, n_head, head_dim, 0.f, 1) == nullptr;
+}
+int dvq_attn_full_ok(int dtype, int64_t B, int64_t T, int C) { return attn_refusal(dtype, B, T, 1, C, 0.f, 0) == nullptr; }
 
 int64_t dvq_attn_causal_scratch_bytes(int64_t B, int64_t T, int n_head, int head_dim, int backward) {
     const int64_t elems = B * T * n_head * head_dim;

@@ -873,6 +873,7 @@ static int halo_try_impl(const void* x, const void* w, const float* bias, const 
     p.mg_gn = magic(p.gn); p.mg_tx = magic(p.tiles_x); p.mg_ty = magic(p.tiles_y);
     // experiment (DVQ_HALO_LDS_PAD=1, probe builds): > 80 KB of LDS = ONE workgroup per CU
     static const int lds_pad = dvq_probe_env("DVQ_HALO_LDS_PAD") != 0 ? 90 * 1024 - LDSB : 0;
+    dvq_note_kernel("conv3x3_halo_kernel");
     auto go = [&](auto kern) {
         dvq_ensure_dynamic_lds((const void*)kern, LDSB + lds_pad);
         kern<<<dim3((unsigned)blocks), dim3(256), LDSB + lds_pad, stream>>>(p);
@@ -1387,6 +1388,7 @@ static int halo_wgrad_impl(const void* x, const void* dy, float* dw, float* db, 
         p.nsplit = 1;
         nblk = (int64_t)p.gi * p.gj;
     }
+    dvq_note_kernel("conv3x3_halo_wgrad_kernel");
     if (thin) {
         dvq_ensure_dynamic_lds((const void*)conv3x3_halo_wgrad_kernel<true>, 2 * WSTAGE);
         conv3x3_halo_wgrad_kernel<true><<<dim3((unsigned)nblk), dim3(512), 2 * WSTAGE, stream>>>(p);
@@ -1519,6 +1521,7 @@ int dvq_conv3x3_thin_k_try(const void* x, const void* w, const float* bias, void
     if (gx > 4096) gx = 4096;
     if (gx < 1) gx = 1;
     const int lds = 4 * 32 * cot * 2;
+    dvq_note_kernel("conv3x3_thin_k_kernel");
     if (cot == 128) conv3x3_thin_k_kernel<4><<<dim3((unsigned)gx, gy), dim3(256), lds, stream>>>(p);
     else if (cot == 64) conv3x3_thin_k_kernel<2><<<dim3((unsigned)gx, gy), dim3(256), lds, stream>>>(p);
     else conv3x3_thin_k_kernel<1><<<dim3((unsigned)gx, gy), dim3(256), lds, stream>>>(p);
@@ -1593,6 +1596,7 @@ int dvq_tconv4x4s2_thin_try(const void* dy, const void* wt, void* dx, int64_t N,
     const int64_t total = N * 4 * OH * OW;
     int64_t blocks = cdiv64(total, 256);
     if (blocks > 8192) blocks = 8192;
+    dvq_note_kernel("tconv4x4s2_thin_kernel");
     dvq_ensure_dynamic_lds((const void*)tconv4x4s2_thin_kernel, lds);
     tconv4x4s2_thin_kernel<<<dim3((unsigned)blocks), dim3(256), lds, stream>>>((const bf16_t*)dy, (const bf16_t*)wt, (bf16_t*)dx, N,
                                                                              (int)OH, (int)OW, (int)Cout, creal);

@@ -597,6 +597,7 @@ int dvq_conv3x3_halo2_try(const void* x, const void* w, const float* bias, const
     // a launch that leaves the persistent workgroups fewer than two tiles each gains nothing from the cross-tile pipeline
     if (blocks < 2 * (int64_t)cus && mode != 2) return 0;
     const unsigned grid = (unsigned)(blocks < cus ? blocks : cus);
+    dvq_note_kernel("conv3x3_halo2_kernel");
     auto go = [&](auto kern) {
         dvq_ensure_dynamic_lds((const void*)kern, LDS2);
         kern<<<dim3(grid), dim3(256), LDS2, stream>>>(p);

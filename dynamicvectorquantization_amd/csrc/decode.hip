@@ -692,11 +692,15 @@ int dvq_decode_stack_status(const void* scratch, int64_t B, int64_t C, int64_t F
     return DVQ_ELAUNCH;
 }
 
+int dvq_decode_stack_ok(int64_t B, int64_t C, int n_head, int64_t F, int64_t Tmax) {
+    return B > 0 && B <= 64 && C > 0 && C % 32 == 0 && C <= 2048 && F > 0 && F % 32 == 0 && n_head > 0 && C % n_head == 0 &&
+           (C / n_head) % 8 == 0 && C / n_head <= 256 && Tmax > 0 && Tmax <= 12000;
+}
+
 int dvq_decode_stack(const void* layers_dev, int n_layers, int64_t B, int64_t C, int n_head, int64_t F, int64_t Tmax, const int64_t* t_dev,
                      float eps, void* x, void* scratch, int n_workgroups, const void* layers_host, dvq_stream_t stream) {
     DVQ_REQUIRE(layers_dev && t_dev && x && scratch && n_layers > 0, DVQ_EINVAL, "dvq_decode_stack: null pointer");
-    DVQ_REQUIRE(B > 0 && B <= 64 && C > 0 && C % 32 == 0 && C <= 2048 && F > 0 && F % 32 == 0 && n_head > 0 && C % n_head == 0 &&
-                    (C / n_head) % 8 == 0 && C / n_head <= 256 && Tmax > 0 && Tmax <= 12000,
+    DVQ_REQUIRE(dvq_decode_stack_ok(B, C, n_head, F, Tmax),
                 DVQ_ESHAPE, "dvq_decode_stack: needs B <= 64, C %% 32 == 0 (<= 2048), F %% 32 == 0, head size %% 8 == 0 (<= 256), Tmax <= 12000");
     int dev = 0, cus = 0;
     DVQ_REQUIRE(hipGetDevice(&dev) == hipSuccess && hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev) == hipSuccess && cus > 0,

@@ -35,6 +35,9 @@ __device__ __forceinline__ void dvq_dma_barrier() {
 // error plumbing (host)
 // ---------------------------------------------------------------------------------------------
 void dvq_set_error(const char* fmt, ...);
+// kernel family of the call in flight (dvq_last_kernel): the `__global__` name of the PRIMARY kernel, set at its dispatch branch
+extern thread_local const char* dvq_kernel_note;
+static inline void dvq_note_kernel(const char* family) { dvq_kernel_note = family; }
 
 #define DVQ_REQUIRE(cond, code, ...)      \
     do {                                  \

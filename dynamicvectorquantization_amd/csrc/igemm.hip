@@ -2780,6 +2780,7 @@ int launch_nt(NtParams p, int64_t batch, int impl, hipStream_t s) {
             if ((impl == 10 || (impl == 0 && p.Ktot >= 4096 && wgm * wgn * batch >= 512)) && pipe_ok) {
                 p.gm = (int)wgm;
                 p.gn = (int)wgn;
+                dvq_note_kernel("gemm_nt_8phase_kernel");
                 dvq_ensure_dynamic_lds((const void*)gemm_nt_8phase_kernel, 8 * 128 * GROW);
                 gemm_nt_8phase_kernel<<<dim3((unsigned)(wgm * wgn), 1, (unsigned)batch), dim3(512), 8 * 128 * GROW, s>>>(p);
                 DVQ_CHECK_LAUNCH("gemm_nt_8phase");
@@ -2788,6 +2789,7 @@ int launch_nt(NtParams p, int64_t batch, int impl, hipStream_t s) {
             if (impl == 7 && pipe_ok) {            // experiment: 4 waves x (4 x 4 tiles), one wave per SIMD
                 p.gm = (int)wgm;
                 p.gn = (int)wgn;
+                dvq_note_kernel("gemm_nt_wide_pipe_kernel");
                 dvq_ensure_dynamic_lds((const void*)gemm_nt_wide_pipe_kernel<2, 2, 4>, 2 * WSTAGEB);
                 gemm_nt_wide_pipe_kernel<2, 2, 4><<<dim3((unsigned)(wgm * wgn), 1, (unsigned)batch), dim3(256), 2 * WSTAGEB, s>>>(p);
                 DVQ_CHECK_LAUNCH("gemm_nt_wide_pipe4");
@@ -2795,6 +2797,7 @@ int launch_nt(NtParams p, int64_t batch, int impl, hipStream_t s) {
             }
             if ((impl == 6 || impl == 8 || (impl == 0 && wgm * wgn * batch >= 128)) && pipe_ok) {
                 // 256- or 192-row tiles: whichever needs less tile-row-time over the 256 CUs (rounds x rows)
+                dvq_note_kernel("gemm_nt_wide_pipe_kernel");
                 const int64_t wgm192 = cdiv64(p.M, 192);
                 const int64_t cost256 = cdiv64(wgm * wgn * batch, 256) * 256, cost192 = cdiv64(wgm192 * wgn * batch, 256) * 192;
                 p.gn = (int)wgn;
@@ -2813,6 +2816,7 @@ int launch_nt(NtParams p, int64_t batch, int impl, hipStream_t s) {
             if (p.mode == MODE_GEMM && p.R == nullptr && (impl == 5 || (p.Ktot >= 8192 && wgm * wgn * batch >= 768))) {
                 p.gm = (int)wgm;
                 p.gn = (int)wgn;
+                dvq_note_kernel("gemm_nt_wide_kernel");
                 dvq_ensure_dynamic_lds((const void*)gemm_nt_wide_kernel, 2 * WSTAGEB);
                 gemm_nt_wide_kernel<<<dim3((unsigned)(wgm * wgn), 1, (unsigned)batch), dim3(512), 2 * WSTAGEB, s>>>(p);
                 DVQ_CHECK_LAUNCH("gemm_nt_wide");
@@ -2857,6 +2861,7 @@ int launch_nt(NtParams p, int64_t batch, int impl, hipStream_t s) {
                 dvq_ensure_dynamic_lds((const void*)kern, lds);
                 kern<<<grid, dim3(cfg == 4 ? 256 : 512), lds, s>>>(p);
             };
+            dvq_note_kernel("conv_nt_pipe_kernel");
             const bool fwd = p.mode == MODE_FWD;
             if (cfg == 4) fwd ? go(conv_nt_pipe_kernel<2, 2, 2, 2, MODE_FWD>) : go(conv_nt_pipe_kernel<2, 2, 2, 2, MODE_TCONV>);
             else if (cfg == 1) fwd ? go(conv_nt_pipe_kernel<4, 2, 2, 4, MODE_FWD>) : go(conv_nt_pipe_kernel<4, 2, 2, 4, MODE_TCONV>);
@@ -2875,6 +2880,7 @@ int launch_nt(NtParams p, int64_t batch, int impl, hipStream_t s) {
             p.gm = 4 * p.par_tiles;
         }
         dim3 grid((unsigned)(p.gm * p.gn), 1, (unsigned)batch);
+        dvq_note_kernel("igemm_nt_glds_kernel");
         auto go = [&](auto kern) {
             dvq_ensure_dynamic_lds((const void*)kern, 2 * GSTAGEB);
             kern<<<grid, dim3(256), 2 * GSTAGEB, s>>>(p);
@@ -2904,12 +2910,14 @@ int launch_nt(NtParams p, int64_t batch, int impl, hipStream_t s) {
         DVQ_CHECK_LAUNCH("igemm_nt_glds");
     } else if (use_mfma) {
         dim3 grid((unsigned)(p.gm * p.gn), 1, (unsigned)batch);
+        dvq_note_kernel("igemm_nt_kernel");
         dvq_ensure_dynamic_lds((const void*)igemm_nt_kernel<T>, 2 * STAGEB);
         igemm_nt_kernel<T><<<grid, dim3(256), 2 * STAGEB, s>>>(p);
         DVQ_CHECK_LAUNCH("igemm_nt");
     } else {
         int64_t total = (int64_t)p.M * p.Ncols;
         unsigned blocks = (unsigned)(cdiv64(total, 256) < 16384 ? cdiv64(total, 256) : 16384);
+        dvq_note_kernel("naive_nt_kernel");
         naive_nt_kernel<T><<<dim3(blocks, 1, (unsigned)batch), dim3(256), 0, s>>>(p);
         DVQ_CHECK_LAUNCH("naive_nt");
     }
@@ -3034,10 +3042,12 @@ int launch_tn(TnParams p, int64_t batch, int impl, hipStream_t s) {
                 return e != nullptr ? atoi(e) : 1;
             }();
             if (tn8_env != 0 && impl == 0 && (p.sA * 2) % 16 == 0 && (p.sB * 2) % 16 == 0) {
+                dvq_note_kernel("gemm_tn_8phase_kernel");
                 dvq_ensure_dynamic_lds((const void*)gemm_tn_8phase_kernel, 8 * 64 * 256);
                 gemm_tn_8phase_kernel<<<dim3((unsigned)(p.itiles * p.jtiles * p.nsplit), 1, (unsigned)batch), dim3(512), 8 * 64 * 256, s>>>(p);
                 DVQ_CHECK_LAUNCH("gemm_tn_8phase");
             } else {
+                dvq_note_kernel("gemm_tn_wide_pipe_kernel");
                 dvq_ensure_dynamic_lds((const void*)gemm_tn_wide_pipe_kernel, 2 * WTSTG);
                 gemm_tn_wide_pipe_kernel<<<dim3((unsigned)(p.itiles * p.jtiles * p.nsplit), 1, (unsigned)batch), dim3(512), 2 * WTSTG, s>>>(p);
                 DVQ_CHECK_LAUNCH("gemm_tn_wide_pipe");
@@ -3071,6 +3081,7 @@ int launch_tn(TnParams p, int64_t batch, int impl, hipStream_t s) {
                 p.m_per_split = (int)npatch;
                 p.nsplit = 1;
             }
+            dvq_note_kernel("conv_tn_patch_kernel");
             dvq_ensure_dynamic_lds((const void*)conv_tn_patch_kernel, 2 * TSTAGEB);
             conv_tn_patch_kernel<<<dim3((unsigned)(ptiles * p.nsplit)), dim3(256), 2 * TSTAGEB, s>>>(p);
             DVQ_CHECK_LAUNCH("conv_tn_patch");
@@ -3090,6 +3101,7 @@ int launch_tn(TnParams p, int64_t batch, int impl, hipStream_t s) {
                 grid = dim3((unsigned)(p.itiles * p.jtiles * tapblk), 1, (unsigned)batch);
             }
         }
+        dvq_note_kernel(sizeof(T) == 2 && impl != 3 ? "igemm_tn_tr_kernel" : "igemm_tn_kernel");
         if (sizeof(T) == 2 && impl != 3) {      // LDS-DMA + transpose-read kernel
             if (p.conv) {
                 dvq_ensure_dynamic_lds((const void*)igemm_tn_tr_kernel<true>, 2 * TSTAGEB);
@@ -3122,6 +3134,7 @@ int launch_tn(TnParams p, int64_t batch, int impl, hipStream_t s) {
     } else {
         int64_t nout = (int64_t)p.I * p.taps * p.J + (p.colsumA ? p.I : 0);
         unsigned blocks = (unsigned)(cdiv64(nout, 4) < 8192 ? cdiv64(nout, 4) : 8192);
+        dvq_note_kernel("naive_tn_kernel");
         naive_tn_kernel<T><<<dim3(blocks, 1, (unsigned)batch), dim3(256), 0, s>>>(p);
         DVQ_CHECK_LAUNCH("naive_tn");
     }
@@ -3129,6 +3142,7 @@ int launch_tn(TnParams p, int64_t batch, int impl, hipStream_t s) {
 }
 
 int conv_check(const dvq_conv_desc* d, const char* who) {
+    dvq_note_kernel("");          // first statement of every conv entry point: no stale family from an earlier call
     DVQ_REQUIRE(d != nullptr, DVQ_EINVAL, "%s: null descriptor", who);
     DVQ_REQUIRE(d->N > 0 && d->H > 0 && d->W > 0 && d->Cin > 0 && d->OH > 0 && d->OW > 0 && d->Cout > 0 && d->KH > 0 &&
                     d->KW > 0 && d->stride > 0 && d->pad_t >= 0 && d->pad_l >= 0,
@@ -3564,6 +3578,7 @@ int dvq_conv2d_dgrad_x3(const dvq_conv_desc* d, const void* dy, const void* wt, 
 int dvq_gemm_nt(const void* A, const void* B, void* C, int dtype, int64_t M, int64_t N, int64_t K, int64_t lda,
                 int64_t ldb, int64_t ldc, int64_t batch, int64_t sA, int64_t sB, int64_t sC, float alpha,
                 const float* bias, int bias_mode, int impl, dvq_stream_t stream) {
+    dvq_note_kernel("");
     DVQ_REQUIRE(A && B && C, DVQ_EINVAL, "dvq_gemm_nt: null pointer");
     DVQ_REQUIRE(M > 0 && N > 0 && K > 0 && batch > 0 && batch <= 65535 && M < (1ll << 31) && N < (1ll << 31), DVQ_ESHAPE,
                 "dvq_gemm_nt: bad shape");
@@ -3600,6 +3615,7 @@ int dvq_gemm_nt(const void* A, const void* B, void* C, int dtype, int64_t M, int
 int dvq_gemm_nt_res(const void* A, const void* B, void* C, const void* R, int dtype, int64_t M, int64_t N, int64_t K, int64_t lda,
                     int64_t ldb, int64_t ldc, int64_t batch, int64_t sA, int64_t sB, int64_t sC, float alpha, const float* bias,
                     int bias_mode, dvq_stream_t stream) {
+    dvq_note_kernel("");
     DVQ_REQUIRE(A && B && C && R, DVQ_EINVAL, "dvq_gemm_nt_res: null pointer");
     DVQ_REQUIRE(M > 0 && N > 0 && K > 0 && batch > 0 && batch <= 65535 && M < (1ll << 31) && N < (1ll << 31), DVQ_ESHAPE,
                 "dvq_gemm_nt_res: bad shape");
@@ -3621,6 +3637,7 @@ int dvq_gemm_nt_res(const void* A, const void* B, void* C, const void* R, int dt
 
 static int gemm_tn_impl(const void* A, const void* B, float* C, float* colsum, int dtype, int64_t Mred, int64_t I, int64_t J, int64_t lda,
                         int64_t ldb, int64_t ldc, int64_t batch, int64_t sA, int64_t sB, int64_t sC, int impl, dvq_stream_t stream) {
+    dvq_note_kernel("");
     DVQ_REQUIRE(A && B && C, DVQ_EINVAL, "dvq_gemm_tn: null pointer");
     DVQ_REQUIRE(Mred > 0 && I > 0 && J > 0 && batch > 0 && batch <= 65535 && Mred < (1ll << 31), DVQ_ESHAPE,
                 "dvq_gemm_tn: bad shape");

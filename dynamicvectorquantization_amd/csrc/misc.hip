@@ -10,6 +10,7 @@
 // error plumbing
 // ---------------------------------------------------------------------------------------------
 static thread_local char g_err[512] = "";
+thread_local const char* dvq_kernel_note = "";
 void dvq_set_error(const char* fmt, ...) {
     va_list ap;
     va_start(ap, fmt);
@@ -751,7 +752,8 @@ int dvq_set_fp32_split(int on) {
 }
 
 const char* dvq_last_error(void) { return g_err; }
-int dvq_version(void) { return 112; }
+const char* dvq_last_kernel(void) { return dvq_kernel_note; }
+int dvq_version(void) { return 113; }
 
 int dvq_set_workspace(void* ptr, int64_t bytes) {
     DVQ_REQUIRE((ptr == nullptr) == (bytes == 0) && bytes >= 0, DVQ_EINVAL, "dvq_set_workspace: bad arguments");

@@ -133,10 +133,13 @@ def _tag(d, mode):
         _cur_tag[0] = f"{mode} N{d.N} {d.H}x{d.W} {d.Cin}->{d.Cout} k{d.KH}s{d.stride}{'u' if d.upsample else ''}"
 
 
-def _timed(name, flops, nbytes, fn):
+def _timed(name, flops, nbytes, fn, entry=None):
+    """name=None (_timed_conv): the record is keyed by the kernel family the library noted at the dispatch branch the call took
+    (dvq_last_kernel), or by `entry`, the entry point's name, when it noted none -- a branch without a note shows up in the table"""
     global _count
+    tag = None
     if _shape_tags and _cur_tag[0] is not None:
-        name, _cur_tag[0] = f"{name} | {_cur_tag[0]}", None
+        tag, _cur_tag[0] = _cur_tag[0], None
     if _count is not None:
         _count += 1
     if _prof is None or len(_pool) < 2:
@@ -145,42 +148,17 @@ def _timed(name, flops, nbytes, fn):
     s.record()
     r = fn()
     e.record()
+    if name is None:
+        name = lib().dvq_last_kernel().decode() or entry
+    if tag is not None:
+        name = f"{name} | {tag}"
     _prof.setdefault(name, []).append((s, e, flops, nbytes))
     return r
 
 
-def _halo_eligible(d: ConvDesc) -> bool:
-    """mirrors halo_eligible()/dvq_conv3x3_halo_try in csrc: which kernel a conv call lands on (for timing labels)"""
-    return (d.dtype == _lib.BF16 and d.KH == 3 and d.KW == 3 and d.stride == 1 and d.pad_t == 1 and d.pad_l == 1 and
-            d.OH == d.H and d.OW == d.W and d.impl in (0, 4) and d.W % 32 == 0 and d.Cin % 64 == 0 and d.Cout % 8 == 0)
-
-
-def _tn_family(d: ConvDesc, cin_real: int) -> str:
-    """mirrors launch_tn() in csrc/igemm.hip: the kernel family a non-halo weight-gradient call lands on (timing labels)"""
-    if d.dtype != _lib.BF16:
-        return "igemm_tn_kernel"
-    if (d.KH == 1 and d.KW == 1 and d.stride == 1 and d.pad_t == 0 and d.pad_l == 0 and not d.upsample and d.Cin >= 256 and d.Cout >= 256 and
-            (d.impl != 0 or os.environ.get("DVQ_TN_1X1_PATCH", "1") == "0")):
-        return "gemm_tn_wide_pipe_kernel"
-    if d.Cin == 8 and 1 < d.KH * d.KW <= 16:
-        return "igemm_tn_tr_kernel"          # thin: taps folded into the column tile
-    if d.impl == 0 and os.environ.get("DVQ_CONV_TN_PATCH", "1") != "0":
-        return "conv_tn_patch_kernel"
-    return "igemm_tn_tr_kernel"
-
-
-def _nt_family(d: ConvDesc, dgrad: bool) -> str:
-    """mirrors launch_nt() in csrc/igemm.hip: the kernel family a non-halo forward / input-gradient call lands on (timing labels)"""
-    cs, ncols = (d.Cout, d.Cin) if dgrad else (d.Cin, d.Cout)
-    if d.dtype != _lib.BF16 or d.impl not in (0, 9):
-        return "igemm_nt_glds_kernel"
-    if (d.KH == 1 and d.KW == 1 and d.stride == 1 and d.pad_t == 0 and d.pad_l == 0 and not d.upsample and ncols >= 256 and cs % 64 == 0
-            and d.impl == 0):
-        return "gemm_nt_wide_pipe_kernel"
-    if (cs % 64 == 0 and ncols % 8 == 0 and not d.upsample and d.KH * d.KW <= 16 and
-            (not dgrad or d.stride == 1 or (d.H % 2 == 0 and d.W % 2 == 0))):
-        return "conv_nt_pipe_kernel"
-    return "igemm_nt_glds_kernel"
+def _timed_conv(flops, nbytes, entry, call):
+    """a conv entry point under _timed: which kernel it lands on is decided -- and reported -- by the library"""
+    return _timed(None, flops, nbytes, lambda: check(call(), entry), entry)
 
 
 def _conv_cost(d: ConvDesc, esize: int):
@@ -440,16 +418,16 @@ def conv2d_fwd(d: ConvDesc, x, w, bias, residual=None, gn_ss=None, out_stats=Non
         ensure_workspace(x.device)        # per-tile statistics partials of the halo kernel
     if act != ACT_NONE:
         assert residual is None and gn_ss is None and out_stats is None
-        _timed("conv3x3_halo_kernel" if _halo_eligible(d) and d.H % 8 == 0 else _nt_family(d, False), fl, nb, lambda: check(
-            lib().dvq_conv2d_fwd_act(C.byref(d), _p(x), _p(w), _p(bias), _p(y), act, _s()), "dvq_conv2d_fwd_act"))
+        _timed_conv(fl, nb, "dvq_conv2d_fwd_act", lambda:
+            lib().dvq_conv2d_fwd_act(C.byref(d), _p(x), _p(w), _p(bias), _p(y), act, _s()))
         return y
     if gn_ss is not None or out_stats is not None:
-        _timed("conv3x3_halo_kernel", fl, nb, lambda: check(
+        _timed_conv(fl, nb, "dvq_conv2d_fwd_ex", lambda:
             lib().dvq_conv2d_fwd_ex(C.byref(d), _p(x), _p(w), _p(bias), _p(residual), _p(y), _p(gn_ss), _p(out_stats),
-                                    out_groups, _s()), "dvq_conv2d_fwd_ex"))
+                                    out_groups, _s()))
         return y
-    _timed("conv3x3_halo_kernel" if _halo_eligible(d) and d.H % 8 == 0 else _nt_family(d, False), fl, nb, lambda: check(
-        lib().dvq_conv2d_fwd(C.byref(d), _p(x), _p(w), _p(bias), _p(residual), _p(y), _s()), "dvq_conv2d_fwd"))
+    _timed_conv(fl, nb, "dvq_conv2d_fwd", lambda:
+        lib().dvq_conv2d_fwd(C.byref(d), _p(x), _p(w), _p(bias), _p(residual), _p(y), _s()))
     return y
 
 
@@ -468,10 +446,8 @@ def conv2d_dgrad(d: ConvDesc, dy, wt, mask=None, mask_act=ACT_NONE):
             "dvq_conv2d_dgrad_x3"))
         return dx
     _tag(d, "dgrad")
-    _timed("conv3x3_halo_kernel" if _halo_eligible(d) and d.H % 8 == 0 and d.Cout % 64 == 0 else _nt_family(d, True), fl, nb,
-           lambda: check(
-        lib().dvq_conv2d_dgrad_mask(C.byref(d), _p(dy), _p(wt), _p(dx), _p(ws), _p(mask), mask_act, _s()),
-        "dvq_conv2d_dgrad_mask"))
+    _timed_conv(fl, nb, "dvq_conv2d_dgrad_mask", lambda:
+        lib().dvq_conv2d_dgrad_mask(C.byref(d), _p(dy), _p(wt), _p(dx), _p(ws), _p(mask), mask_act, _s()))
     return dx
 
 
@@ -570,13 +546,13 @@ def conv2d_wgrad_oihw(d: ConvDesc, x, dy, cin_real, cout_real, grad_oihw, db=Non
         return
     _tag(d, "wgrad")
     if gn_ss is not None:
-        _timed("conv3x3_halo_wgrad_kernel", fl, nb, lambda: check(
+        _timed_conv(fl, nb, "dvq_conv2d_wgrad_oihw_ex", lambda:
             lib().dvq_conv2d_wgrad_oihw_ex(C.byref(d), _p(x), _p(dy), cin_real, cout_real, _praw(grad_oihw), _p(db),
-                                           int(is_ohwi(grad_oihw)), _p(gn_ss), _s()), "dvq_conv2d_wgrad_oihw_ex"))
+                                           int(is_ohwi(grad_oihw)), _p(gn_ss), _s()))
         return
-    _timed("conv3x3_halo_wgrad_kernel" if _halo_eligible(d) and d.H % 4 == 0 else _tn_family(d, cin_real), fl, nb, lambda: check(
+    _timed_conv(fl, nb, "dvq_conv2d_wgrad_oihw", lambda:
         lib().dvq_conv2d_wgrad_oihw(C.byref(d), _p(x), _p(dy), cin_real, cout_real, _praw(grad_oihw), _p(db),
-                                    int(is_ohwi(grad_oihw)), _s()), "dvq_conv2d_wgrad_oihw"))
+                                    int(is_ohwi(grad_oihw)), _s()))
 
 
 def set_deterministic(on: bool):
@@ -1005,10 +981,10 @@ def dropout(x, p, seed):
 
 
 def attn_causal_ok(x, n_head, b, t):
-    """eligibility of the fused attention kernels (include/dvq_hip.h: bf16, head size 64 / 128, T % 8 == 0, index range)"""
+    """do the fused attention kernels take this call (dvq_attn_causal_ok: the check the entry points make themselves)?"""
     c = x.shape[-1]
-    return (x.dtype == torch.bfloat16 and c in (n_head * 64, n_head * 128) and t % 8 == 0 and b * n_head <= 65535 and b * n_head * t * t < (1 << 32)
-            and os.environ.get("DVQ_NO_FUSED_ATTN", "0") != "1")
+    return (x.dtype in _DT and c % n_head == 0 and os.environ.get("DVQ_NO_FUSED_ATTN", "0") != "1" and
+            bool(lib().dvq_attn_causal_ok(dt(x), b, t, n_head, c // n_head)))
 
 
 def _attn_scratch(q, b, t, n_head, backward):
@@ -1082,9 +1058,9 @@ def attn_causal_bwd_fused(qkv, cols, out, dout, lse, b, t, n_head, scale, p_drop
 
 
 def attn_full_ok(q, t):
-    """eligibility of the fused single-head full attention (AttnBlock): bf16, C = 256, T % 32 == 0"""
-    return (q.dtype == torch.bfloat16 and q.shape[-1] == 256 and t % 32 == 0 and q.shape[0] // max(1, t) <= 65535
-            and os.environ.get("DVQ_NO_FUSED_ATTNBLOCK", "0") != "1")
+    """does the fused single-head full attention (AttnBlock) take this call (dvq_attn_full_ok)?"""
+    return (q.dtype in _DT and os.environ.get("DVQ_NO_FUSED_ATTNBLOCK", "0") != "1" and
+            bool(lib().dvq_attn_full_ok(dt(q), q.shape[0] // max(1, t), t, q.shape[-1])))
 
 
 def attn_full_fwd(q, k, v, b, t, scale):
@@ -1112,6 +1088,11 @@ def attn_full_bwd(q, k, v, out, dout, lse, b, t, scale):
 def decode_stack_scratch(b, c, f, device):
     """zeroed scratch of dvq_decode_stack (activations between its phases + the barrier counters it re-arms itself)"""
     return torch.zeros(lib().dvq_decode_stack_scratch_bytes(b, c, f), dtype=torch.uint8, device=device)
+
+
+def decode_stack_ok(b, c, n_head, f, tmax) -> bool:
+    """does dvq_decode_stack take this geometry (its own shape check)?"""
+    return bool(lib().dvq_decode_stack_ok(b, c, n_head, f, tmax))
 
 
 def decode_stack_status(scratch, b, c, f, reset=True):

@@ -438,8 +438,8 @@ class DecodeState:
         blocks, caches = (g.position_transformer, self.pos_cache) if which == "pos" else (g.content_transformer, self.con_cache)
         c, cd = g.config.n_embd, rt.compute_dtype()
         nh = blocks[0].attn.n_head
-        if (getattr(self, "_no_stack", False) or os.environ.get("DVQ_DECODE_STACK", "1") == "0" or cd != torch.bfloat16 or self.b > 64 or c % 32 or c > 2048 or (c // nh) % 8 or
-                c // nh > 256 or self.max_rows > 12000):
+        if (getattr(self, "_no_stack", False) or os.environ.get("DVQ_DECODE_STACK", "1") == "0" or cd != torch.bfloat16 or
+                not K.decode_stack_ok(self.b, c, nh, blocks[0].mlp[0].out_features, self.max_rows)):
             return None
         ent = self._stacks.get(which)
         if ent is not None and ent["sig"] == self._sig:

@@ -42,7 +42,12 @@ enum { DVQ_F32 = 0, DVQ_BF16 = 1 };
 enum { DVQ_OK = 0, DVQ_EINVAL = -1, DVQ_ESHAPE = -2, DVQ_EARCH = -3, DVQ_ELAUNCH = -4, DVQ_EWORKSPACE = -5 };
 
 const char* dvq_last_error(void);
-int dvq_version(void);     /* 112: dvq_token_nll, dvq_nll_segment_sums (teacher-forced likelihood scoring);
+/* Kernel family the calling thread's last dvq_conv2d_* / dvq_gemm_* call landed on: the `__global__` name of its primary kernel as
+ * written in csrc ("conv3x3_halo_kernel", "conv_nt_pipe_kernel", ...; no template arguments, no fold / reduce / transpose helpers), noted
+ * at the dispatch branch that launches it.  "" when nothing was noted (those entry points clear it first).  For timing labels. */
+const char* dvq_last_kernel(void);
+int dvq_version(void);     /* 113: dvq_last_kernel (kernel family of a conv call), dvq_attn_causal_ok / dvq_attn_full_ok / dvq_decode_stack_ok;
+                            * 112: dvq_token_nll, dvq_nll_segment_sums (teacher-forced likelihood scoring);
                             * 111: dvq_sample_guided (classifier-free-guided constrained draw), dvq_label_dropout (null-label dropout);
                             * 110: dvq_recon_metrics (+ _workspace_bytes), dvq_code_histogram (reconstruction evaluation);
                             * 109: round 5 (dvq_conv2d_fwd_x3 / dvq_conv2d_dgrad_x3: fp32x3 3 x 3 convolutions on the halo kernel, fp32 output);
@@ -508,7 +513,9 @@ int dvq_sample_guided(const void* logits, int dtype, int64_t B, int64_t V, int64
  * drop_mask (may be NULL): dvq_attn_causal_mask_bytes(B, T, n_head) bytes; the forward stores its keep decisions there, one bit per
  * (query, key) of every causal 32 x 32 tile, and a backward given the same buffer reads them instead of hashing every element again
  * in each of its three kernels (identical results: test_fused_attention_drop_mask_equals_rehash).  NULL: decisions recomputed.
- * DVQ_ESHAPE when dtype / head_dim are not bf16 / 64 or 128: callers use the per-head GEMM path then. */
+ * DVQ_ESHAPE when dtype / head_dim are not bf16 / 64 or 128: callers use the per-head GEMM path then.
+ * dvq_attn_causal_ok: 1 when the entry points below take this geometry (the check they make themselves), else 0. */
+int dvq_attn_causal_ok(int dtype, int64_t B, int64_t T, int n_head, int head_dim);
 int64_t dvq_attn_causal_scratch_bytes(int64_t B, int64_t T, int n_head, int head_dim, int backward);
 int64_t dvq_attn_causal_mask_bytes(int64_t B, int64_t T, int n_head);
 int dvq_attn_causal_fwd(const void* q, const void* k, const void* v, int dtype, int64_t B, int64_t T, int n_head, int head_dim,
@@ -531,7 +538,8 @@ int dvq_attn_causal_bwd_ld(const void* q, const void* k, const void* v, int64_t 
 /* Single-head FULL (non-causal) self-attention of the DQ-VAE's AttnBlock (modules/diffusionmodules/model.py:168-192:
  * w = softmax_j(q^T k * C^-1/2), h = v w^T) for C = 256 (bf16, T %% 32 == 0): the same flash kernels as above with one head of
  * size C, no mask, no dropout; q, k, v, out [B*T][C]; lse fp32 [B][T].  The [B,T,T] score tensor never reaches HBM.  Other
- * shapes (C = 512) return DVQ_ESHAPE: the caller keeps the GEMM + softmax path for them. */
+ * shapes (C = 512) return DVQ_ESHAPE: the caller keeps the GEMM + softmax path for them -- dvq_attn_full_ok tells (1 / 0). */
+int dvq_attn_full_ok(int dtype, int64_t B, int64_t T, int C);
 int64_t dvq_attn_full_scratch_bytes(int64_t B, int64_t T, int C, int backward);
 int dvq_attn_full_fwd(const void* q, const void* k, const void* v, int dtype, int64_t B, int64_t T, int C, float scale, void* out,
                       float* lse, void* scratch, dvq_stream_t stream);
@@ -574,6 +582,8 @@ typedef struct dvq_decode_layer {
     void *kcache, *vcache;                            /* bf16 [B][Tmax][C] */
 } dvq_decode_layer;
 size_t dvq_decode_stack_scratch_bytes(int64_t B, int64_t C, int64_t F);
+/* 1 when dvq_decode_stack takes this geometry (its own shape check), else 0: the caller keeps the per-kernel token steps */
+int dvq_decode_stack_ok(int64_t B, int64_t C, int n_head, int64_t F, int64_t Tmax);
 /* Synchronising read-back of the error word of dvq_decode_stack (call once per sampling run, not per token): DVQ_OK, or
  * DVQ_ELAUNCH when a device-wide barrier timed out since the scratch was last zeroed -- every workgroup left the kernel at that
  * barrier, so the rows produced since are invalid; reset != 0 re-arms the counters (on `stream`) so that later launches run. */

@@ -1,0 +1,128 @@
+"""What the library says about its own dispatch: the kernel family a conv call landed on (dvq_last_kernel, read by kernels._timed while
+profiling) and the eligibility predicates against the entry points they speak for.  `pytest -m gpu`.
+
+One bf16, impl 0 case per branch of the conv entry points that notes a family and is reachable with the default environment, each at
+the smallest shape that meets the branch's conditions in csrc/igemm.hip / csrc/conv_halo.hip.  Noted branches WITHOUT a case here:
+  * conv3x3_halo2_kernel: exists in the probes build only (-DDVQ_PROBES, DVQ_HALO2=1);
+  * gemm_nt_wide_kernel, igemm_nt_kernel: plain GEMMs at K >= 8192 / impl 3 only -- no conv call reaches them with impl 0;
+  * gemm_tn_8phase_kernel, gemm_tn_wide_pipe_kernel: a conv reaches them only with DVQ_TN_1X1_PATCH=0 (gemm_tn calls do by default, under
+    the fixed label "gemm_tn");
+  * igemm_tn_kernel: fp32 operands only, and fp32 weight gradients go to the bf16 planes ("conv_wgrad_x3_planes") or need impl 3;
+  * the fp32x3 forms of the halo kernels (dvq_conv2d_fwd_x3 / _dgrad_x3 / _wgrad_oihw_x3) keep their fixed labels."""
+import pytest
+import torch
+
+pytestmark = pytest.mark.gpu
+
+BF16, F32 = torch.bfloat16, torch.float32
+
+
+def _desc(K, n, h, w, cin, cout, k, stride=1, pad=None, oh=None, ow=None, dtype=BF16):
+    pad = (k - 1) // 2 if pad is None else pad
+    oh = (h + 2 * pad - k) // stride + 1 if oh is None else oh
+    ow = (w + 2 * pad - k) // stride + 1 if ow is None else ow
+    return K.conv_desc(n, h, w, cin, cout, k, k, stride, pad, pad, oh, ow, False, dtype, 0)
+
+
+def _rand(dev, dtype, *shape):
+    return (torch.rand(*shape, device=dev) - 0.5).to(dtype)
+
+
+def _fwd(K, dev, d, dtype=BF16):
+    x, w = _rand(dev, dtype, d.N, d.H, d.W, d.Cin), _rand(dev, dtype, d.Cout, d.KH, d.KW, d.Cin)
+    return K.conv2d_fwd(d, x, w, torch.zeros(d.Cout, device=dev))
+
+
+def _dgrad(K, dev, d, dtype=BF16):
+    dy, wt = _rand(dev, dtype, d.N, d.OH, d.OW, d.Cout), _rand(dev, dtype, d.Cin, d.KH, d.KW, d.Cout)
+    return K.conv2d_dgrad(d, dy, wt)
+
+
+def _wgrad(K, dev, d, dtype=BF16):
+    x, dy = _rand(dev, dtype, d.N, d.H, d.W, d.Cin), _rand(dev, dtype, d.N, d.OH, d.OW, d.Cout)
+    dw = torch.zeros(d.Cout, d.Cin, d.KH, d.KW, device=dev)
+    K.conv2d_wgrad_oihw(d, x, dy, d.Cin, d.Cout, dw, torch.zeros(d.Cout, device=dev))
+    return dw
+
+
+# (id, pass, family, descriptor arguments of _desc, dtype)
+DISPATCH_CASES = [
+    # halo_try_impl: H % 8, W % 32, Cin % 64, Cout % 8
+    ("halo-fwd", _fwd, "conv3x3_halo_kernel", dict(n=1, h=8, w=32, cin=64, cout=64, k=3), BF16),
+    # conv2d_fwd_impl: Cin == 8 (image heads) -> dvq_conv3x3_thin_k_try: W % 32, Cout % 8
+    ("thin-k-fwd", _fwd, "conv3x3_thin_k_kernel", dict(n=1, h=8, w=32, cin=8, cout=64, k=3), BF16),
+    # dvq_conv2d_dgrad_mask: Cout == 8 (gradient of the 3-channel output conv), the same kernel with the taps reversed
+    ("thin-k-dgrad", _dgrad, "conv3x3_thin_k_kernel", dict(n=1, h=8, w=32, cin=64, cout=8, k=3), BF16),
+    # dvq_conv2d_dgrad_mask: 4 x 4 / stride 2 / pad 1, Cin == 8, H == 2 OH (input gradient of the PatchGAN's first conv)
+    ("tconv4x4s2-thin", _dgrad, "tconv4x4s2_thin_kernel", dict(n=1, h=16, w=16, cin=8, cout=64, k=4, stride=2, pad=1), BF16),
+    # launch_nt pipe_ok: 64-channel K slabs, stride 1 / 2; the encoder's downsampling conv (3 x 3 / stride 2, pad bottom / right only)
+    ("nt-pipe-down", _fwd, "conv_nt_pipe_kernel", dict(n=1, h=16, w=16, cin=64, cout=64, k=3, stride=2, pad=0, oh=8, ow=8), BF16),
+    # Cin % 64 != 0: neither the halo nor the pipelined kernel; M * Ncols >= 1024 -> the 128 x 128 LDS-DMA kernel
+    ("nt-glds", _fwd, "igemm_nt_glds_kernel", dict(n=1, h=8, w=32, cin=32, cout=32, k=3), BF16),
+    # 1 x 1 as a plain GEMM on 256 x 256 tiles from 128 workgroups on: ceil(M / 256) * ceil(256 / 256) >= 128 <=> M >= 32513 = 533 x 61
+    ("nt-wide-pipe", _fwd, "gemm_nt_wide_pipe_kernel", dict(n=1, h=533, w=61, cin=64, cout=256, k=1), BF16),
+    # ... and on the 8-phase kernel from K >= 4096 over >= 512 tiles on: 8192 x 4096 x 4096
+    ("nt-8phase", _fwd, "gemm_nt_8phase_kernel", dict(n=1, h=64, w=128, cin=4096, cout=4096, k=1), BF16),
+    # M * Ncols < 1024: no MFMA tile
+    ("nt-naive", _fwd, "naive_nt_kernel", dict(n=1, h=4, w=4, cin=8, cout=8, k=1), BF16),
+    # halo_wgrad_impl: H % 4, W % 32, Cin % 64, Cout % 8
+    ("halo-wgrad", _wgrad, "conv3x3_halo_wgrad_kernel", dict(n=1, h=8, w=32, cin=64, cout=64, k=3), BF16),
+    # launch_tn: a conv off the halo shapes, I % 8 == 0 and J % 8 == 0 -> 8 x 8 pixel patches (1 x 1 convs included)
+    ("tn-patch", _wgrad, "conv_tn_patch_kernel", dict(n=2, h=20, w=24, cin=128, cout=64, k=1), BF16),
+    # launch_tn thin: J == 8 with 1 < taps <= 16 (taps folded into the column tile); Mred >= 256 for the MFMA path
+    ("tn-tr-thin", _wgrad, "igemm_tn_tr_kernel", dict(n=1, h=8, w=32, cin=8, cout=64, k=3), BF16),
+    # Mred < 256: no MFMA tile
+    ("tn-naive", _wgrad, "naive_tn_kernel", dict(n=1, h=4, w=4, cin=8, cout=8, k=1), BF16),
+    # fp32 operands: every forward off the fp32x3 halo shapes is igemm_nt_glds_kernel<float>
+    ("fp32-fwd", _fwd, "igemm_nt_glds_kernel", dict(n=1, h=8, w=32, cin=32, cout=32, k=3), F32),
+]
+
+
+@pytest.mark.parametrize("case", DISPATCH_CASES, ids=lambda c: c[0])
+def test_dispatch_label(dev, case):
+    from dynamicvectorquantization_amd import kernels as K
+    _, run, family, geo, dtype = case
+    d = _desc(K, dtype=dtype, **geo)
+    torch.manual_seed(0)
+    K.profile_start(8)
+    try:
+        out = run(K, dev, d, dtype)
+    finally:
+        fams = K.profile_stop()
+    assert list(fams) == [family] and fams[family]["launches"] == 1, fams
+    assert bool(torch.isfinite(out.float()).all())
+
+
+@pytest.mark.parametrize("dtype", [BF16, F32], ids=["bf16", "fp32"])
+@pytest.mark.parametrize("hs", [32, 64])
+@pytest.mark.parametrize("t", [8, 12])
+def test_attn_causal_ok_is_what_the_entry_point_accepts(dev, t, hs, dtype):
+    from dynamicvectorquantization_amd import _lib
+    from dynamicvectorquantization_amd import kernels as K
+    q, k, v = (_rand(dev, dtype, t, hs) for _ in range(3))
+    try:
+        out, _ = K.attn_causal_fwd(q, k, v, 1, t, 1, hs ** -0.5)
+        accepted = True
+    except _lib.DvqError:
+        accepted = False
+    assert K.attn_causal_ok(q, 1, 1, t) == accepted
+    assert accepted == (t == 8 and hs == 64 and dtype == BF16)
+    if accepted:
+        assert bool(torch.isfinite(out.float()).all())
+
+
+@pytest.mark.parametrize("c", [128, 256])
+@pytest.mark.parametrize("t", [32, 40])
+def test_attn_full_ok_is_what_the_entry_point_accepts(dev, t, c):
+    from dynamicvectorquantization_amd import _lib
+    from dynamicvectorquantization_amd import kernels as K
+    q, k, v = (_rand(dev, BF16, t, c) for _ in range(3))
+    try:
+        out, _ = K.attn_full_fwd(q, k, v, 1, t, c ** -0.5)
+        accepted = True
+    except _lib.DvqError:
+        accepted = False
+    assert K.attn_full_ok(q, t) == accepted
+    assert accepted == (t == 32 and c == 256)
+    if accepted:
+        assert bool(torch.isfinite(out.float()).all())

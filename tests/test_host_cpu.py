@@ -334,3 +334,93 @@ def test_train_py_gpu_id_mapping():
     import train
     assert train._gpu_ids("-1", 8) == list(range(8)) and train._gpu_ids("3", 8) == [0, 1, 2]
     assert train._gpu_ids("2,3", 8) == [2, 3] and train._gpu_ids("5,", 8) == [5]
+
+
+# ---- eligibility predicates and the kernel-family note of libdvq_hip (host code: no GPU needed) -----------------------------------
+F32_, BF16_ = 0, 1          # DVQ_F32 / DVQ_BF16
+
+
+def _table(fn, cases):
+    lib_fn = getattr(__import__("dynamicvectorquantization_amd._lib", fromlist=["load"]).load(), fn)
+    bad = [(args, want, lib_fn(*args)) for args, want in cases if bool(lib_fn(*args)) != want]
+    assert not bad, f"{fn}: (args, expected, got) = {bad}"
+
+
+def test_attn_causal_ok_table():
+    """dvq_attn_causal_ok(dtype, B, T, n_head, head_dim): both sides of every bound of the geometry check in csrc/attention.hip"""
+    _table("dvq_attn_causal_ok", [
+        ((BF16_, 2, 64, 4, 64), True), ((BF16_, 2, 64, 4, 128), True),
+        ((BF16_, 2, 8, 1, 64), True), ((BF16_, 2, 12, 1, 64), False), ((BF16_, 2, 60, 4, 64), False),      # T % 8
+        ((BF16_, 2, 64, 4, 32), False), ((BF16_, 2, 64, 4, 256), False),                                    # head size 64 / 128 only
+        ((BF16_, 65535, 8, 1, 64), True), ((BF16_, 65536, 8, 1, 64), False),                                # B * n_head <= 65535
+        ((BF16_, 13107, 8, 5, 64), True), ((BF16_, 8192, 8, 8, 64), False),
+        ((BF16_, 1, 65528, 1, 128), True), ((BF16_, 1, 65536, 1, 128), False),                              # B * n_head * T * T < 2^32
+        ((BF16_, 4, 32760, 1, 64), True), ((BF16_, 2, 32768, 2, 64), False), ((BF16_, 65535, 256, 1, 64), True), ((BF16_, 16384, 512, 1, 64), False),
+        ((F32_, 2, 64, 4, 64), False), ((F32_, 2, 64, 4, 128), False),                                      # bf16 only
+        ((BF16_, 0, 64, 4, 64), False), ((BF16_, 2, 0, 4, 64), False), ((BF16_, 2, 64, 0, 64), False),
+    ])
+
+
+def test_attn_full_ok_table():
+    """dvq_attn_full_ok(dtype, B, T, C): one head of 256 channels, T % 32 == 0, B * T * T < 2^32"""
+    _table("dvq_attn_full_ok", [
+        ((BF16_, 2, 1024, 256), True), ((BF16_, 2, 32, 256), True),
+        ((BF16_, 2, 40, 256), False), ((BF16_, 2, 1016, 256), False), ((BF16_, 2, 16, 256), False),         # T % 32
+        ((BF16_, 2, 1024, 128), False), ((BF16_, 2, 1024, 64), False), ((BF16_, 2, 256, 512), False),       # C == 256 only
+        ((BF16_, 65535, 32, 256), True), ((BF16_, 65536, 32, 256), False),                                  # B <= 65535
+        ((BF16_, 4095, 1024, 256), True), ((BF16_, 4096, 1024, 256), False),                                # B * T * T < 2^32
+        ((BF16_, 1, 65504, 256), True), ((BF16_, 1, 65536, 256), False),
+        ((F32_, 2, 1024, 256), False), ((BF16_, 0, 1024, 256), False),
+    ])
+
+
+def test_decode_stack_ok_table():
+    """dvq_decode_stack_ok(B, C, n_head, F, Tmax): both sides of every bound of dvq_decode_stack's shape check (csrc/decode.hip)"""
+    _table("dvq_decode_stack_ok", [
+        ((8, 1024, 8, 4096, 1288), True),
+        ((64, 1024, 8, 4096, 1288), True), ((65, 1024, 8, 4096, 1288), False), ((0, 1024, 8, 4096, 1288), False),   # B <= 64
+        ((8, 1040, 5, 4096, 64), False), ((8, 1056, 6, 4096, 64), True),                                            # C % 32 (head sizes 208 / 176)
+        ((8, 2048, 8, 4096, 64), True), ((8, 2080, 13, 4096, 64), False),                                           # C <= 2048 (head size 160: fine)
+        ((8, 1024, 8, 4080, 64), False), ((8, 1024, 8, 4064, 64), True), ((8, 1024, 8, 0, 64), False),              # F % 32
+        ((8, 96, 8, 128, 64), False), ((8, 96, 6, 128, 64), True), ((8, 96, 12, 128, 64), True),                    # head size % 8 (12 / 16 / 8)
+        ((8, 96, 5, 128, 64), False),                                                                               # C % n_head
+        ((8, 256, 1, 128, 64), True), ((8, 1056, 4, 128, 64), False),                                               # head size 256 / 264
+        ((8, 1024, 8, 4096, 12000), True), ((8, 1024, 8, 4096, 12001), False), ((8, 1024, 8, 4096, 0), False),      # Tmax <= 12000
+    ])
+
+
+def test_predicates_agree_with_the_python_rules_they_replace():
+    """the expressions kernels.attn_causal_ok / attn_full_ok and DecodeState._stack evaluated before the library exported its own
+    checks, verbatim, next to the library's answers -- on the product geometries: StackGPT p6c18 (configs/stage2/*: 1024 wide, 8
+    heads), the AttnBlock shapes of configs/stage1/* (256 channels at 32 x 32, 512 at 16 x 16 and 8 x 8) and the sampler's DecodeState
+    (16 x 16 + 32 x 32 + 8 cache rows) at batch 8 and 50 -- and, doubled by classifier-free guidance, 16 and 100"""
+    from dynamicvectorquantization_amd import _lib
+    lib = _lib.load()
+
+    def old_causal(bf16, c, n_head, b, t):
+        return bf16 and c in (n_head * 64, n_head * 128) and t % 8 == 0 and b * n_head <= 65535 and b * n_head * t * t < (1 << 32)
+
+    def old_full(bf16, rows, c, t):
+        return bf16 and c == 256 and t % 32 == 0 and rows // max(1, t) <= 65535
+
+    def old_stack(b, c, nh, max_rows):
+        return not (b > 64 or c % 32 or c > 2048 or (c // nh) % 8 or c // nh > 256 or max_rows > 12000)
+
+    for bf16 in (True, False):
+        dtype = BF16_ if bf16 else F32_
+        for b in (1, 2, 8, 30, 32, 50):
+            for t in (256, 257, 264, 648, 1024, 1280, 1288, 2048):
+                assert bool(lib.dvq_attn_causal_ok(dtype, b, t, 8, 1024 // 8)) == old_causal(bf16, 1024, 8, b, t), (bf16, b, t)
+        for b in (1, 2, 30, 64):
+            for c, t in ((256, 1024), (512, 256), (512, 64)):
+                assert bool(lib.dvq_attn_full_ok(dtype, (b * t) // max(1, t), t, c)) == old_full(bf16, b * t, c, t), (bf16, b, c, t)
+    rows = 16 * 16 + 32 * 32 + 8
+    for b in (8, 16, 50, 100):
+        assert bool(lib.dvq_decode_stack_ok(b, 1024, 8, 4 * 1024, rows)) == old_stack(b, 1024, 8, rows), b
+
+
+def test_last_kernel_is_empty_in_a_fresh_process():
+    import subprocess
+    out = subprocess.run([sys.executable, "-c", "from dynamicvectorquantization_amd import _lib; print(repr(_lib.load().dvq_last_kernel()))"],
+                         cwd=REPO, capture_output=True, text=True, timeout=120)
+    assert out.returncode == 0 and out.stdout.strip() == "b''", out.stdout + out.stderr
