@@ -176,6 +176,8 @@ SIGNATURES = {
     "dvq_code_histogram": (i32, [vp, vp, i64, i64, i64, i64, i64, i64, i32, vp, vp, vp, vp]),
     "dvq_token_nll": (i32, [vp, i32, i64, i64, i64, vp, i64, vp, vp, vp]),
     "dvq_nll_segment_sums": (i32, [vp, vp, i64, i64, i64, vp, vp]),
+    "dvq_tokens_pack": (i32, [vp, vp, i64, i32, i32, i64, vp, vp, vp, vp, vp]),
+    "dvq_tokens_unpack": (i32, [vp, vp, i64, i32, i32, i32, i64, i64, i64, i64, i64, i64, i64, i64, vp, vp, vp, vp, vp]),
 }
 
 

@@ -272,14 +272,25 @@ class LikelihoodMeter:
         return out
 
 
+def token_pixels_per_image(model) -> int:
+    """H * W * 3 of the images behind a token batch: the fine grid times the first stage's downsampling, i.e. the resolution its encoder
+    was built for"""
+    side = int(model.first_stage_model.encoder.resolution)
+    return side * side * 3
+
+
 def evaluate_likelihood(model, batches, per_image: bool = False) -> dict:
     """Teacher-forced likelihood of images under a Dualformer / ClassDualformer: one model.score per batch (frozen DQ-VAE -> codes ->
     permuter -> StackGPT in eval mode, no dropout, no gradient), blocks kept on the device, one host copy at the end.  batches: dicts
-    for model.get_xc ({"image": ..., "class_label": ...}), or bare image tensors for an unconditional model.  Keys: see
+    for model.get_xc ({"image": ..., "class_label": ...}), bare image tensors for an unconditional model, or token batches
+    ({"tokens": ...} of tokens.TokenBatchLoader: model.score_tokens, no first stage).  Keys: see
     aggregate_likelihood(), plus dtype; per_image=True adds "per_image", the [N, 4, 4] fp64 array."""
     meter = LikelihoodMeter(model.content_loss_weight, model.position_loss_weight)
     with torch.no_grad():
         for batch in batches:
+            if isinstance(batch, dict) and "tokens" in batch:
+                meter.update(model.score_tokens(*model.get_tc(batch)), pixels_per_image=token_pixels_per_image(model))
+                continue
             if isinstance(batch, dict):
                 x, c = model.get_xc(batch)
             elif model.cond_stage_key == model.first_stage_key:

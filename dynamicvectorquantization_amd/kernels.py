@@ -1259,3 +1259,83 @@ def code_histogram(codes, grain, n_codes, n_grains, counts, invalid, tokens=None
     check(lib().dvq_code_histogram(_p(codes), _p(grain), b, hf, wf, hg, wg, int(n_codes), int(n_grains), _p(counts), _p(tokens),
                                    _p(invalid), _s()), "dvq_code_histogram")
     return tokens
+
+
+# ---------------------------------------------------------------------------------------------
+# token shards (csrc/tokens.hip, docs/design/16-token-shards.md)
+# ---------------------------------------------------------------------------------------------
+def _tokens_arg(name, t, dtype, shape):
+    if not torch.is_tensor(t) or t.dtype != dtype:
+        raise TypeError(f"{name}: expected a {dtype} tensor, got {t.dtype if torch.is_tensor(t) else type(t).__name__}")
+    if tuple(t.shape) != tuple(shape):
+        raise _lib.DvqError(f"{name}: expected shape {tuple(shape)}, got {tuple(t.shape)}")
+    return t
+
+
+def tokens_pack(indices, grain, codebook_size, out=None):
+    """indices int64 [B, fhw, fhw], grain int64 [B, hw1, hw1] (DualGrainVQModel.encode's info[2] and grain map) -> (codes uint16
+    [B, fhw * fhw], grain_bits uint32 [B, ceil(hw1^2 / 32)], n_fine_cells int32 [B], bad int32 [B]); definitions: include/dvq_hip.h,
+    dvq_tokens_pack.  out: the four tensors to write into, or None.  Never synchronises: the caller reads `bad`."""
+    if not torch.is_tensor(indices) or indices.dtype != torch.int64 or indices.dim() != 3 or indices.shape[1] != indices.shape[2]:
+        raise TypeError("tokens_pack: indices must be an int64 [B, fhw, fhw] tensor")
+    b, fhw = int(indices.shape[0]), int(indices.shape[1])
+    if not torch.is_tensor(grain) or grain.dtype != torch.int64 or grain.dim() != 3 or grain.shape[1] != grain.shape[2]:
+        raise TypeError("tokens_pack: grain must be an int64 [B, hw1, hw1] tensor")
+    hw1 = int(grain.shape[1])
+    if grain.shape[0] != b or hw1 == 0 or fhw % hw1:
+        raise _lib.DvqError(f"tokens_pack: grain {tuple(grain.shape)} does not tile indices {tuple(indices.shape)}")
+    if grain.device != indices.device:
+        raise _lib.DvqError("tokens_pack: indices and grain live on different devices")
+    words = (hw1 * hw1 + 31) // 32
+    dev = indices.device
+    if out is None:
+        out = (torch.empty(b, fhw * fhw, dtype=torch.uint16, device=dev), torch.empty(b, words, dtype=torch.uint32, device=dev),
+               torch.empty(b, dtype=torch.int32, device=dev), torch.empty(b, dtype=torch.int32, device=dev))
+    codes = _tokens_arg("tokens_pack: codes", out[0], torch.uint16, (b, fhw * fhw))
+    bits = _tokens_arg("tokens_pack: grain_bits", out[1], torch.uint32, (b, words))
+    n_fine = _tokens_arg("tokens_pack: n_fine_cells", out[2], torch.int32, (b,))
+    bad = _tokens_arg("tokens_pack: bad", out[3], torch.int32, (b,))
+    check(lib().dvq_tokens_pack(_p(indices), _p(grain), b, hw1, fhw // hw1, int(codebook_size), _p(codes), _p(bits), _p(n_fine), _p(bad),
+                                _s()), "dvq_tokens_pack")
+    return codes, bits, n_fine, bad
+
+
+def tokens_unpack(codes, grain_bits, hw1, hw2, order, codes6, lc, lf, n_fine_cells, out=None):
+    """codes uint16 [B, (hw1 * hw2)^2], grain_bits uint32 [B, ceil(hw1^2 / 32)] -> DualGrainSeperatePermuter.forward's dict (four int64
+    streams [B, lc] / [B, lf] from dvq_tokens_unpack, segments of zeros / ones).  order: "region-first" | "row-first"; codes6: (content
+    pad, content eos, coarse-position pad, eos, fine-position pad, eos).  n_fine_cells: the HOST's fine-cell count per image (sequence
+    of ints -- the caller has the bitmap): lc < max(coarse cells) + 1 or lf < max(fine codes) + 1 raises ValueError before anything is
+    launched.  out: the four stream tensors to write into, or None.  Never synchronises."""
+    if order not in ("region-first", "row-first"):
+        raise ValueError(f"tokens_unpack: order {order!r} is neither 'region-first' nor 'row-first'")
+    if len(codes6) != 6:
+        raise ValueError("tokens_unpack: codes6 = (content pad, content eos, coarse-position pad, eos, fine-position pad, eos)")
+    hw1, hw2, lc, lf = int(hw1), int(hw2), int(lc), int(lf)
+    ncell, q = hw1 * hw1, hw2 * hw2
+    if not torch.is_tensor(codes) or codes.dtype != torch.uint16:
+        raise TypeError(f"tokens_unpack: codes must be a uint16 tensor, got {getattr(codes, 'dtype', type(codes).__name__)}")
+    if not torch.is_tensor(grain_bits) or grain_bits.dtype != torch.uint32:
+        raise TypeError(f"tokens_unpack: grain_bits must be a uint32 tensor, got {getattr(grain_bits, 'dtype', type(grain_bits).__name__)}")
+    b = int(codes.shape[0])
+    _tokens_arg("tokens_unpack: codes", codes, torch.uint16, (b, ncell * q))
+    _tokens_arg("tokens_unpack: grain_bits", grain_bits, torch.uint32, (b, (ncell + 31) // 32))
+    if grain_bits.device != codes.device:
+        raise _lib.DvqError("tokens_unpack: codes and grain_bits live on different devices")
+    counts = [int(n) for n in n_fine_cells]
+    if len(counts) != b or any(n < 0 or n > ncell for n in counts):
+        raise ValueError(f"tokens_unpack: n_fine_cells must hold {b} counts in [0, {ncell}]")
+    need_c, need_f = ncell - min(counts) + 1, max(counts) * q + 1
+    if lc < need_c or lf < need_f:
+        raise ValueError(f"tokens_unpack: row lengths ({lc}, {lf}) cut a stream: the batch needs at least ({need_c}, {need_f})")
+    dev = codes.device
+    if out is None:
+        out = (torch.empty(b, lc, dtype=torch.int64, device=dev), torch.empty(b, lc, dtype=torch.int64, device=dev),
+               torch.empty(b, lf, dtype=torch.int64, device=dev), torch.empty(b, lf, dtype=torch.int64, device=dev))
+    cc = _tokens_arg("tokens_unpack: coarse_content", out[0], torch.int64, (b, lc))
+    cp = _tokens_arg("tokens_unpack: coarse_position", out[1], torch.int64, (b, lc))
+    fc = _tokens_arg("tokens_unpack: fine_content", out[2], torch.int64, (b, lf))
+    fp = _tokens_arg("tokens_unpack: fine_position", out[3], torch.int64, (b, lf))
+    check(lib().dvq_tokens_unpack(_p(codes), _p(grain_bits), b, hw1, hw2, 0 if order == "region-first" else 1, *[int(v) for v in codes6],
+                                  lc, lf, _p(cc), _p(cp), _p(fc), _p(fp), _s()), "dvq_tokens_unpack")
+    return {"coarse_content": cc, "fine_content": fc, "coarse_position": cp, "fine_position": fp,
+            "coarse_segment": torch.zeros_like(cc), "fine_segment": torch.ones_like(fc)}

@@ -286,12 +286,13 @@ class Dualformer(_SamplerMixinBase, nn.Module):
         _, z_out = self.encode_to_z(x)
         return self.transformer(**self.teacher_forcing_inputs(z_out, self.encode_to_c(c)))
 
-    @torch.no_grad()
-    def score(self, x, c):
-        """teacher-forced likelihood of the images x under conditioning c (what get_xc returns): fp64 device tensor [B, 4, 4], per
-        image and stream (StackGPT.SCORE_STREAMS) the (nll sum in nats, tokens, top-1 hits, top-5 hits) -- StackGPT.score.  The
-        transformer runs in eval mode (no dropout) whatever mode it is in; every module's training flag is put back as found."""
-        _, z_out = self.encode_to_z(x)
+    def forward_tokens(self, tokens, c):
+        """forward() from stored codes: `tokens` = the permuter's dict (tokens.TokenBatchLoader), no first stage, no host sync"""
+        return self.transformer(**self.teacher_forcing_inputs(tokens, self.encode_to_c(c)))
+
+    def _score_streams(self, z_out, c):
+        """StackGPT.score of the permuter dict z_out under conditioning c, the transformer in eval mode (no dropout) whatever mode it is
+        in; every module's training flag is put back as found"""
         inputs = self.teacher_forcing_inputs(z_out, self.encode_to_c(c))
         on = [m for m in self.transformer.modules() if m.training]        # (already in eval mode, the usual case: nothing to switch)
         for m in on:
@@ -302,7 +303,32 @@ class Dualformer(_SamplerMixinBase, nn.Module):
             for m in on:
                 m.training = True
 
+    @torch.no_grad()
+    def score(self, x, c):
+        """teacher-forced likelihood of the images x under conditioning c (what get_xc returns): fp64 device tensor [B, 4, 4], per
+        image and stream (StackGPT.SCORE_STREAMS) the (nll sum in nats, tokens, top-1 hits, top-5 hits) -- StackGPT.score.  The
+        transformer runs in eval mode (no dropout) whatever mode it is in; every module's training flag is put back as found."""
+        _, z_out = self.encode_to_z(x)
+        return self._score_streams(z_out, c)
+
+    @torch.no_grad()
+    def score_tokens(self, tokens, c):
+        """score() from stored codes (`tokens` = the permuter's dict of a token batch, c = what get_tc returns)"""
+        return self._score_streams(tokens, c)
+
+    def get_tc(self, batch):
+        """(tokens, conditioning) of a token batch.  The unconditional start tokens only need the batch size and the device
+        (PositionAwareSOSProvider.encode reads nothing else of its argument), so a stream stands in for the image that is not there"""
+        tokens = batch["tokens"]
+        if self.cond_stage_key == self.first_stage_key:
+            return tokens, tokens["coarse_content"]
+        if self.cond_stage_key not in batch:
+            raise KeyError(f"a token batch without '{self.cond_stage_key}' (the token set stores no labels) for a conditional model")
+        return tokens, batch[self.cond_stage_key]
+
     def shared_step(self, batch, batch_idx):
+        if "tokens" in batch:
+            return self.forward_tokens(*self.get_tc(batch))
         x, c = self.get_xc(batch)
         return self(x, c)
 

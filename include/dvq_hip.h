@@ -46,7 +46,8 @@ const char* dvq_last_error(void);
  * written in csrc ("conv3x3_halo_kernel", "conv_nt_pipe_kernel", ...; no template arguments, no fold / reduce / transpose helpers), noted
  * at the dispatch branch that launches it.  "" when nothing was noted (those entry points clear it first).  For timing labels. */
 const char* dvq_last_kernel(void);
-int dvq_version(void);     /* 113: dvq_last_kernel (kernel family of a conv call), dvq_attn_causal_ok / dvq_attn_full_ok / dvq_decode_stack_ok;
+int dvq_version(void);     /* 114: dvq_tokens_pack, dvq_tokens_unpack (token shards: stored code maps <-> stage-2 streams);
+                            * 113: dvq_last_kernel (kernel family of a conv call), dvq_attn_causal_ok / dvq_attn_full_ok / dvq_decode_stack_ok;
                             * 112: dvq_token_nll, dvq_nll_segment_sums (teacher-forced likelihood scoring);
                             * 111: dvq_sample_guided (classifier-free-guided constrained draw), dvq_label_dropout (null-label dropout);
                             * 110: dvq_recon_metrics (+ _workspace_bytes), dvq_code_histogram (reconstruction evaluation);
@@ -663,6 +664,23 @@ int dvq_code_histogram(const int64_t* idx, const int64_t* grain, int64_t B, int6
 int dvq_token_nll(const void* logits, int dtype, int64_t rows, int64_t V, int64_t ldl, const int64_t* target, int64_t ignore_index,
                   float* nll, int32_t* rank, dvq_stream_t stream);
 int dvq_nll_segment_sums(const float* nll, const int32_t* rank, int64_t B, int64_t Tp, int64_t split, double* out, dvq_stream_t stream);
+
+/* ---- token shards (docs/design/16-token-shards.md; no reference kernel: the reference re-encodes every image in every stage-2 step) ---
+ * dvq_tokens_pack: indices int64 [B][fhw][fhw], grain int64 [B][hw1][hw1] (what DualGrainVQModel.encode returns; fhw = hw1 * hw2) ->
+ *   codes u16 [B][fhw * fhw]; grain_bits u32 [B][W], W = ceil(hw1^2 / 32): bit c % 32 of word c / 32 is 1 iff cell c (row-major) is fine,
+ *   bits past the grid are 0; n_fine_cells int32 [B]; bad int32 [B] = codes outside [0, min(codebook_size, 65536)) + grain values other
+ *   than 0 / 1 of image b.  Such an image is still written: its codes are clamped into the range, a bad grain value counts as coarse.
+ * dvq_tokens_unpack: codes / grain_bits as above -> the four rows of dvq_permute_dual (same pad / eos arguments, order 0 region-first,
+ *   1 row-first with ANY hw2) at the caller's row lengths: coarse_content / coarse_position int64 [B][Lc], fine_content / fine_position
+ *   int64 [B][Lf], EOS-terminated and PAD-filled.  With Lc = max_b(coarse cells) + 1 and Lf = max_b(fine codes) + 1 they equal
+ *   DualGrainSeperatePermuter.forward's output bit for bit; larger lengths add padding; a row that does not fit is cut at Lc / Lf
+ *   (nothing is written beyond them).  Bits of grain_bits past the grid are ignored.  hw1^2 > 1024: DVQ_ESHAPE. */
+int dvq_tokens_pack(const int64_t* indices, const int64_t* grain, int64_t B, int hw1, int hw2, int64_t codebook_size, uint16_t* codes,
+                    uint32_t* grain_bits, int32_t* n_fine_cells, int32_t* bad, dvq_stream_t stream);
+int dvq_tokens_unpack(const uint16_t* codes, const uint32_t* grain_bits, int64_t B, int hw1, int hw2, int order, int64_t content_pad,
+                      int64_t content_eos, int64_t cpos_pad, int64_t cpos_eos, int64_t fpos_pad, int64_t fpos_eos, int64_t Lc, int64_t Lf,
+                      int64_t* coarse_content, int64_t* coarse_position, int64_t* fine_content, int64_t* fine_position,
+                      dvq_stream_t stream);
 
 #ifdef __cplusplus
 }

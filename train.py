@@ -46,6 +46,10 @@ def get_parser():
     p.add_argument("--real_data", action="store_true",
                    help="instantiate the config's `data:` section (data.build.DataModuleFromConfig -> GPU input pipeline, "
                         "$DVQ_IMAGENET_ROOT/train|val) instead of synthetic batches")
+    p.add_argument("--token_data", type=str, default="",
+                   help="stage 2 only: train from this token set (scripts/tools/tokenize_dataset.py) instead of images -- no first-stage "
+                        "forward, no image decoding")
+    p.add_argument("--token_val", type=str, default="", help="with --token_data: the token set of the validation loop")
     p.add_argument("--precision", type=str, default="bf16", help="compute dtype of the HIP path: bf16 | fp32 | fp32x3 (fp32 tensors, products as three bf16 MFMA passes on split operands)")
     p.add_argument("--logdir", type=str, default="logs")
     p.add_argument("--save_every", type=int, default=0,
@@ -150,6 +154,35 @@ def run(rank, world, opt, unknown):
                     yield {k: v for k, v in b.items() if torch.is_tensor(v)}      # strings (paths, synsets) stay on the host side
         real_iter = _batches()
 
+    token_iter, token_vloader = None, None
+    if opt.token_val and not opt.token_data:
+        raise SystemExit("--token_val needs --token_data")
+    if opt.token_data:
+        # stored codes instead of images (docs/design/16-token-shards.md); like --real_data: built BEFORE the Trainer, one shuffle per rank
+        if opt.real_data:
+            raise SystemExit("--token_data and --real_data are two sources for the same batches: give one")
+        if not hasattr(model, "forward_tokens"):
+            raise SystemExit(f"--token_data trains a stage-2 (DQ-Transformer) model; {opt.base} builds {type(model).__name__}")
+        from dynamicvectorquantization_amd import tokens as T
+
+        def token_loader(path, shuffle, seed):
+            ds = T.TokenShardDataset(path)
+            ds.check_model(model)
+            if len(ds) < bs:
+                raise SystemExit(f"{path}: {len(ds)} images do not fill one batch of {bs}")
+            return T.TokenBatchLoader(ds, bs, dev, model.permuter, shuffle=shuffle, seed=seed)
+        tloader = token_loader(opt.token_data, True, opt.seed + 977 * rank)
+        opt.steps_per_epoch = model.steps_per_epoch = len(tloader)
+        model.training_steps = len(tloader) * opt.max_epochs
+        if opt.token_val:
+            token_vloader = token_loader(opt.token_val, False, opt.seed)
+
+        def _token_batches():
+            while True:
+                for b in tloader:
+                    yield b
+        token_iter = _token_batches()
+
     total = model.training_steps if opt.max_steps < 0 else min(opt.max_steps, model.training_steps)
     trainer = Trainer(model, max_steps=total, log_every=10 if rank == 0 else 0)
     pool = [torch.from_numpy(synth.half_flat_images(bs, size, seed=opt.seed + 977 * rank + i)).to(dev) for i in range(4)]
@@ -161,6 +194,8 @@ def run(rank, world, opt, unknown):
 
     def batch_fn(step):
         model.current_epoch = step // opt.steps_per_epoch
+        if token_iter is not None:
+            return next(token_iter)
         if real_iter is not None:
             b = next(real_iter)
             return {image_key: b["image"], **({"class_label": b["class_label"]} if "class_label" in b and n_classes is not None else {})}
@@ -180,7 +215,13 @@ def run(rank, world, opt, unknown):
     # the model's `monitor` (val_rec_loss in the shipped stage-1 YAMLs) picks the --save_n best checkpoints kept beside last.ckpt
     val_fn = None
     if opt.check_val_every_n_epoch > 0 and hasattr(model, "validation_step"):
-        if opt.real_data and "validation" not in getattr(dm, "datasets", {"validation": None}):
+        if token_iter is not None:
+            if token_vloader is not None:
+                def val_fn():
+                    return iter(token_vloader)
+            elif rank == 0:
+                print("no --token_val: training without the validation loop")
+        elif opt.real_data and "validation" not in getattr(dm, "datasets", {"validation": None}):
             if rank == 0:
                 print("the data config has no validation split: training without the validation loop")
         elif opt.real_data:
