@@ -178,6 +178,16 @@ SIGNATURES = {
     "dvq_nll_segment_sums": (i32, [vp, vp, i64, i64, i64, vp, vp]),
     "dvq_tokens_pack": (i32, [vp, vp, i64, i32, i32, i64, vp, vp, vp, vp, vp]),
     "dvq_tokens_unpack": (i32, [vp, vp, i64, i32, i32, i32, i64, i64, i64, i64, i64, i64, i64, i64, vp, vp, vp, vp, vp]),
+    "dvq_vq_trained_prep_bytes": (sz, [i64, i64]),
+    "dvq_vq_trained_prepare": (i32, [vp, i64, i64, i32, vp, vp]),
+    "dvq_vq_sample_argmax": (i32, [vp, i32, vp, vp, i64, i64, i64, i32, f32, vp, vp, vp]),
+    "dvq_vq_gumbel_noise": (i32, [C.c_uint64, C.c_uint64, i64, i64, vp, vp]),
+    "dvq_vq_codebook_grad": (i32, [vp, i32, vp, vp, vp, vp, i64, i64, i64, vp, vp]),
+    "dvq_vq_mask_ratio": (i32, [vp, i64, vp, vp]),
+    "dvq_vq_rownorm": (i32, [vp, i64, i64, vp, vp, vp]),
+    "dvq_vq_ortho_scratch_bytes": (sz, []),
+    "dvq_vq_ortho_sumsq": (i32, [vp, i64, f32, vp, vp, vp]),
+    "dvq_vq_rownorm_bwd": (i32, [vp, vp, vp, vp, f32, i64, i64, vp, vp]),
 }
 
 

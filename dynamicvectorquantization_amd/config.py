@@ -34,6 +34,7 @@ TARGET_ALIASES = {
     "modules.dynamic_modules.fourier_embedding.FourierPositionEmbedding": (_P + "dqvae", "FourierPositionEmbedding"),
     "modules.vector_quantization.quantize2_mask.VectorQuantize2": (_P + "quantize", "VectorQuantize2"),
     "modules.vector_quantization.quantize2_mask.VQEmbedding": (_P + "quantize", "VQEmbedding"),
+    "modules.vector_quantization.quantize_codebook_mask.MaskVectorQuantize": (_P + "quantize_trained", "MaskVectorQuantize"),
     "modules.diffusionmodules.model.ResnetBlock": (_P + "layers", "ResnetBlock"),
     "modules.diffusionmodules.model.AttnBlock": (_P + "layers", "AttnBlock"),
     "modules.diffusionmodules.model.Upsample": (_P + "layers", "Upsample"),

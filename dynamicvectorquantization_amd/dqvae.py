@@ -548,7 +548,10 @@ class DualGrainVQModel(nn.Module):
             gate_out = gate.permute(0, 3, 1, 2)
             h_dual, mask, _ = self.encoder.fwd(x, grain, _child(tape, "enc"))
         h = self.quant_conv.fwd(h_dual, _child(tape, "qc"))
-        xq, qloss, codes = self.quantize.fwd(h, mask, _child(tape, "vq"))
+        if getattr(self.quantize, "takes_temperature", False):      # quantisers that sample their code (MaskVectorQuantize)
+            xq, qloss, codes = self.quantize.fwd(h, mask, _child(tape, "vq"), temp=self.quant_sample_temperature)
+        else:
+            xq, qloss, codes = self.quantize.fwd(h, mask, _child(tape, "vq"))
         z = self.post_quant_conv.fwd(xq, _child(tape, "pqc"))
         rec_p = self.decoder.fwd(z, _child(tape, "dec"))
         rec = K.nhwc_pad_to_nchw(rec_p, self.decoder.out_ch)
@@ -725,6 +728,10 @@ class DualGrainVQModel(nn.Module):
         cb = getattr(self.quantize, "codebook", None)
         if getattr(cb, "restart_perm", None) is not None or getattr(self.encoder, "gumbel_exponential", None) is not None:
             return None                      # injected test noise lives on the host
+        if getattr(self.quantize, "kmeans_perm", None) is not None:
+            return None                      # injected k-means starting rows (tests)
+        if hasattr(self.quantize, "is_initted") and self.training and not self.quantize.is_initted():
+            return None                      # the k-means initialisation of a trained codebook runs eagerly on the first training forward
         if any(isinstance(m, ResnetBlock) and m.dropout.p > 0.0 for m in self.modules()):
             return None                      # dropout seeds are drawn on the host per call (a replay would repeat the masks)
         if getattr(getattr(self.loss, "perceptual_loss", None), "lin_dropout", False):

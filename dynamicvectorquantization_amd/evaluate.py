@@ -150,9 +150,11 @@ def evaluate_reconstruction(model, batches, quantize_u8: bool = True, lpips=None
     pretrained_loaded).  on_batch(x, out): optional callback with the batch and ae_fwd's output dict.
     Keys: see aggregate(), plus ema_dead_codes (codes with cluster_size_ema < 1) and dtype."""
     model.eval()
-    cbk = model.quantize.codebook
-    meter = ReconstructionMeter(cbk.n_embed, model.N_GRAINS, quantize_u8=quantize_u8)
-    lp_mod = _lpips_module(lpips, cbk.weight.device)
+    from .quantize import codebook_of
+    weight, n_codes = codebook_of(model.quantize)
+    cbk = getattr(model.quantize, "codebook", None)          # the EMA quantiser's embedding (None for a gradient-trained codebook)
+    meter = ReconstructionMeter(n_codes, model.N_GRAINS, quantize_u8=quantize_u8)
+    lp_mod = _lpips_module(lpips, weight.device)
     with torch.no_grad():
         for batch in batches:
             x = batch[getattr(model, "image_key", "image")] if isinstance(batch, dict) else batch

@@ -277,6 +277,78 @@ def vq_ema_apply(stats, restart_rows, decay, eps, cluster_size_ema, embed_ema, w
                                  _p(weight), None, _s()), "dvq_vq_ema_apply")
 
 
+# -- gradient-trained codebook (csrc/vq_trained.hip) ------------------------------------------------
+def vq_trained_prepare(codebook: torch.Tensor, cosine: bool) -> torch.Tensor:
+    """split planes + per-code bias of dvq_vq_sample_argmax (cosine: rows normalised); rebuild when the codebook changes"""
+    k, d = codebook.shape
+    assert codebook.dtype == torch.float32
+    prep = torch.empty(lib().dvq_vq_trained_prep_bytes(k, d), dtype=torch.uint8, device=codebook.device)
+    check(lib().dvq_vq_trained_prepare(_p(codebook), k, d, int(bool(cosine)), _p(prep), _s()), "dvq_vq_trained_prepare")
+    return prep
+
+
+def vq_sample_argmax(x, prep, k, cosine: bool, temp: float = 0.0, state=None, codebook=None):
+    """x [N,D] (fp32/bf16), prep = vq_trained_prepare(codebook [k,D], cosine) -> idx int64 [N] = argmax_k (score / temp + Gumbel noise),
+    lowest index on ties; temp == 0: no noise.  state: device int64 [2] {seed, counter}; the counter advances by one per noisy call.
+    codebook: the raw fp32 [k,D] rows, needed by the noiseless cosine search (its near ties are re-ranked in fp64: exact)."""
+    n, d = x.shape
+    idx = torch.empty(n, dtype=torch.int64, device=x.device)
+    nbytes = n * d * x.element_size() + k * d * 4 + n * 8
+    _timed("vq_sample_argmax", 2 * n * k * d, nbytes, lambda: check(
+        lib().dvq_vq_sample_argmax(_p(x), dt(x), _p(prep), _p(codebook), n, k, d, int(bool(cosine)), float(temp), _p(state), _p(idx), _s()),
+        "dvq_vq_sample_argmax"))
+    return idx
+
+
+def vq_gumbel_noise(seed: int, counter: int, n: int, k: int, device) -> torch.Tensor:
+    """fp32 [n,k]: the noise vq_sample_argmax adds while its state holds (seed, counter); tests and analysis"""
+    out = torch.empty(n, k, dtype=torch.float32, device=device)
+    check(lib().dvq_vq_gumbel_noise(int(seed) & (2 ** 64 - 1), int(counter) & (2 ** 64 - 1), n, k, _p(out), _s()), "dvq_vq_gumbel_noise")
+    return out
+
+
+def vq_codebook_grad(x, codebook, idx, mask, coef_dev, grad):
+    """grad [K,D] fp32 += coef_dev[0] * sum_{n: idx[n] = k} mask[n] (codebook[k] - x[n]); bit-reproducible under set_deterministic"""
+    n, d = x.shape
+    k = codebook.shape[0]
+    assert grad.dtype == torch.float32 and tuple(grad.shape) == (k, d) and codebook.dtype == torch.float32
+    _timed("vq_codebook_grad", 2 * n * d, n * d * x.element_size() + n * 8 + 2 * k * d * 4, lambda: check(
+        lib().dvq_vq_codebook_grad(_p(x), dt(x), _p(codebook), _p(idx), _p(mask), _p(coef_dev), n, k, d, _p(grad), _s()),
+        "dvq_vq_codebook_grad"))
+    return grad
+
+
+def vq_mask_ratio(mask):
+    """fp32 device scalar [1] = numel / sum(mask)"""
+    out = torch.empty(1, dtype=torch.float32, device=mask.device)
+    check(lib().dvq_vq_mask_ratio(_p(mask), mask.numel(), _p(out), _s()), "dvq_vq_mask_ratio")
+    return out
+
+
+def vq_rownorm(e):
+    """e [K,D] fp32 -> (w = e / max(|e|, 1e-12) per row, inv [K] = the reciprocals)"""
+    k, d = e.shape
+    w = torch.empty_like(e)
+    inv = torch.empty(k, dtype=torch.float32, device=e.device)
+    check(lib().dvq_vq_rownorm(_p(e), k, d, _p(w), _p(inv), _s()), "dvq_vq_rownorm")
+    return w, inv
+
+
+def vq_ortho_sumsq(g, k, scale):
+    """g [k,k] fp32 -= I in place -> fp32 device scalar [1] = scale * sum(g^2) (fixed summation order)"""
+    scratch = torch.empty(lib().dvq_vq_ortho_scratch_bytes(), dtype=torch.uint8, device=g.device)
+    out = torch.empty(1, dtype=torch.float32, device=g.device)
+    check(lib().dvq_vq_ortho_sumsq(_p(g), k, float(scale), _p(scratch), _p(out), _s()), "dvq_vq_ortho_sumsq")
+    return out
+
+
+def vq_rownorm_bwd(w, inv, dw, coef_dev, scale, grad):
+    """grad [K,D] += coef_dev[0] * scale * inv[k] * (dw[k] - w[k] (w[k] . dw[k]))"""
+    k, d = w.shape
+    check(lib().dvq_vq_rownorm_bwd(_p(w), _p(inv), _p(dw), _p(coef_dev), float(scale), k, d, _p(grad), _s()), "dvq_vq_rownorm_bwd")
+    return grad
+
+
 # ---------------------------------------------------------------------------------------------
 # entropy / gate
 # ---------------------------------------------------------------------------------------------

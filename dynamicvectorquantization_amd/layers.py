@@ -291,6 +291,7 @@ class _LinearPackRegistry:
     def __init__(self):
         self.items = {}       # device -> list of weakref(module)
         self.tables = {}      # (device, group) -> dict(sig, table, n, tiles)
+        self.retired = []     # replaced tables, kept alive (see _PackRegistry.retired)
 
     @staticmethod
     def _key(m):
@@ -312,7 +313,7 @@ class _LinearPackRegistry:
         if not known:
             self.items.setdefault(dev, []).append(weakref.ref(mod))
         for k in [k for k in self.tables if k[0] == dev]:
-            self.tables.pop(k, None)
+            self.retired.append(self.tables.pop(k))
         return ent
 
     def _launch(self, mods, cache_key=None):
@@ -332,6 +333,8 @@ class _LinearPackRegistry:
             raw = torch.frombuffer(bytearray(bytes(arr)), dtype=torch.uint8).to(mods[0].weight.device)
             tab = {"sig": sig, "table": raw, "n": len(mods), "tiles": begin}
             if cache_key is not None:
+                if cache_key in self.tables:
+                    self.retired.append(self.tables[cache_key])
                 self.tables[cache_key] = tab
         K.linear_pack_multi(tab["table"], tab["n"], tab["tiles"])
         for m in mods:
@@ -638,13 +641,19 @@ class _PackRegistry:
     def __init__(self):
         self.items = {}       # (dtype, device) -> list of (weakref(module))
         self.tables = {}      # (dtype, device) -> dict(sig, table tensor, n, total)
+        # Tables that were replaced.  A recorded training step has the device address of the table it was recorded with baked into
+        # its dvq_pack_weights_multi launch, and that table lives in the ordinary allocator pool (it is built in an eager step: the
+        # host-to-device copy cannot be captured).  A second model whose convolutions register later used to drop the first model's
+        # table here; its memory went back to the allocator, the second recording's empty_cache() unmapped it, and the first model's
+        # next replay read the table from an unmapped address.  A table is a few KB and still describes live buffers: keep it.
+        self.retired = []
 
     def register(self, mod, dtype):
         import weakref
         key = (dtype, mod.weight.device)
         self.items.setdefault(key, []).append(weakref.ref(mod))
         for k in [k for k in self.tables if k[:2] == key]:
-            self.tables.pop(k, None)
+            self.retired.append(self.tables.pop(k))
 
     def repack(self, dtype, device, group=0):
         import ctypes
@@ -669,6 +678,8 @@ class _PackRegistry:
                 begin += m.out_channels * k2 * e["cin_p"] + m.in_channels * k2 * e["cout_p"]
             raw = torch.frombuffer(bytearray(bytes(arr)), dtype=torch.uint8).to(device)
             tab = {"sig": sig, "table": raw, "n": len(live), "total": begin}
+            if key in self.tables:
+                self.retired.append(self.tables[key])
             self.tables[key] = tab
         K.pack_weights_multi(tab["table"], tab["n"], tab["total"])
         for m in live:

@@ -246,6 +246,19 @@ class VectorQuantize2(nn.Module):
         return self.codebook.embed(indices)   # (batch, height, width, channel)
 
 
+def codebook_of(quantizer):
+    """(codebook weight as the quantiser stores it, number of codes K) of either quantiser: VectorQuantize2 keeps `codebook.weight`
+    [K+1, D] (row K is the padding row; it stays in, so that token-shard fingerprints made from this tensor do not change),
+    MaskVectorQuantize keeps `embedding.weight` [K, D].  Rows 0 .. K-1 are the codes in both."""
+    cb = getattr(quantizer, "codebook", None)
+    if cb is not None:
+        return cb.weight, int(cb.n_embed)
+    emb = getattr(quantizer, "embedding", None)
+    if emb is not None:
+        return emb.weight, int(emb.weight.shape[0])
+    raise TypeError(f"{type(quantizer).__name__} has no codebook this package knows (VectorQuantize2.codebook / MaskVectorQuantize.embedding)")
+
+
 class _VQFn(torch.autograd.Function):
     @staticmethod
     def forward(ctx, module, x, mask):

@@ -99,12 +99,13 @@ def fingerprint_arrays(codebook_weight, threshold) -> str:
 
 
 def first_stage_fingerprint(first_stage) -> str:
-    """fingerprint_arrays of a DualGrainVQModel: quantize.codebook.weight and the fixed entropy router's fine_grain_threshold"""
+    """fingerprint_arrays of a DualGrainVQModel: the quantiser's stored codebook weight (quantize.codebook_of) and the fixed entropy router's fine_grain_threshold"""
     router = getattr(getattr(first_stage, "encoder", None), "router", None)
     thr = getattr(router, "fine_grain_threshold", None)
     if thr is None:
         return FEATURE_ROUTER
-    w = first_stage.quantize.codebook.weight
+    from .quantize import codebook_of
+    w = codebook_of(first_stage.quantize)[0]
     return fingerprint_arrays(w.detach().float().cpu().numpy(), thr)
 
 
@@ -112,7 +113,8 @@ def describe_model(model) -> dict:
     """what a token set must agree with: a Dualformer (hw1 / hw2 from its permuter, first_stage_model) or a bare first stage given
     together with hw1 / hw2 attributes"""
     fs = getattr(model, "first_stage_model", model)
-    return {"hw1": int(model.hw1), "hw2": int(model.hw2), "codebook_size": int(fs.quantize.codebook.n_embed),
+    from .quantize import codebook_of
+    return {"hw1": int(model.hw1), "hw2": int(model.hw2), "codebook_size": codebook_of(fs.quantize)[1],
             "fingerprint": first_stage_fingerprint(fs)}
 
 

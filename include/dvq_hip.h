@@ -46,7 +46,9 @@ const char* dvq_last_error(void);
  * written in csrc ("conv3x3_halo_kernel", "conv_nt_pipe_kernel", ...; no template arguments, no fold / reduce / transpose helpers), noted
  * at the dispatch branch that launches it.  "" when nothing was noted (those entry points clear it first).  For timing labels. */
 const char* dvq_last_kernel(void);
-int dvq_version(void);     /* 114: dvq_tokens_pack, dvq_tokens_unpack (token shards: stored code maps <-> stage-2 streams);
+int dvq_version(void);     /* 115: dvq_vq_sample_argmax (+ dvq_vq_trained_prepare), dvq_vq_gumbel_noise, dvq_vq_codebook_grad, dvq_vq_mask_ratio,
+                            * dvq_vq_rownorm / _ortho_sumsq / _rownorm_bwd (gradient-trained codebook: Gumbel search, codebook gradient, orthogonality term);
+                            * 114: dvq_tokens_pack, dvq_tokens_unpack (token shards: stored code maps <-> stage-2 streams);
                             * 113: dvq_last_kernel (kernel family of a conv call), dvq_attn_causal_ok / dvq_attn_full_ok / dvq_decode_stack_ok;
                             * 112: dvq_token_nll, dvq_nll_segment_sums (teacher-forced likelihood scoring);
                             * 111: dvq_sample_guided (classifier-free-guided constrained draw), dvq_label_dropout (null-label dropout);
@@ -681,6 +683,41 @@ int dvq_tokens_unpack(const uint16_t* codes, const uint32_t* grain_bits, int64_t
                       int64_t content_eos, int64_t cpos_pad, int64_t cpos_eos, int64_t fpos_pad, int64_t fpos_eos, int64_t Lc, int64_t Lf,
                       int64_t* coarse_content, int64_t* coarse_position, int64_t* fine_content, int64_t* fine_position,
                       dvq_stream_t stream);
+
+/* ---- gradient-trained codebook (MaskVectorQuantize, quantize_codebook_mask.py) -- csrc/vq_trained.hip ----------------------------
+ * Prepared codebook of dvq_vq_sample_argmax: two bf16 planes (e = e1 + e2 to 2^-17) and a per-code bias; cosine != 0 stores the rows
+ * normalised (e / max(|e|, 1e-12)) with bias 0, else the raw rows with bias -|e_k|^2.  Rebuild it whenever the codebook changes. */
+size_t dvq_vq_trained_prep_bytes(int64_t K, int64_t D);
+int dvq_vq_trained_prepare(const float* codebook, int64_t K, int64_t D, int cosine, void* prep, dvq_stream_t stream);
+/* idx[n] = argmax_k (s[n,k] / temp + g(n,k)), lowest index on ties, never forming [N,K].  s = -|x_n - e_k|^2 (cosine == 0) or the cosine
+ * similarity of x_n and e_k (`cosine` must match the prepare call); g = -log(-log(u)) Gumbel noise from a counter-based hash of
+ * (seed, draw counter, n, k).  temp == 0: no noise (plain argmax of s; `state` may be NULL).  temp > 0: state = uint64[2] {seed, counter}
+ * in device memory, the counter is advanced by ONE on the stream after the search (replays of a recorded step draw fresh noise).
+ * x: [N,D] fp32 or bf16.  D in {64, 128, 256}: bf16 MFMA with split operands (x1.e1 + x1.e2 + x2.e1, fp32 accumulate; bf16 rows:
+ * two products); every other D <= 4096: a plain kernel.  N < 2^31, K < 2^24.  With noise there is no re-rank: scores closer than the
+ * evaluation error (~3 * 2^-18 |x||e| / temp) may resolve either way.  The noiseless COSINE search (cosine != 0, temp == 0) is exact:
+ * rows whose two best scores are within the evaluation bound are re-ranked in fp64 from `codebook` (the raw fp32 [K,D] rows the
+ * prepare call saw; required in that case, else it may be NULL).  The noiseless L2 form is not re-ranked: dvq_vq_argmin is the exact one. */
+int dvq_vq_sample_argmax(const void* x, int x_dtype, const void* prep, const float* codebook, int64_t N, int64_t K, int64_t D, int cosine,
+                         float temp, uint64_t* state, int64_t* idx, dvq_stream_t stream);
+/* out[n,k] = g(n,k) of the draw (seed, counter): the noise dvq_vq_sample_argmax adds when its state holds these two values.
+ * fp32 [N,K]; tests and analysis only. */
+int dvq_vq_gumbel_noise(uint64_t seed, uint64_t counter, int64_t N, int64_t K, float* out, dvq_stream_t stream);
+/* grad[k,:] += coef_dev[0] * sum_{n: idx[n] = k} mask[n] * (codebook[k,:] - x[n,:])   (mask NULL = 1).  grad: fp32 [K,D], accumulated.
+ * One wave per (code, slice of 1024 rows) + fp32 atomics; under dvq_set_deterministic(1) one wave per code walks all rows in order
+ * and adds without atomics: repeated launches are bit-identical. */
+int dvq_vq_codebook_grad(const void* x, int dtype, const float* codebook, const int64_t* idx, const float* mask, const float* coef_dev,
+                         int64_t N, int64_t K, int64_t D, float* grad, dvq_stream_t stream);
+/* out[0] = N / sum(mask) (fp32; one workgroup, fixed order): the loss' mask-ratio normalisation without a host read */
+int dvq_vq_mask_ratio(const float* mask, int64_t N, float* out, dvq_stream_t stream);
+/* Orthogonality regulariser sum((W W^T - I)^2), W = normalize(E), around the caller's two GEMMs:
+ * rownorm: w[k,:] = e[k,:] * inv[k], inv[k] = 1 / max(|e[k,:]|, 1e-12);  ortho_sumsq: g [K,K] -= I in place, out[0] = scale * sum(g^2)
+ * (scratch: dvq_vq_ortho_scratch_bytes());  rownorm_bwd: grad[k,:] += coef_dev[0] * scale * inv[k] * (dw[k,:] - w[k,:] (w[k,:] . dw[k,:])) */
+int dvq_vq_rownorm(const float* e, int64_t K, int64_t D, float* w, float* inv, dvq_stream_t stream);
+size_t dvq_vq_ortho_scratch_bytes(void);
+int dvq_vq_ortho_sumsq(float* g, int64_t K, float scale, void* scratch, float* out, dvq_stream_t stream);
+int dvq_vq_rownorm_bwd(const float* w, const float* inv, const float* dw, const float* coef_dev, float scale, int64_t K, int64_t D,
+                       float* grad, dvq_stream_t stream);
 
 #ifdef __cplusplus
 }

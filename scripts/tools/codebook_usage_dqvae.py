@@ -17,6 +17,7 @@ import sys
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.dirname(os.path.abspath(__file__)))))
 
 from dynamicvectorquantization_amd import evaluate as E  # noqa: E402
+from dynamicvectorquantization_amd.quantize import codebook_of  # noqa: E402
 
 
 def main():
@@ -27,7 +28,7 @@ def main():
     from dynamicvectorquantization_amd import runtime as rt
     rt.set_compute_dtype(opt.dtype)
     model, size = E.load_model(opt.yaml_path, opt.model_path, "cuda")
-    k = model.quantize.codebook.n_embed
+    k = codebook_of(model.quantize)[1]
     if opt.codebook_size is not None and opt.codebook_size != k:
         print(f"warning: --codebook_size {opt.codebook_size} differs from the model's {k} codes", file=sys.stderr)
     s = E.evaluate_reconstruction(model, E.image_batches(opt.batch_size, size, "cuda", source, opt.synthetic, opt.limit), lpips=False)

@@ -21,6 +21,7 @@ sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.dirname(os.path.abspa
 
 from dynamicvectorquantization_amd import evaluate as E  # noqa: E402
 from dynamicvectorquantization_amd import tokens as T  # noqa: E402
+from dynamicvectorquantization_amd.quantize import codebook_of  # noqa: E402
 
 
 def get_parser():
@@ -164,7 +165,7 @@ def main():
         batches = tensor_view_batches(E.image_batches(opt.batch_size, size, dev, source, opt.synthetic, n), views, lo, hi)
     else:
         batches = decoded_view_batches(ds, views, lo, hi, opt.batch_size, size, dev, opt.seed, opt.num_workers)
-    writer = T.TokenShardWriter(opt.out, hw1, hw2, model.quantize.codebook.n_embed, views, shard_size=opt.shard_size,
+    writer = T.TokenShardWriter(opt.out, hw1, hw2, codebook_of(model.quantize)[1], views, shard_size=opt.shard_size,
                                 compute_dtype=E.dtype_name(), fingerprint=T.first_stage_fingerprint(model), dataset=described, part=part)
     stats = T.tokenize_batches(model, batches, writer)
     writer.close()
