@@ -1,4 +1,5 @@
-// Fused causal multi-head self-attention of the stage-2 transformer (bf16, head size 64 or 128), forward and backward:
+// Fused causal multi-head self-attention of the stage-2 transformer (bf16), forward and backward.  The kernels of this file serve
+// head size 64; causal head size 128 and the DQ-VAE's full attention (one head of 256) run on attention2.hip, entered from here:
 //   CausalSelfAttention.forward   modules/dynamic_modules/stackgpt.py:41-69
 //       att = softmax(mask(q k^T / sqrt(hs)));  att = attn_drop(att);  y = att v
 // The unfused path (per-head GEMMs + softmax + dropout kernels, stackgpt.py of this package) moves the [B, nh, T, T] score
@@ -38,7 +39,7 @@ struct AttnParams {
     float* dsum;                             // [B][nh][T]: rowsum(dO * O)
     int T, nh, C;
     int causal;                              // 1: stage-2 causal attention; 0: full attention (AttnBlock of the DQ-VAE: one head of size
-                                             //    C, every query sees every key; T % 32 == 0)
+                                             //    C, every query sees every key; T % 32 == 0: attention2.hip only)
     float scale;                             // 1 / sqrt(hs)
     float inv_keep;                          // 1 / (1 - p)
     unsigned thr, rm, ra;                    // dropout: keep iff dvq_hash32(idx * rm + ra) >= thr (thr == 0: no dropout)
@@ -173,7 +174,7 @@ __device__ __forceinline__ void store_ct(bf16_t* dst /* row base + head offset *
 // ------------------------------------------------------------------------------------------------------------------
 // (two workgroups per CU: without the explicit bound the compiler spreads into AGPRs and settles for one wave per SIMD)
 template <int HS>
-__global__ __launch_bounds__(256, HS <= 128 ? 2 : 1) void attn_fwd_kernel(AttnParams p) {
+__global__ __launch_bounds__(256, 2) void attn_fwd_kernel(AttnParams p) {
     using G = Geo<HS>;
     constexpr int NS = HS / 16, NM = HS / 32, STAGE = G::RTILE + G::CTILE;
     extern __shared__ __attribute__((aligned(16))) char smem[];
@@ -315,7 +316,7 @@ __global__ __launch_bounds__(256) void attn_rowdot_kernel(AttnParams p, int64_t 
 // backward, dQ: one wave per 32 queries (same walk as the forward); LDS stage = K, V (row-major) and K^T tiles
 // ------------------------------------------------------------------------------------------------------------------
 template <int HS, bool MASKED = false>
-__global__ __launch_bounds__(256, HS <= 128 ? 2 : 1) void attn_bwd_dq_kernel(AttnParams p) {
+__global__ __launch_bounds__(256, 2) void attn_bwd_dq_kernel(AttnParams p) {
     using G = Geo<HS>;
     constexpr int NS = HS / 16, NM = HS / 32, STAGE = 2 * G::RTILE + G::CTILE;
     extern __shared__ __attribute__((aligned(16))) char smem[];
@@ -344,8 +345,8 @@ __global__ __launch_bounds__(256, HS <= 128 ? 2 : 1) void attn_bwd_dq_kernel(Att
     // dsum[query] = sum_ch dO * O: taken here from the dO fragments this wave holds anyway (+ the matching O fragments) and left in
     // p.dsum for the dK kernel, which is launched after this one (a separate one-thread-per-row pass over dO and O was 38 us per layer)
     float dq_ = 0.f;
-    if (HS > 128 || (p.dbg & 16)) {                              // (head size 256 has no registers to spare: the separate pass stays;
-        dq_ = qok ? p.dsum[(int64_t)bh * T + qrow] : 0.f;        //  DVQ_ATTN_DBG=16: A/B against the separate pass)
+    if (p.dbg & 16) {                                            // (DVQ_ATTN_DBG=16: A/B against the separate pass)
+        dq_ = qok ? p.dsum[(int64_t)bh * T + qrow] : 0.f;
     } else {
         const bf16_t* op = p.o + (rowbase + qrow) * C + h * HS + 8 * half;
 #pragma unroll
@@ -427,8 +428,6 @@ __global__ __launch_bounds__(256, HS <= 128 ? 2 : 1) void attn_bwd_dq_kernel(Att
             if (p.dbg & 2) {
 #pragma unroll
                 for (int r = 0; r < 16; ++r) s[r] += dp[r];
-            } else if constexpr (HS > 128) {
-                elementwise(std::false_type{});                  // full attention only (T % 32 == 0): no diagonal tiles
             } else {
                 if (diag) elementwise(std::true_type{});
                 else elementwise(std::false_type{});
@@ -460,12 +459,9 @@ __global__ __launch_bounds__(256, HS <= 128 ? 2 : 1) void attn_bwd_dq_kernel(Att
 // backward, dK and dV: one wave per 32 keys; the workgroup walks the query tiles from its first key tile to the end;
 // LDS stage = Q, dO (row-major) and Q^T, dO^T tiles
 // ------------------------------------------------------------------------------------------------------------------
-// (head size 128 keeps one wave per SIMD: 128 accumulator + 64 resident operand registers do not fit 256 without spilling)
-// MODE 0: dK and dV together; 1: dV only; 2: dK only.  Head size 256 runs as two launches (1, then 2): 2 x 128 accumulator
-// registers next to 2 x 64 resident operand registers and the staged tiles do not fit one wave (measured: 1220 B/lane of
-// scratch); the score tile is then computed by both launches (1.25x the flops of this kernel).
+// MODE 0: dK and dV together (the one launch head size 64 makes); 1: dV only; 2: dK only.
 template <int HS, int MODE = 0, bool MASKED = false>
-__global__ __launch_bounds__(256, (HS == 64 || (HS == 128 && MODE != 0)) ? 2 : 1) void attn_bwd_dkv_kernel(AttnParams p) {
+__global__ __launch_bounds__(256, 2) void attn_bwd_dkv_kernel(AttnParams p) {
     constexpr bool DO_DV = MODE != 2, DO_DK = MODE != 1;
     using G = Geo<HS>;
     constexpr int NS = HS / 16, NM = HS / 32, STAGE = 2 * G::RTILE + 2 * G::CTILE;
@@ -594,12 +590,8 @@ __global__ __launch_bounds__(256, (HS == 64 || (HS == 128 && MODE != 0)) ? 2 : 1
                     }
                 }
             };
-            if constexpr (HS > 128) {
-                second(std::false_type{});                       // full attention only (T % 32 == 0): no diagonal / ragged tiles
-            } else {
-                if (edge) second(std::true_type{});
-                else second(std::false_type{});
-            }
+            if (edge) second(std::true_type{});
+            else second(std::false_type{});
         }
         if (more) {
             char* nl = smem + ((qt + 1 - qt_first) & 1) * STAGE;
@@ -624,44 +616,21 @@ int launch_fwd(const AttnParams& p, dim3 grid, hipStream_t stream) {
     attn_fwd_kernel<HS><<<grid, dim3(256), lds, stream>>>(p);
     return 0;
 }
-static bool split128_env() {
-    static const bool v = [] {
-        const char* e = getenv("DVQ_ATTN_DKV_SPLIT");
-        return e == nullptr || atoi(e) != 0;
-    }();
-    return v;
-}
 
 template <int HS, bool MASKED>
 int launch_bwd_m(const AttnParams& p, dim3 grid, int64_t rows, hipStream_t stream) {
     using G = Geo<HS>;
-    if (HS > 128 || (p.dbg & 16)) attn_rowdot_kernel<HS><<<dim3((unsigned)cdiv64(rows * p.nh, 256)), dim3(256), 0, stream>>>(p, rows);
+    if (p.dbg & 16) attn_rowdot_kernel<HS><<<dim3((unsigned)cdiv64(rows * p.nh, 256)), dim3(256), 0, stream>>>(p, rows);
     const int lds_kv = 2 * (2 * G::RTILE + 2 * G::CTILE), lds_q = 2 * (2 * G::RTILE + G::CTILE);
     dvq_ensure_dynamic_lds((const void*)attn_bwd_dq_kernel<HS, MASKED>, lds_q);
     attn_bwd_dq_kernel<HS, MASKED><<<grid, dim3(256), lds_q, stream>>>(p);        // first: it also produces dsum for the dK kernel
-    if constexpr (HS > 128) {
-        dvq_ensure_dynamic_lds((const void*)attn_bwd_dkv_kernel<HS, 1, MASKED>, lds_kv);
-        dvq_ensure_dynamic_lds((const void*)attn_bwd_dkv_kernel<HS, 2, MASKED>, lds_kv);
-        attn_bwd_dkv_kernel<HS, 1, MASKED><<<grid, dim3(256), lds_kv, stream>>>(p);
-        attn_bwd_dkv_kernel<HS, 2, MASKED><<<grid, dim3(256), lds_kv, stream>>>(p);
-    } else if (HS == 128 && split128_env()) {
-        // head size 128: dV and dK in two launches of half the accumulators (188 / 256 registers instead of 470: two waves per SIMD hide
-        // the operand loads; the score tile is computed twice).  Stage-2 train step 91.5 -> 90.3 ms; DVQ_ATTN_DKV_SPLIT=0: one launch
-        dvq_ensure_dynamic_lds((const void*)attn_bwd_dkv_kernel<HS, 1, MASKED>, lds_kv);
-        dvq_ensure_dynamic_lds((const void*)attn_bwd_dkv_kernel<HS, 2, MASKED>, lds_kv);
-        attn_bwd_dkv_kernel<HS, 1, MASKED><<<grid, dim3(256), lds_kv, stream>>>(p);
-        attn_bwd_dkv_kernel<HS, 2, MASKED><<<grid, dim3(256), lds_kv, stream>>>(p);
-    } else {
-        dvq_ensure_dynamic_lds((const void*)attn_bwd_dkv_kernel<HS, 0, MASKED>, lds_kv);
-        attn_bwd_dkv_kernel<HS, 0, MASKED><<<grid, dim3(256), lds_kv, stream>>>(p);
-    }
+    dvq_ensure_dynamic_lds((const void*)attn_bwd_dkv_kernel<HS, 0, MASKED>, lds_kv);
+    attn_bwd_dkv_kernel<HS, 0, MASKED><<<grid, dim3(256), lds_kv, stream>>>(p);
     return 0;
 }
 template <int HS>
 int launch_bwd(const AttnParams& p, dim3 grid, int64_t rows, hipStream_t stream) {
-    if constexpr (HS <= 128) {
-        if (p.thr != 0 && p.mask != nullptr) return launch_bwd_m<HS, true>(p, grid, rows, stream);
-    }
+    if (p.thr != 0 && p.mask != nullptr) return launch_bwd_m<HS, true>(p, grid, rows, stream);
     return launch_bwd_m<HS, false>(p, grid, rows, stream);
 }
 
@@ -696,15 +665,7 @@ int fill_params(AttnParams& p, const char* who, int dtype, int64_t B, int64_t T,
     return DVQ_OK;
 }
 
-// head size 128 runs on the round-6 kernels (attention2.hip: LDS-DMA ring, transpose reads instead of channel-major copies);
-// DVQ_ATTN_V2=0 keeps the first generation for A/B runs
-static bool attn_v2_env() {
-    static const bool v = [] {
-        const char* e = getenv("DVQ_ATTN_V2");
-        return e == nullptr || atoi(e) != 0;
-    }();
-    return v;
-}
+// head sizes 128 and 256 run on the round-6 kernels (attention2.hip: LDS-DMA ring, transpose reads instead of channel-major copies)
 Attn2Args v2_args(const AttnParams& p, int64_t B) {
     Attn2Args a{};
     a.q = p.q; a.k = p.k; a.v = p.v; a.o = p.o; a.dout = p.dout;
@@ -752,7 +713,7 @@ int dvq_attn_causal_fwd(const void* q, const void* k, const void* v, int dtype, 
 int dvq_attn_causal_fwd_ld(const void* q, const void* k, const void* v, int64_t ldqkv, int dtype, int64_t B, int64_t T, int n_head,
                            int head_dim, float scale, float p_drop, uint64_t seed, void* out, float* lse, void* drop_mask,
                            dvq_stream_t stream) {
-    DVQ_REQUIRE(head_dim == 128 && attn_v2_env(), DVQ_ESHAPE, "dvq_attn_causal_fwd_ld: a row pitch needs the head-size-128 kernels of attention2.hip");
+    DVQ_REQUIRE(head_dim == 128, DVQ_ESHAPE, "dvq_attn_causal_fwd_ld: a row pitch needs the head-size-128 kernels of attention2.hip");
     DVQ_REQUIRE(ldqkv >= (int64_t)n_head * head_dim && ldqkv % 8 == 0 && (double)T * (double)ldqkv * 2.0 < 4294967296.0, DVQ_ESHAPE,
                 "dvq_attn_causal_fwd_ld: bad pitch");
     return attn_causal_fwd_impl(q, k, v, ldqkv, dtype, B, T, n_head, head_dim, scale, p_drop, seed, out, lse, out /* unused */, drop_mask, stream);
@@ -768,20 +729,17 @@ static int attn_causal_fwd_impl(const void* q, const void* k, const void* v, int
     p.q = (const bf16_t*)q; p.k = (const bf16_t*)k; p.v = (const bf16_t*)v; p.vt = (const bf16_t*)scratch;
     p.out = (bf16_t*)out; p.lse = lse;
     p.mask = (unsigned long long*)drop_mask;
-    if (head_dim == 128 && attn_v2_env()) {
+    if (head_dim == 128) {
         Attn2Args a = v2_args(p, B);
         a.ldq = (int)ldqkv;
         dvq_attn2_fwd(a, (hipStream_t)stream);
         DVQ_CHECK_LAUNCH("attn_causal_fwd");
         return DVQ_OK;
     }
-    DVQ_REQUIRE(ldqkv == p.C, DVQ_ESHAPE, "dvq_attn_causal_fwd: the first-generation kernels take contiguous q, k, v");
-    rc = dvq_transpose(v, dtype, B, T, p.C, scratch, stream);                        // v^T [B][C][T]
+    rc = dvq_transpose(v, dtype, B, T, p.C, scratch, stream);                        // head size 64: v^T [B][C][T]
     if (rc != DVQ_OK) return rc;
     const int nqt = (int)((T + 31) / 32);
-    const dim3 grid((unsigned)((nqt + 3) / 4), (unsigned)(B * n_head));
-    if (head_dim == 64) launch_fwd<64>(p, grid, (hipStream_t)stream);
-    else launch_fwd<128>(p, grid, (hipStream_t)stream);
+    launch_fwd<64>(p, dim3((unsigned)((nqt + 3) / 4), (unsigned)(B * n_head)), (hipStream_t)stream);
     DVQ_CHECK_LAUNCH("attn_causal_fwd");
     return DVQ_OK;
 }
@@ -800,7 +758,7 @@ int dvq_attn_causal_bwd(const void* q, const void* k, const void* v, const void*
 int dvq_attn_causal_bwd_ld(const void* q, const void* k, const void* v, int64_t ldqkv, const void* out, const void* dout, const float* lse,
                            int dtype, int64_t B, int64_t T, int n_head, int head_dim, float scale, float p_drop, uint64_t seed, void* dq,
                            void* dk, void* dv, void* scratch, const void* drop_mask, dvq_stream_t stream) {
-    DVQ_REQUIRE(head_dim == 128 && attn_v2_env(), DVQ_ESHAPE, "dvq_attn_causal_bwd_ld: a row pitch needs the head-size-128 kernels of attention2.hip");
+    DVQ_REQUIRE(head_dim == 128, DVQ_ESHAPE, "dvq_attn_causal_bwd_ld: a row pitch needs the head-size-128 kernels of attention2.hip");
     DVQ_REQUIRE(ldqkv >= (int64_t)n_head * head_dim && ldqkv % 8 == 0 && (double)T * (double)ldqkv * 2.0 < 4294967296.0, DVQ_ESHAPE,
                 "dvq_attn_causal_bwd_ld: bad pitch");
     return attn_causal_bwd_impl(q, k, v, ldqkv, out, dout, lse, dtype, B, T, n_head, head_dim, scale, p_drop, seed, dq, dk, dv, scratch, drop_mask,
@@ -824,27 +782,25 @@ static int attn_causal_bwd_impl(const void* q, const void* k, const void* v, int
     p.dq = (bf16_t*)dq; p.dk = (bf16_t*)dk; p.dv = (bf16_t*)dv;
     p.lse = const_cast<float*>(lse); p.dsum = dsum;
     p.mask = (unsigned long long*)const_cast<void*>(drop_mask);
-    if (head_dim == 128 && attn_v2_env()) {
+    if (head_dim == 128) {
         Attn2Args a = v2_args(p, B);
         a.ldq = (int)ldqkv;
         dvq_attn2_bwd(a, (hipStream_t)stream);
         DVQ_CHECK_LAUNCH("attn_causal_bwd");
         return DVQ_OK;
     }
-    DVQ_REQUIRE(ldqkv == p.C, DVQ_ESHAPE, "dvq_attn_causal_bwd: the first-generation kernels take contiguous q, k, v");
     if ((rc = dvq_transpose(q, dtype, B, T, p.C, qt, stream)) != DVQ_OK) return rc;
     if ((rc = dvq_transpose(k, dtype, B, T, p.C, kt, stream)) != DVQ_OK) return rc;
     if ((rc = dvq_transpose(dout, dtype, B, T, p.C, dot, stream)) != DVQ_OK) return rc;
     const int nt = (int)((T + 31) / 32);
-    const dim3 grid((unsigned)((nt + 3) / 4), (unsigned)(B * n_head));
-    if (head_dim == 64) launch_bwd<64>(p, grid, B * T, (hipStream_t)stream);
-    else launch_bwd<128>(p, grid, B * T, (hipStream_t)stream);
+    launch_bwd<64>(p, dim3((unsigned)((nt + 3) / 4), (unsigned)(B * n_head)), B * T, (hipStream_t)stream);
     DVQ_CHECK_LAUNCH("attn_causal_bwd");
     return DVQ_OK;
 }
 
-/* ---- single-head FULL (non-causal) attention of the DQ-VAE's AttnBlock (modules/diffusionmodules/model.py:168-192): same kernels,
- * one head of size C = 256, every query sees every key, no dropout; scores never reach HBM. ---- */
+/* ---- single-head FULL (non-causal) attention of the DQ-VAE's AttnBlock (modules/diffusionmodules/model.py:168-192): one head of
+ * size C = 256 (fill_params refuses any other), every query sees every key, no dropout; scores never reach HBM.  The scratch sizes
+ * are those of the causal entry points: callers size their buffers by them. ---- */
 int64_t dvq_attn_full_scratch_bytes(int64_t B, int64_t T, int C, int backward) {
     return dvq_attn_causal_scratch_bytes(B, T, 1, C, backward);
 }
@@ -855,17 +811,9 @@ int dvq_attn_full_fwd(const void* q, const void* k, const void* v, int dtype, in
     AttnParams p{};
     int rc = fill_params(p, "dvq_attn_full_fwd", dtype, B, T, 1, C, scale, 0.f, 0, 0);
     if (rc != DVQ_OK) return rc;
-    p.q = (const bf16_t*)q; p.k = (const bf16_t*)k; p.v = (const bf16_t*)v; p.vt = (const bf16_t*)scratch;
+    p.q = (const bf16_t*)q; p.k = (const bf16_t*)k; p.v = (const bf16_t*)v;
     p.out = (bf16_t*)out; p.lse = lse;
-    if (C == 256 && attn_v2_env()) {
-        dvq_attn2_fwd(v2_args(p, B), (hipStream_t)stream);
-        DVQ_CHECK_LAUNCH("attn_full_fwd");
-        return DVQ_OK;
-    }
-    rc = dvq_transpose(v, dtype, B, T, p.C, scratch, stream);                        // v^T [B][C][T]
-    if (rc != DVQ_OK) return rc;
-    const int nqt = (int)(T / 32);
-    launch_fwd<256>(p, dim3((unsigned)((nqt + 3) / 4), (unsigned)B), (hipStream_t)stream);
+    dvq_attn2_fwd(v2_args(p, B), (hipStream_t)stream);
     DVQ_CHECK_LAUNCH("attn_full_fwd");
     return DVQ_OK;
 }
@@ -876,25 +824,11 @@ int dvq_attn_full_bwd(const void* q, const void* k, const void* v, const void* o
     AttnParams p{};
     int rc = fill_params(p, "dvq_attn_full_bwd", dtype, B, T, 1, C, scale, 0.f, 0, 0);
     if (rc != DVQ_OK) return rc;
-    const int64_t elems = B * T * p.C;
-    bf16_t* qt = (bf16_t*)scratch;
-    bf16_t* kt = qt + elems;
-    bf16_t* dot = kt + elems;
-    float* dsum = reinterpret_cast<float*>(dot + elems);
     p.q = (const bf16_t*)q; p.k = (const bf16_t*)k; p.v = (const bf16_t*)v; p.o = (const bf16_t*)out; p.dout = (const bf16_t*)dout;
-    p.qt = qt; p.kt = kt; p.dot = dot;
     p.dq = (bf16_t*)dq; p.dk = (bf16_t*)dk; p.dv = (bf16_t*)dv;
-    p.lse = const_cast<float*>(lse); p.dsum = dsum;
-    if (C == 256 && attn_v2_env()) {
-        dvq_attn2_bwd(v2_args(p, B), (hipStream_t)stream);
-        DVQ_CHECK_LAUNCH("attn_full_bwd");
-        return DVQ_OK;
-    }
-    if ((rc = dvq_transpose(q, dtype, B, T, p.C, qt, stream)) != DVQ_OK) return rc;
-    if ((rc = dvq_transpose(k, dtype, B, T, p.C, kt, stream)) != DVQ_OK) return rc;
-    if ((rc = dvq_transpose(dout, dtype, B, T, p.C, dot, stream)) != DVQ_OK) return rc;
-    const int nt = (int)(T / 32);
-    launch_bwd<256>(p, dim3((unsigned)((nt + 3) / 4), (unsigned)B), B * T, (hipStream_t)stream);
+    p.lse = const_cast<float*>(lse);
+    p.dsum = reinterpret_cast<float*>((bf16_t*)scratch + 3 * B * T * p.C);           // where the causal layout keeps it
+    dvq_attn2_bwd(v2_args(p, B), (hipStream_t)stream);
     DVQ_CHECK_LAUNCH("attn_full_bwd");
     return DVQ_OK;
 }

@@ -2826,13 +2826,9 @@ int launch_nt(NtParams p, int64_t batch, int impl, hipStream_t s) {
     }
     if constexpr (sizeof(T) == 2) {
         // pipelined implicit-GEMM convolution (conv_nt_pipe_kernel): everything with 64-channel K slabs; impl 9 forces it (tests)
-        static const int pipe_env = [] {
-            const char* e = getenv("DVQ_CONV_PIPE");           // 0: off (A/B timing against the 128 x 128 kernel); 1 / 2 / 3: force a tile
-            return e != nullptr ? atoi(e) : -1;
-        }();
         const int khn = p.mode != MODE_GEMM && p.lda > 0 && p.KW > 0 ? (int)(p.Ktot / p.lda / p.KW) : 0;
         const bool s2par = p.mode == MODE_TCONV && p.stride == 2;
-        bool pipe_ok = (impl == 0 || impl == 9) && pipe_env != 0 && p.mode != MODE_GEMM && p.up == 0 && p.lda % 64 == 0 && p.ldb == p.Ktot &&
+        bool pipe_ok = (impl == 0 || impl == 9) && p.mode != MODE_GEMM && p.up == 0 && p.lda % 64 == 0 && p.ldb == p.Ktot &&
                        p.Ncols % 8 == 0 && p.ldc % 8 == 0 && (p.stride == 1 || p.stride == 2) && khn >= 1 && khn * p.KW <= 16 &&
                        (int64_t)khn * p.KW * p.lda == p.Ktot && p.bias_mode != 2 && p.alpha == 1.f &&
                        ((int64_t)p.SH * p.SW * (p.M / ((int64_t)p.DH * p.DW)) + 2 * (4 * (int64_t)p.SW + 4)) * p.lda * 2 < 0x7fe00000ll &&
@@ -2841,10 +2837,9 @@ int launch_nt(NtParams p, int64_t batch, int impl, hipStream_t s) {
         if (p.mode == MODE_FWD && p.stride == 2) pipe_ok = pipe_ok && true;
         DVQ_REQUIRE(!(impl == 9 && !pipe_ok), DVQ_ESHAPE, "igemm_nt: shape not eligible for the pipelined convolution kernel");
         if (pipe_ok) {
-            // tile choice (tools/conv_bench.py sweeps, DVQ_CONV_PIPE=1..4): 256 x 256 when that fills >= 3/4 of a round of 256 CUs,
+            // tile choice (tools/conv_bench.py sweeps): 256 x 256 when that fills >= 3/4 of a round of 256 CUs,
             // else 128 x 128 at two workgroups per CU; thin outputs 512 x 64
-            int cfg = p.Ncols <= 16 ? 4 : p.Ncols <= 64 ? 3 : p.Ncols <= 128 ? 4 : (cdiv64(p.M, 256) * cdiv64(p.Ncols, 256) < 192 ? 4 : 1);
-            if (pipe_env >= 1 && pipe_env <= 4) cfg = pipe_env;
+            const int cfg = p.Ncols <= 16 ? 4 : p.Ncols <= 64 ? 3 : p.Ncols <= 128 ? 4 : (cdiv64(p.M, 256) * cdiv64(p.Ncols, 256) < 192 ? 4 : 1);
             const int tm = cfg == 3 ? 512 : cfg == 4 ? 128 : 256, tn = cfg == 1 ? 256 : cfg == 3 ? 64 : 128;
             if (s2par) {
                 p.par = 1;
@@ -2865,7 +2860,6 @@ int launch_nt(NtParams p, int64_t batch, int impl, hipStream_t s) {
             const bool fwd = p.mode == MODE_FWD;
             if (cfg == 4) fwd ? go(conv_nt_pipe_kernel<2, 2, 2, 2, MODE_FWD>) : go(conv_nt_pipe_kernel<2, 2, 2, 2, MODE_TCONV>);
             else if (cfg == 1) fwd ? go(conv_nt_pipe_kernel<4, 2, 2, 4, MODE_FWD>) : go(conv_nt_pipe_kernel<4, 2, 2, 4, MODE_TCONV>);
-            else if (cfg == 2) fwd ? go(conv_nt_pipe_kernel<4, 2, 2, 2, MODE_FWD>) : go(conv_nt_pipe_kernel<4, 2, 2, 2, MODE_TCONV>);
             else fwd ? go(conv_nt_pipe_kernel<8, 1, 2, 2, MODE_FWD>) : go(conv_nt_pipe_kernel<8, 1, 2, 2, MODE_TCONV>);
             DVQ_CHECK_LAUNCH("conv_nt_pipe");
             return DVQ_OK;
@@ -2989,20 +2983,9 @@ int launch_tn(TnParams p, int64_t batch, int impl, hipStream_t s) {
         p.m_per_split = (int)mps;
         p.nsplit = (int)splits;
         dim3 grid((unsigned)(p.itiles * p.jtiles * tapblk * splits), 1, (unsigned)batch);
-        // the weight gradient of a 1 x 1 / stride 1 / unpadded convolution IS a plain TN product (dy^T x)
-        const bool conv1x1 = p.conv && p.taps == 1 && p.stride == 1 && p.pad_t == 0 && p.pad_l == 0 && p.up == 0 && p.LH == p.DH &&
-                             p.LW == p.DW;
-        // 1 x 1 weight gradients run on the patch kernel too (DVQ_TN_1X1_PATCH=0: the 256-wide plain-GEMM kernel): 65536 x 256 x 256
+        // 1 x 1 weight gradients run on the patch kernel too, not on the 256-wide plain-GEMM kernel: 65536 x 256 x 256
         // 31 against 52 us, 16384 x 512 x 512 30 against 40 us -- a 256 x 256 tile leaves 64 workgroups for the whole chip
-        static const int x11_env = [] {
-            const char* e = getenv("DVQ_TN_1X1_PATCH");
-            return e != nullptr ? atoi(e) : 1;
-        }();
-        static const int pwgs_env = [] {         // workgroups the patch kernel aims at (sweep: 128 / 256 / 512 / 1024, profiles/)
-            const char* e = getenv("DVQ_TN_PATCH_WGS");
-            return e != nullptr ? atoi(e) : 512;
-        }();
-        if (sizeof(T) == 2 && (impl == 0 || impl == 6) && (!p.conv || (conv1x1 && impl == 0 && x11_env == 0)) && p.taps == 1 && p.I >= 256 && p.J >= 256 && p.Mred >= 1024 &&
+        if (sizeof(T) == 2 && (impl == 0 || impl == 6) && !p.conv && p.taps == 1 && p.I >= 256 && p.J >= 256 && p.Mred >= 1024 &&
             p.I % 8 == 0 && p.J % 8 == 0 && (int64_t)p.Mred * p.lda < (1ll << 30) && (int64_t)p.Mred * p.ldb < (1ll << 30) &&
             (p.sA * 2) % 4 == 0 && (p.sB * 2) % 4 == 0) {
             // large plain weight-gradient GEMMs: 256 x 256 tiles, pipelined main loop; ~one resident workgroup per CU
@@ -3012,11 +2995,8 @@ int launch_tn(TnParams p, int64_t batch, int impl, hipStream_t s) {
             // workgroups a wide TN product aims at.  Round 5: 128, not one per CU -- these weight gradients run on the side stream beside
             // the input-gradient GEMMs (layers.Linear.bwd), so half a chip's worth of workgroups is what they get anyway, and half the
             // splits mean half the partials to write and fold: StackGPT p6c18 step 79.9 -> 77.9 ms (64: 81.3 ms; same-box A/B,
-            // profiles/r05_stage2_ab.txt).  DVQ_TN_WIDE_WGS overrides.
-            static const int wide_wgs = [] {
-                const char* e = getenv("DVQ_TN_WIDE_WGS");
-                return e != nullptr && atoi(e) > 0 ? atoi(e) : 128;
-            }();
+            // profiles/r05_stage2_ab.txt).
+            constexpr int wide_wgs = 128;
             int64_t wsplits = wtiles >= wide_wgs ? 1 : wide_wgs / wtiles;
             // >= 16 stages per workgroup: prologue, partial-tile store and fold amortised (8 / 4 / 32 measured slower on the 1 x 1
             // weight gradients: 60 / 95 / 66 against 52 us at 65536 x 256 x 256)
@@ -3025,7 +3005,6 @@ int launch_tn(TnParams p, int64_t batch, int impl, hipStream_t s) {
             const int64_t wmps = cdiv64(cdiv64(p.Mred, wsplits), BK) * BK;
             p.m_per_split = (int)wmps;
             p.nsplit = (int)cdiv64(p.Mred, wmps);
-            p.conv = 0;
             int64_t ws_bytes = 0;
             char* wsp = (char*)dvq_workspace_stream(s, &ws_bytes);
             const int64_t need = (int64_t)p.nsplit * wtiles * 65536 * 4 + (int64_t)p.nsplit * p.itiles * 256 * 4;
@@ -3036,12 +3015,9 @@ int launch_tn(TnParams p, int64_t batch, int impl, hipStream_t s) {
                 p.m_per_split = (int)(cdiv64(p.Mred, BK) * BK);
                 p.nsplit = 1;
             }
-            // the 8-phase main loop (DMA queue never drained) unless DVQ_TN_8PHASE=0 / impl 6 ask for the per-stage-drain kernel (A/B, tests)
-            static const int tn8_env = [] {
-                const char* e = getenv("DVQ_TN_8PHASE");
-                return e != nullptr ? atoi(e) : 1;
-            }();
-            if (tn8_env != 0 && impl == 0 && (p.sA * 2) % 16 == 0 && (p.sB * 2) % 16 == 0) {
+            // the 8-phase main loop (DMA queue never drained) unless impl 6 asks for the per-stage-drain kernel (tests) or a stride is
+            // not a multiple of 16 bytes
+            if (impl == 0 && (p.sA * 2) % 16 == 0 && (p.sB * 2) % 16 == 0) {
                 dvq_note_kernel("gemm_tn_8phase_kernel");
                 dvq_ensure_dynamic_lds((const void*)gemm_tn_8phase_kernel, 8 * 64 * 256);
                 gemm_tn_8phase_kernel<<<dim3((unsigned)(p.itiles * p.jtiles * p.nsplit), 1, (unsigned)batch), dim3(512), 8 * 64 * 256, s>>>(p);
@@ -3058,18 +3034,14 @@ int launch_tn(TnParams p, int64_t batch, int impl, hipStream_t s) {
             }
             return DVQ_OK;
         }
-        static const int patch_env = [] {
-            const char* e = getenv("DVQ_CONV_TN_PATCH");
-            return e != nullptr ? atoi(e) : 1;
-        }();
-        if (sizeof(T) == 2 && p.conv && !p.thin && impl == 0 && patch_env != 0 && batch == 1 && p.I % 8 == 0 && p.J % 8 == 0 &&
+        if (sizeof(T) == 2 && p.conv && !p.thin && impl == 0 && batch == 1 && p.I % 8 == 0 && p.J % 8 == 0 &&
             p.pad_t <= 8 && p.pad_l <= 8 && p.Mred % (p.DH * p.DW) == 0 &&
             (int64_t)(8 * p.stride + p.taps / p.KW + 10) * p.SW * p.ldb * 2 < (1ll << 30) && (int64_t)8 * p.DW * p.lda * 2 < (1ll << 30)) {
             // 8 x 8 output-pixel patches as reduction stages (conv_tn_patch_kernel): split over patch ranges
             const int64_t PH = cdiv64(p.DH, 8), PW = cdiv64(p.DW, 8);
             const int64_t npatch = (p.Mred / ((int64_t)p.DH * p.DW)) * PH * PW;
             const int64_t ptiles = (int64_t)p.itiles * p.jtiles * p.taps;
-            int64_t psplits = pwgs_env / ptiles;
+            int64_t psplits = 512 / ptiles;          // workgroups the patch kernel aims at (sweep: 128 / 256 / 512 / 1024, profiles/)
             if (psplits > npatch / 16) psplits = npatch / 16;       // >= 16 stages per workgroup: the 64-KiB atomic flush amortised
             if (psplits < 1) psplits = 1;
             int64_t pps = cdiv64(npatch, psplits);
@@ -3481,12 +3453,8 @@ int dvq_conv2d_wgrad_oihw_x3(const dvq_conv_desc* d, const void* x, const void* 
     b.Cout = o8;
     // 3 x 3 / stride 1 / pad 1 on the halo kernel: ONE launch over "3 N images" -- image n of plane triple (x_lo, dy_hi), (x_hi, dy_lo),
     // (x_hi, dy_hi) -- instead of three launches with three folds of the partials (the planes of an operand are contiguous: eligible
-    // shapes have plane sizes that are multiples of 256 bytes).  DVQ_WGRAD_X3_ONE=0: three launches
-    static const int one_env = [] {
-        const char* e = getenv("DVQ_WGRAD_X3_ONE");
-        return e == nullptr ? 1 : atoi(e);
-    }();
-    if (one_env && halo_eligible(&b) && xl == xh + xrows * c8 * 2 && yl == yh + yrows * o8 * 2) {
+    // shapes have plane sizes that are multiples of 256 bytes).  Shapes the halo kernel does not take: three launches
+    if (halo_eligible(&b) && xl == xh + xrows * c8 * 2 && yl == yh + yrows * o8 * 2) {
         const int rc = dvq_conv3x3_halo_wgrad_planes_try(xh, yh, grad_oihw, dbias, d->N, d->H, d->W, c8, o8, cin_real, cout_real, ohwi ? 0 : 1,
                                                          d->upsample, (hipStream_t)stream);
         if (rc < 0) return rc;

@@ -109,7 +109,7 @@ __host__ __device__ __forceinline__ float vqt_cos_tau(int64_t D) {
 }
 
 // ---- search, MFMA path: 4 waves x 32 rows per workgroup, x fragments in registers, the codebook planes stream through LDS in
-// 32-code stages (double buffered, register-staged prefetch: the tiling of vq_argmin_mfma_kernel).  Lane (l31, half) of a wave owns
+// 32-code stages (double buffered, register-staged prefetch: the tiling of vq.hip's round-1 kernel).  Lane (l31, half) of a wave owns
 // code c * 32 + l31 of stage c for the 16 accumulator rows (r & 3) + 8 (r >> 2) + 4 half: it keeps a running (best value, index) per
 // row over ITS codes in ascending order (strict >, so the lowest index survives a tie), and the 32 lanes are merged at the end. ----
 template <int KSTEPS, typename XT, bool NOISE, bool COS>

@@ -129,7 +129,7 @@ class CausalSelfAttention(nn.Module):
 
     def _qkv_fusable(self, x2d, hs):
         return (hs == 128 and x2d.dtype == torch.bfloat16 and os.environ.get("DVQ_QKV_FUSED", "1") != "0" and
-                os.environ.get("DVQ_ATTN_V2", "1") != "0" and os.environ.get("DVQ_LINEAR_MULTIPACK", "1") != "0" and
+                os.environ.get("DVQ_LINEAR_MULTIPACK", "1") != "0" and
                 all(l.bias is not None and l.out_p == l.out_features for l in (self.key, self.query, self.value)))
 
     def fwd(self, x2d, b, t, tape, resid=None):

@@ -5,8 +5,8 @@ One bf16, impl 0 case per branch of the conv entry points that notes a family an
 the smallest shape that meets the branch's conditions in csrc/igemm.hip / csrc/conv_halo.hip.  Noted branches WITHOUT a case here:
   * conv3x3_halo2_kernel: exists in the probes build only (-DDVQ_PROBES, DVQ_HALO2=1);
   * gemm_nt_wide_kernel, igemm_nt_kernel: plain GEMMs at K >= 8192 / impl 3 only -- no conv call reaches them with impl 0;
-  * gemm_tn_8phase_kernel, gemm_tn_wide_pipe_kernel: a conv reaches them only with DVQ_TN_1X1_PATCH=0 (gemm_tn calls do by default, under
-    the fixed label "gemm_tn");
+  * gemm_tn_8phase_kernel, gemm_tn_wide_pipe_kernel: no conv call reaches them (gemm_tn calls do by default, under the fixed label
+    "gemm_tn");
   * igemm_tn_kernel: fp32 operands only, and fp32 weight gradients go to the bf16 planes ("conv_wgrad_x3_planes") or need impl 3;
   * the fp32x3 forms of the halo kernels (dvq_conv2d_fwd_x3 / _dgrad_x3 / _wgrad_oihw_x3) keep their fixed labels."""
 import pytest

@@ -424,3 +424,28 @@ def test_last_kernel_is_empty_in_a_fresh_process():
     out = subprocess.run([sys.executable, "-c", "from dynamicvectorquantization_amd import _lib; print(repr(_lib.load().dvq_last_kernel()))"],
                          cwd=REPO, capture_output=True, text=True, timeout=120)
     assert out.returncode == 0 and out.stdout.strip() == "b''", out.stdout + out.stderr
+
+
+# every environment switch the native code reads.  Adding one takes an edit here AND a row in the switch table of
+# docs/design/03-kernels.md: a switch nobody lists is a kernel nobody tests.
+CSRC_GETENV_SWITCHES = {
+    "DVQ_ATTN2_ORDER", "DVQ_HALO_NT", "DVQ_HALO_NT_IN", "DVQ_WGRAD_NT", "DVQ_HALO_MFMA_STATS",       # read by kernels through a params field
+    "DVQ_DECODE_MODE", "DVQ_DECODE_ATTN_SPLIT", "DVQ_DECODE_WAVE_ATTN", "DVQ_DECODE_TRACE",          # sampler: tests and tools name them
+    "DVQ_DETERMINISTIC", "DVQ_FP32_SPLIT",                                                           # API defaults
+    "DVQ_CMDLIST_LAUNCH", "DVQ_CMDLIST_DEBUG", "DVQ_LN_BWD_WAVES",
+    "DVQ_HALO2", "DVQ_HALO2_DBG", "DVQ_HALO_DBG",                                                    # conv_halo2.hip: probe library only
+}
+CSRC_PROBE_SWITCHES = {"DVQ_ATTN_DBG", "DVQ_ATTN2_DBG", "DVQ_HALO_DBG", "DVQ_HALO_LDS_PAD", "DVQ_VQ_DBG", "DVQ_WGRAD_DBG", "DVQ_X3_DBG"}
+
+
+def test_csrc_environment_switches_are_listed_and_documented():
+    csrc = os.path.join(REPO, "dynamicvectorquantization_amd", "csrc")
+    text = "".join(open(os.path.join(csrc, f)).read() for f in sorted(os.listdir(csrc)) if f.endswith((".hip", ".h")))
+    assert set(re.findall(r'\bgetenv\("(DVQ_[A-Z0-9_]+)"\)', text)) == CSRC_GETENV_SWITCHES
+    assert set(re.findall(r'\bdvq_probe_env\("(DVQ_[A-Z0-9_]+)"\)', text)) == CSRC_PROBE_SWITCHES
+    # no other spelling reads the environment: the one getenv without a literal name is dvq_probe_env's own
+    assert len(re.findall(r"\bgetenv\(", text)) == len(re.findall(r'\bgetenv\("DVQ_', text)) + 1
+    doc = open(os.path.join(REPO, "docs", "design", "03-kernels.md")).read()
+    table = doc[doc.index("| variable | effect |"):doc.index("**Retired switches.**")]
+    for name in sorted(CSRC_GETENV_SWITCHES | CSRC_PROBE_SWITCHES):
+        assert re.search(r"\b%s\b" % name, table), f"{name} is read in csrc/ but has no row in the switch table of docs/design/03-kernels.md"

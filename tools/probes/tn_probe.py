@@ -1,5 +1,5 @@
-"""TN GEMM (weight-gradient shapes of the StackGPT Linear layers): the automatic route (8-phase main loop; DVQ_TN_8PHASE=0 = the
-per-stage-drain kernel) against torch.matmul (hipBLASLt) as a yardstick only; full-tensor check against an fp32 product, column sums."""
+"""TN GEMM (weight-gradient shapes of the StackGPT Linear layers): the automatic route (8-phase main loop) against
+torch.matmul (hipBLASLt) as a yardstick only; full-tensor check against an fp32 product, column sums."""
 import os, sys
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.dirname(os.path.abspath(__file__)))))
 import torch
@@ -14,7 +14,6 @@ def timeit(fn, reps=10):
     for _ in range(reps): fn()
     e.record(); torch.cuda.synchronize()
     return s.elapsed_time(e) / reps
-print("DVQ_TN_8PHASE =", os.environ.get("DVQ_TN_8PHASE", "1 (default)"))
 for (mred, i, j) in [(20576, 1024, 1024), (20576, 3072, 1024), (20576, 4096, 1024), (20576, 1024, 4096), (65536, 256, 256), (16384, 512, 512), (5000, 264, 520)]:
     torch.manual_seed(mred + i)
     a2 = (torch.rand(mred, i, device=dev)*2-1).to(torch.bfloat16)
