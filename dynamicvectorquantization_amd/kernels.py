@@ -9,11 +9,10 @@ from __future__ import annotations
 
 import ctypes as C
 
-import os
-
 import torch
 
 from . import _lib
+from . import runtime as rt
 from ._lib import ConvDesc, check
 
 _DT = {torch.float32: _lib.F32, torch.bfloat16: _lib.BF16}
@@ -124,12 +123,16 @@ def profile_stop():
     return out
 
 
-_shape_tags = os.environ.get("DVQ_PROFILE_SHAPES", "0") == "1"    # debug: split the families by call geometry
 _cur_tag = [None]
 
 
+def _shape_tags() -> bool:
+    """debug: split the families by call geometry"""
+    return rt.switch("DVQ_PROFILE_SHAPES") == "1"
+
+
 def _tag(d, mode):
-    if _shape_tags:
+    if _shape_tags():
         _cur_tag[0] = f"{mode} N{d.N} {d.H}x{d.W} {d.Cin}->{d.Cout} k{d.KH}s{d.stride}{'u' if d.upsample else ''}"
 
 
@@ -138,7 +141,7 @@ def _timed(name, flops, nbytes, fn, entry=None):
     (dvq_last_kernel), or by `entry`, the entry point's name, when it noted none -- a branch without a note shows up in the table"""
     global _count
     tag = None
-    if _shape_tags and _cur_tag[0] is not None:
+    if _cur_tag[0] is not None:
         tag, _cur_tag[0] = _cur_tag[0], None
     if _count is not None:
         _count += 1
@@ -407,18 +410,14 @@ def gn_scale_shift(x, gamma, beta, groups=32, eps=1e-6, stats=None):
     return ss, mr
 
 
-_GN_PARTIALS = os.environ.get("DVQ_GN_PARTIALS", "1") != "0"
-
-
 def gn_backward(x, dy, mean_rstd, gamma, beta, dgamma, dbeta, groups=32, silu=True, addend=None, fixed_stats=False):
     """dgamma/dbeta (fp32 [C]) are accumulated into; returns dx.  fixed_stats: mean / rstd are constants, not functions of x (ActNorm:
     a per-channel affine): the statistic terms of dx are dropped by zeroing the reduced sums, dx = rstd * gamma * dz"""
     n, c = x.shape[0], x.shape[-1]
     hw = x.numel() // (n * c)
     red = zeros_small((n, groups, 2), torch.float64, x.device)
-    part = None
-    if _GN_PARTIALS:      # per-block partials + fold kernel instead of thousands of atomics per address
-        part = torch.empty(lib().dvq_gn_bwd_partial_bytes(n, hw, c), dtype=torch.uint8, device=x.device)
+    # per-block partials + fold kernel instead of thousands of atomics per address
+    part = torch.empty(lib().dvq_gn_bwd_partial_bytes(n, hw, c), dtype=torch.uint8, device=x.device)
     check(lib().dvq_gn_bwd_reduce(_p(x), _p(dy), dt(x), n, hw, c, groups, _p(mean_rstd), _p(gamma), _p(beta), int(silu),
                                   _p(red), _p(dgamma), _p(dbeta), _p(part), _s()), "dvq_gn_bwd_reduce")
     if fixed_stats:
@@ -468,7 +467,7 @@ ACT_NONE, ACT_SWISH, ACT_LRELU, ACT_RELU = 0, 1, 2, 3      # include/dvq_hip.h D
 def _x3_halo(d: ConvDesc, t, dgrad: bool) -> bool:
     """fp32x3 forward / input gradient of this call on the halo kernel (bf16 planes on the channel axis, fp32 output)?
     DVQ_X3_HALO=0: stay on the fp32 kernel that splits at every fragment read (A/B switch)"""
-    return (t.dtype == torch.float32 and d.KH == 3 and d.stride == 1 and os.environ.get("DVQ_X3_HALO", "1") != "0" and
+    return (t.dtype == torch.float32 and d.KH == 3 and d.stride == 1 and rt.switch("DVQ_X3_HALO") != "0" and
             bool(lib().dvq_fp32_split()) and bool(lib().dvq_conv3x3_x3_ok(C.byref(d), int(dgrad))))
 
 
@@ -483,7 +482,7 @@ def conv2d_fwd(d: ConvDesc, x, w, bias, residual=None, gn_ss=None, out_stats=Non
             lib().dvq_conv2d_fwd_x3(C.byref(d), _p(x), _p(w), _p(bias), _p(residual), _p(y), act, _p(scratch), need, _s()),
             "dvq_conv2d_fwd_x3"))
         return y
-    if _shape_tags:       # per-shape tables split the forward by epilogue / prologue variant (tools/debug/step_shapes.py)
+    if _shape_tags():     # per-shape tables split the forward by epilogue / prologue variant (tools/debug/step_shapes.py)
         _tag(d, "fwd" + ("+res" if residual is not None else "") + ("+gn" if gn_ss is not None else "") +
              ("+st" if out_stats is not None else "") + ("+act" if act != ACT_NONE else ""))
     if out_stats is not None:
@@ -581,7 +580,7 @@ class CmdList:
 def ensure_workspace(device):
     """register the process-wide scratch buffer of libdvq_hip (kept alive here)"""
     device = torch.device(device)
-    if _workspace.get("dev") != device and os.environ.get("DVQ_NO_WORKSPACE", "0") != "1":
+    if _workspace.get("dev") != device:
         buf = torch.empty(WORKSPACE_BYTES, dtype=torch.uint8, device=device)
         check(lib().dvq_set_workspace(buf.data_ptr(), buf.numel()), "dvq_set_workspace")
         _workspace.update(dev=device, buf=buf)
@@ -589,7 +588,7 @@ def ensure_workspace(device):
 
 def _wgrad_x3_planes() -> bool:
     """DVQ_X3_WGRAD_PLANES=0: fp32x3 weight gradients stay on the fp32 kernel that splits at every fragment read (A/B switch)"""
-    return os.environ.get("DVQ_X3_WGRAD_PLANES", "1") != "0"
+    return rt.switch("DVQ_X3_WGRAD_PLANES") != "0"
 
 
 def split_bf16_planes(x2d, cout=None):
@@ -1055,7 +1054,7 @@ def dropout(x, p, seed):
 def attn_causal_ok(x, n_head, b, t):
     """do the fused attention kernels take this call (dvq_attn_causal_ok: the check the entry points make themselves)?"""
     c = x.shape[-1]
-    return (x.dtype in _DT and c % n_head == 0 and os.environ.get("DVQ_NO_FUSED_ATTN", "0") != "1" and
+    return (x.dtype in _DT and c % n_head == 0 and rt.switch("DVQ_NO_FUSED_ATTN") != "1" and
             bool(lib().dvq_attn_causal_ok(dt(x), b, t, n_head, c // n_head)))
 
 
@@ -1131,7 +1130,7 @@ def attn_causal_bwd_fused(qkv, cols, out, dout, lse, b, t, n_head, scale, p_drop
 
 def attn_full_ok(q, t):
     """does the fused single-head full attention (AttnBlock) take this call (dvq_attn_full_ok)?"""
-    return (q.dtype in _DT and os.environ.get("DVQ_NO_FUSED_ATTNBLOCK", "0") != "1" and
+    return (q.dtype in _DT and rt.switch("DVQ_NO_FUSED_ATTNBLOCK") != "1" and
             bool(lib().dvq_attn_full_ok(dt(q), q.shape[0] // max(1, t), t, q.shape[-1])))
 
 

@@ -14,7 +14,6 @@ tape; there is no per-op autograd graph and no ATen math on the path).
 from __future__ import annotations
 
 import math
-import os
 
 import torch
 import torch.nn as nn
@@ -183,7 +182,7 @@ class Linear(nn.Module):
     def _w(self, dtype):
         """compute-dtype copy of the weight (+ zero-padded rows / bias), cached until the parameters change"""
         ep = (rt.param_epoch(self.weight), self.weight.data_ptr(), self.weight._version)
-        if dtype == torch.bfloat16 and self.weight.is_cuda and _LINEAR_MULTIPACK:
+        if dtype == torch.bfloat16 and self.weight.is_cuda:
             # persistent bf16 copies (w and the transposed wt) refreshed for ALL Linear layers of this optimizer group by one launch
             ent = getattr(self, "_lpack", None)
             if ent is None or ent["w"].device != self.weight.device:
@@ -248,12 +247,11 @@ class Linear(nn.Module):
             tape.s.update(x=x2d, w=w)
         return y.view(m, self.out_p)
 
-    def bwd(self, dy, tape, need_dx=True, addend=None):
-        """addend [M, in]: an input gradient this layer's is added to (in the GEMM's epilogue: one rounding, no add kernel)"""
+    def bwd(self, dy, tape, need_dx=True):
         x2d, w = tape.s["x"], tape.s["w"]
         m = x2d.shape[0]
         # dW[o][i] += sum_m dy[m][o] x[m][i]  straight into the fp32 gradient; db = column sums of dy
-        fused_db = self.bias is not None and self.out_p == self.out_features and os.environ.get("DVQ_LINEAR_DB", "fused") == "fused"
+        fused_db = self.bias is not None and self.out_p == self.out_features
         # bias gradient = column sums of dy: taken from the weight-gradient kernel's pass over dy (a separate 17-us reduction per layer
         # otherwise: 2.5 ms of a stage-2 train step)
         def wgrad():
@@ -269,17 +267,17 @@ class Linear(nn.Module):
 
         # the weight gradient has no consumer before the optimizer step / gradient exchange: on the side stream (runtime.side_wgrad)
         # its workgroups fill the partially occupied last round of the input-gradient GEMM that runs beside it (20576-row operands
-        # give 324 / 432 tiles for 256 CUs) and its HBM-bound partial fold overlaps MFMA-bound kernels.  DVQ_LINEAR_SIDE=0: main stream
-        if need_dx and m >= 1024 and rt.side_wgrad_enabled() and os.environ.get("DVQ_LINEAR_SIDE", "1") != "0":
+        # give 324 / 432 tiles for 256 CUs) and its HBM-bound partial fold overlaps MFMA-bound kernels
+        if need_dx and m >= 1024 and rt.side_wgrad_enabled():
             wt = self._wt(w)                                                 # made on the main stream, before the fork
-            dx = K.gemm_nt(dy, wt, m, self.in_features, self.out_p, self.out_p, self._wt_ld(w), self.in_features, residual=addend)
+            dx = K.gemm_nt(dy, wt, m, self.in_features, self.out_p, self.out_p, self._wt_ld(w), self.in_features)
             rt.run_on_side(wgrad, dy, x2d)      # after the input gradient (forking before it measured the same: 82.3 vs 82.0 ms)
             return dx.view(m, self.in_features)
         wgrad()
         if not need_dx:
             return None
         wt = self._wt(w)                                                     # [in, out_p]
-        dx = K.gemm_nt(dy, wt, m, self.in_features, self.out_p, self.out_p, self._wt_ld(w), self.in_features, residual=addend)
+        dx = K.gemm_nt(dy, wt, m, self.in_features, self.out_p, self.out_p, self._wt_ld(w), self.in_features)
         return dx.view(m, self.in_features)
 
 
@@ -356,7 +354,6 @@ class _LinearPackRegistry:
 
 
 LINEAR_PACKS = _LinearPackRegistry()
-_LINEAR_MULTIPACK = os.environ.get("DVQ_LINEAR_MULTIPACK", "1") != "0"
 
 
 class BatchNorm2d(HipModule):
@@ -476,9 +473,6 @@ class ActNorm(HipModule):
         return dx.view(s["shape"])
 
 
-_SIDE_AFTER_DGRAD = os.environ.get("DVQ_SIDE_AFTER_DGRAD", "1") != "0"
-
-
 class Conv2d(HipModule):
     """torch.nn.Conv2d-compatible parameters ([Cout,Cin,KH,KW] + bias, same default init) driving the
     implicit-GEMM kernels.  `asym_pad` reproduces Downsample's F.pad(0,1,0,1); `upsample` reads the
@@ -589,7 +583,7 @@ class Conv2d(HipModule):
         x, d = tape.s["x"], tape.s["d"]
         side = need_dw and need_dx and rt.side_wgrad_enabled()
         dx = None
-        if need_dx and side and _SIDE_AFTER_DGRAD:
+        if side:
             # the input gradient FIRST: the side stream then waits for it, so the weight gradient (matrix pipes) runs beside what
             # follows the input gradient on this stream -- the HBM-bound GroupNorm backward -- instead of beside the input
             # gradient itself, which wants the same matrix pipes
@@ -745,7 +739,7 @@ def norm_swish_conv(norm, conv, x, tape, nname, cname, residual=None):
     # with a backward to come the weight-gradient kernel would have to re-apply the transform (measured: as expensive as the
     # gn_apply pass it saves), so the prologue fusion is used for tape-less forwards only: inference, and the discriminator
     # step's second autoencoder forward (DVQ_FUSE_GN=1 forces it everywhere)
-    if (rt.fuse_gn_prologue() or (tape is None and rt.fuse_gn_inference())) and conv.fused_ok(x):
+    if (rt.fuse_gn_prologue() or tape is None) and conv.fused_ok(x):
         ss = norm.prep(x, _child(tape, nname))
         return conv.fwd(x, _child(tape, cname), residual=residual, gn_ss=ss, want_stats=True)
     a = norm.fwd(x, _child(tape, nname), silu=True)
@@ -848,14 +842,6 @@ class AttnBlock(HipModule):
         q, k, v, p = st["q"], st["k"], st["v"], st["p"]
         impl = rt.impl()
         do = self.proj_out.bwd(dy, tape.child("proj"))
-        if p is None and os.environ.get("DVQ_ATTNBLOCK_BWD", "flash") == "gemm":
-            # DVQ_ATTNBLOCK_BWD=gemm: fused forward, backward on the pipelined batched GEMM kernels -- the probabilities are recomputed
-            # (q k^T, row softmax) into scratch that lives only inside this call.  This was the default while the flash-style backward at
-            # head size 256 ran at 175 TFLOP/s (first-generation kernels, 0.98 ms per call at B 64, T 1024, against 0.68 ms here); the
-            # round-6 kernels (csrc/attention2.hip) take 0.45 ms, so the fused backward below is the default again.
-            s = K.gemm_nt(q, k, n, n, c, c, c, n, batch=b, sa=n * c, sb=n * c, sc=n * n, impl=impl)
-            p = K.softmax_rows(s, b * n, n, float(int(c) ** (-0.5)))
-            del s
         if p is None:                                   # fused forward: fused backward (dQ, then dV and dK kernels)
             dq, dk, dv = K.attn_full_bwd(q.view(b * n, c), k.view(b * n, c), v.view(b * n, c), st["o"], do.view(b * n, c), st["lse"],
                                          b, n, float(int(c) ** (-0.5)))

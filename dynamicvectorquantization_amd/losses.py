@@ -208,10 +208,6 @@ class vgg16(nn.Module):
         return [[getattr(self, name)[j] for j in range(len(idxs))] for name, idxs, _ in self.SLICES]
 
 
-_GEN_SIDE = os.environ.get("DVQ_GEN_SIDE", "1") != "0"
-_LOSS_PREFETCH = os.environ.get("DVQ_LOSS_PREFETCH", "1") != "0"
-
-
 class LPIPS(nn.Module):
     """Learned perceptual metric (modules/losses/lpips.py:11-50) on the HIP kernels.
 
@@ -220,14 +216,13 @@ class LPIPS(nn.Module):
     w.r.t. the reconstruction's features; the backward walks the reconstruction half only (dgrad kernels gated by the
     ReLU masks, max-pool routing fused with the tap gradient).  VGG16 and the lin layers are frozen, as in the reference.
     NetLinLayer dropout: the reference leaves nn.Dropout(0.5) on the squared differences active in training (Lightning's
-    model.train() reaches the loss module; lpips.py:64-70).  `lin_dropout=True` (or DVQ_LPIPS_DROPOUT=1) applies it here -- in
+    model.train() reaches the loss module; lpips.py:64-70).  `lin_dropout=True` applies it here -- in
     training mode only, hash-seeded per call inside the head kernel, so the training distribution matches the reference's; the
     draws are device-RNG dependent (parity unpinned), the default (off) computes the expectation of that value."""
 
-    def __init__(self, use_dropout=True, lin_dropout=None):
+    def __init__(self, use_dropout=True, lin_dropout=False):
         super().__init__()
-        import os
-        self.lin_dropout = bool(use_dropout) and (os.environ.get("DVQ_LPIPS_DROPOUT", "0") == "1" if lin_dropout is None else bool(lin_dropout))
+        self.lin_dropout = bool(use_dropout) and bool(lin_dropout)
         self.scaling_layer = ScalingLayer()
         self.chns = [64, 128, 256, 512, 512]
         self.net = vgg16(pretrained=True, requires_grad=False)
@@ -451,7 +446,7 @@ class VQLPIPSWithDiscriminator(nn.Module):
         (models call this at the top of training_step), so that it runs beside the autoencoder's HBM-bound passes instead of after
         them.  forward() picks the results up if it is then called with the same tensor; DVQ_LOSS_PREFETCH=0 switches it off."""
         self._pre = None
-        if not (_LOSS_PREFETCH and rt.side_wgrad_enabled() and torch.is_grad_enabled() and self.training and inputs.is_cuda):
+        if not (rt.switch("DVQ_LOSS_PREFETCH") != "0" and rt.side_wgrad_enabled() and torch.is_grad_enabled() and self.training and inputs.is_cuda):
             return
         x = inputs.contiguous().float()
         cd = rt.compute_dtype()
@@ -497,7 +492,7 @@ class VQLPIPSWithDiscriminator(nn.Module):
         # backward) only share r_p: with both wanted, the GAN branch runs on the side stream so that its HBM-bound BatchNorm /
         # activation passes and the perceptual branch's pooling passes overlap the other branch's convolutions (DVQ_GEN_SIDE=0: off)
         gan_side = None
-        if want_grad and disc_factor != 0 and self.perceptual_weight > 0 and _GEN_SIDE and rt.side_wgrad_enabled():
+        if want_grad and disc_factor != 0 and self.perceptual_weight > 0 and rt.switch("DVQ_GEN_SIDE") != "0" and rt.side_wgrad_enabled():
             gan_side = {}
 
             def gan_branch():

@@ -12,8 +12,6 @@ padding row, requires_grad False under EMA) and return signatures.  Differences 
 """
 from __future__ import annotations
 
-import os
-
 import numpy as np
 import torch
 import torch.distributed as dist
@@ -22,8 +20,6 @@ import torch.nn as nn
 from . import kernels as K
 from . import runtime as rt
 from .layers import Tape, to_nchw, to_nhwc
-
-_FORCE_DP = os.environ.get("DVQ_FORCE_DP", "0") == "1"     # exchange even in a one-rank group (single-GPU test of the DP path)
 
 
 class VQEmbedding(nn.Embedding):
@@ -143,7 +139,7 @@ class VQEmbedding(nn.Embedding):
 
     @staticmethod
     def _dp_active():
-        return dist.is_available() and dist.is_initialized() and (dist.get_world_size() > 1 or _FORCE_DP)
+        return dist.is_available() and dist.is_initialized() and (dist.get_world_size() > 1 or rt.force_dp())
 
     @staticmethod
     def _exchange(buf):
@@ -154,7 +150,7 @@ class VQEmbedding(nn.Embedding):
         on the host before the collective is sized -- a device-to-host sync in the middle of every training forward, which a
         recorded step cannot have; the whole [K, D] block is 1 MB at K = 1024.)  Device-agnostic (tested on CPU tensors over gloo)."""
         def exchange():          # eager even inside a captured training step (runtime.graph_break)
-            if os.environ.get("DVQ_DP_NOOP_COLLECTIVES", "0") == "1":
+            if rt.switch("DVQ_DP_NOOP_COLLECTIVES") == "1":
                 return
             dist.all_reduce(buf, op=dist.ReduceOp.SUM)
         rt.graph_break(exchange)

@@ -15,6 +15,45 @@ _weights_epoch = 0
 _impl = 0
 
 
+# Every environment variable the Python package honours as a switch: name -> (default, what the non-default selects).  All of them
+# are read through switch(), at call time.  (Paths and build inputs are not switches: DVQ_IMAGENET_ROOT, DVQ_VGG16_WEIGHTS,
+# DVQ_LPIPS_LIN_WEIGHTS, DVQ_USE_PROBES_LIB, DVQ_BUILD_EXTRA_FLAGS.)  A new row takes a row in the switch table of
+# docs/design/03-kernels.md too; tests/test_host_cpu.py pins both.
+SWITCHES = {
+    "DVQ_FUSE_GN": ("0", "1: GroupNorm+swish inside the consuming 3x3 conv on taped forwards too"),
+    "DVQ_X3_HALO": ("1", "0: fp32x3 3x3 forward / input gradient on the fp32 kernel that splits at every fragment read"),
+    "DVQ_X3_WGRAD_PLANES": ("1", "0: fp32x3 weight gradients on the fp32 kernel that splits at every fragment read"),
+    "DVQ_NO_FUSED_ATTN": ("0", "1: causal attention as per-head GEMMs + softmax instead of the fused kernels"),
+    "DVQ_NO_FUSED_ATTNBLOCK": ("0", "1: AttnBlock on GEMMs + softmax (stores the [B,N,N] probabilities)"),
+    "DVQ_QKV_FUSED": ("1", "0: key / query / value as three Linear layers instead of one GEMM"),
+    "DVQ_FUSE_DROP_BWD": ("1", "0: stand-alone dropout passes in the StackGPT backward"),
+    "DVQ_GEN_SIDE": ("1", "0: generator loss with the PatchGAN branch on the main stream"),
+    "DVQ_LOSS_PREFETCH": ("1", "0: target-only loss work inside the loss call instead of beside the autoencoder's forward"),
+    "DVQ_SIDE_WGRAD": ("1", "0: weight gradients on the main stream"),
+    "DVQ_STEP_GRAPH": ("1", "0: every training step eager, nothing recorded"),
+    "DVQ_DECODE_GRAPH": ("1", "0: single-row sampler steps eager, nothing recorded"),
+    "DVQ_DECODE_STACK": ("1", "0: a sampler token step as per-kernel launches instead of the persistent kernel"),
+    "DVQ_DECODE_WGS": ("0", "n: workgroups of the persistent token-step kernel (0: the library chooses)"),
+    "DVQ_PROFILE_SHAPES": ("0", "1: the profiler splits the conv families by call geometry"),
+    "DVQ_GRAPH_DEBUG": ("0", "1: print the library calls of every recorded segment, synchronise after every replayed item"),
+    "DVQ_GRAPH_BREAK_EVERY": ("0", "n: with DVQ_GRAPH_DEBUG=1, cut a recorded segment every n library calls"),
+    "DVQ_FORCE_DP": ("0", "1: the data-parallel path in a one-rank group"),
+    "DVQ_DP_CHECK_EVERY": ("0", "k: assert that the replicas are equal every k steps"),
+    "DVQ_DP_NO_HOOK": ("0", "1: no all-reduce launch from inside the backward"),
+    "DVQ_DP_NOOP_COLLECTIVES": ("0", "1: exchange points without the RCCL calls"),
+}
+
+
+def switch(name: str) -> str:
+    """value of a registered switch, read from the environment NOW (KeyError for a name that is not in SWITCHES)"""
+    return os.environ.get(name, SWITCHES[name][0])
+
+
+def force_dp() -> bool:
+    """exchange even in a one-rank group (single-GPU tests of the data-parallel path)"""
+    return switch("DVQ_FORCE_DP") == "1"
+
+
 def compute_dtype() -> torch.dtype:
     return _compute_dtype
 
@@ -114,19 +153,11 @@ def bump_codebook_epoch():
 # ~1/3 of the saved-activation memory) -- measured SLOWER than the separate HBM-bound pass at B=64 (the in-LDS
 # transform steals VALU issue slots from MFMA-feeding waves), so it is off by default; the statistics epilogue of
 # the producing conv is always on.  DVQ_FUSE_GN=1 enables it (e.g. when memory-bound on activations).
-_fuse_gn = os.environ.get("DVQ_FUSE_GN", "0") == "1"
+_fuse_gn = None          # None: the environment decides; True / False: set_fuse_gn_prologue() was called
 
 
 def fuse_gn_prologue() -> bool:
-    return _fuse_gn
-
-
-_fuse_gn_inference = os.environ.get("DVQ_FUSE_GN_INFERENCE", "1") == "1"
-
-
-def fuse_gn_inference() -> bool:
-    """GroupNorm+swish applied inside the consuming 3x3 conv on forwards that record no tape"""
-    return _fuse_gn_inference
+    return switch("DVQ_FUSE_GN") == "1" if _fuse_gn is None else _fuse_gn
 
 
 def set_fuse_gn_prologue(v: bool):
@@ -162,9 +193,10 @@ def impl_ctx(v: int):
 # the remembered callables run in recorded order.  Outside a capture `graph_break(fn)` is just `fn()`.
 # ---------------------------------------------------------------------------------------------------------------
 _capture = None
-_GRAPH_DEBUG = os.environ.get("DVQ_GRAPH_DEBUG", "0") == "1"
-_BREAK_EVERY = int(os.environ.get("DVQ_GRAPH_BREAK_EVERY", "0"))
-_SEPARATE_POOLS = os.environ.get("DVQ_GRAPH_SEPARATE_POOLS", "0") == "1"     # experiment: one private pool per segment
+
+
+def _graph_debug() -> bool:
+    return switch("DVQ_GRAPH_DEBUG") == "1"
 
 
 def capturing() -> bool:
@@ -190,8 +222,8 @@ def next_dropout_seed() -> int:
 
 def step_replay_mode() -> str:
     """how a recorded segment is replayed: "list" = csrc/cmdlist.hip re-issues the captured launches on the current + side stream
-    (default: the device sees an eager step's queues); "graph" = hipGraphLaunch of the instantiated capture (DVQ_STEP_REPLAY)"""
-    return os.environ.get("DVQ_STEP_REPLAY", "list")
+    (the device sees an eager step's queues).  A segment the list cannot re-issue falls back to hipGraphLaunch on its own."""
+    return "list"
 
 
 class StepGraph:
@@ -210,42 +242,38 @@ class StepGraph:
         self._mode = "thread_local"
 
     def _dbg(self, *a):
-        if _GRAPH_DEBUG:
+        if _graph_debug():
             print("[stepgraph]", *a, flush=True)
 
     def _on_launch(self, what):
         """debugging: library calls of the current segment; DVQ_GRAPH_BREAK_EVERY=N cuts a segment every N calls so that a
         faulting replay can be narrowed down to a handful of launches"""
         self._names.append(what)
-        if _BREAK_EVERY and len(self._names) >= _BREAK_EVERY and not self._in_brk:
+        every = int(switch("DVQ_GRAPH_BREAK_EVERY"))
+        if every and len(self._names) >= every and not self._in_brk:
             self.brk(lambda: None)
 
     def _begin(self):
         self._dbg("begin segment", len(self.items))
         self._names = []
-        # launch-list replay (default) reads the captured nodes itself and never instantiates an executable graph
-        g = torch.cuda.CUDAGraph(keep_graph=True) if step_replay_mode() == "list" else torch.cuda.CUDAGraph()
-        if _SEPARATE_POOLS:
-            self.pool = torch.cuda.graph_pool_handle()
+        # launch-list replay reads the captured nodes itself and never instantiates an executable graph
+        g = torch.cuda.CUDAGraph(keep_graph=True)
         g.capture_begin(pool=self.pool, capture_error_mode=self._mode)
         self._g = g
         self._tick.add_(1)
 
     def _end(self):
         self._g.capture_end()
-        if _GRAPH_DEBUG:
+        if _graph_debug():
             self._dbg("segment", len(self.items), "calls:", " ".join(getattr(self, "_names", [])))
-        if step_replay_mode() == "list":
-            from . import kernels as K
-            from ._lib import DvqError
-            try:
-                self.items.append(("list", K.CmdList(self._g)))
-            except DvqError as e:
-                # a segment with nodes the list cannot re-issue (a torch memcpy): this segment replays through hipGraphLaunch
-                import warnings
-                warnings.warn(f"StepGraph: segment {len(self.items)} replays as a hipGraph ({e})")
-                self.items.append(("graph", self._g))
-        else:
+        from . import kernels as K
+        from ._lib import DvqError
+        try:
+            self.items.append(("list", K.CmdList(self._g)))
+        except DvqError as e:
+            # a segment with nodes the list cannot re-issue (a torch memcpy): this segment replays through hipGraphLaunch
+            import warnings
+            warnings.warn(f"StepGraph: segment {len(self.items)} replays as a hipGraph ({e})")
             self.items.append(("graph", self._g))
         self._g = None
 
@@ -266,7 +294,7 @@ class StepGraph:
         with torch.cuda.stream(self.aux):
             out = fn()
         self.stream.wait_stream(self.aux)
-        if _GRAPH_DEBUG:
+        if _graph_debug():
             torch.cuda.synchronize(self.device)
             self._dbg("eager item done")
         self.items.append(("eager", fn))
@@ -284,7 +312,7 @@ class StepGraph:
         torch.cuda.empty_cache()
         self.stream.wait_stream(torch.cuda.current_stream(self.device))
         from . import _lib
-        if _GRAPH_DEBUG:
+        if _graph_debug():
             _lib._launch_hook = self._on_launch
         self._in_brk, self._names = False, []
         with torch.cuda.stream(self.stream):
@@ -316,7 +344,7 @@ class StepGraph:
                 it.replay(torch.cuda.current_stream(self.device), side_stream(self.device)["stream"])
             else:
                 it()
-            if _GRAPH_DEBUG:                     # localise a faulting segment: finish every item before the next one
+            if _graph_debug():                     # localise a faulting segment: finish every item before the next one
                 torch.cuda.synchronize(self.device)
                 self._dbg("replayed item", i, kind)
 
@@ -357,17 +385,13 @@ def side_wgrad_enabled():
 class side_wgrad:
     """context: inside, layers.Conv2d.bwd issues its weight gradient on the side stream; on exit the current stream has waited
     for it.  Only callers that read gradients through join_side() points may switch this on (trainer.Trainer does; code that
-    calls bwd() and then reads .grad directly keeps the single-stream behaviour).  DVQ_SIDE_WGRAD=0 disables it."""
+    calls bwd() and then reads .grad directly keeps the single-stream behaviour).  DVQ_SIDE_WGRAD=0 disables it; read on every entry."""
 
     def __enter__(self):
         global _side_on
         self.prev = _side_on
-        # eagerly launched steps only: a hipGraph replay of the two-stream capture ran no faster than the single-stream one on
-        # ROCm 7.2 (179.9 vs 179.1 ms, with 39 ms of host time per launch; DEBUG_HIP_FORCE_GRAPH_QUEUES / packet capture made no
-        # difference), while eager steps gain 2.5 % (174.8 vs 179.3 ms); DVQ_SIDE_WGRAD=graph forces it inside captures too.
-        # A capture that is replayed as a launch list keeps the fork: the list issues the side chain on the side stream.
-        mode = os.environ.get("DVQ_SIDE_WGRAD", "1")
-        _side_on = mode == "graph" or (mode == "1" and (not capturing() or step_replay_mode() == "list"))
+        # inside a capture too: the launch list issues the recorded side chain on the side stream
+        _side_on = switch("DVQ_SIDE_WGRAD") != "0"
         return self
 
     def __exit__(self, *exc):

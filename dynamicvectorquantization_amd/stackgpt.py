@@ -13,7 +13,6 @@ walks the tapes (gradients accumulate in place into .grad / the flat optimizer b
 from __future__ import annotations
 
 import math
-import os
 
 import torch
 import torch.nn as nn
@@ -37,7 +36,7 @@ _next_seed = rt.next_dropout_seed
 
 
 def _fuse_drop_bwd() -> bool:
-    return os.environ.get("DVQ_FUSE_DROP_BWD", "1") != "0"
+    return rt.switch("DVQ_FUSE_DROP_BWD") != "0"
 
 
 def _drop(x, p, training, tape, key):
@@ -128,8 +127,7 @@ class CausalSelfAttention(nn.Module):
         return ent
 
     def _qkv_fusable(self, x2d, hs):
-        return (hs == 128 and x2d.dtype == torch.bfloat16 and os.environ.get("DVQ_QKV_FUSED", "1") != "0" and
-                os.environ.get("DVQ_LINEAR_MULTIPACK", "1") != "0" and
+        return (hs == 128 and x2d.dtype == torch.bfloat16 and rt.switch("DVQ_QKV_FUSED") != "0" and
                 all(l.bias is not None and l.out_p == l.out_features for l in (self.key, self.query, self.value)))
 
     def fwd(self, x2d, b, t, tape, resid=None):
@@ -146,7 +144,7 @@ class CausalSelfAttention(nn.Module):
             p_drop = self.attn_drop.p if self.training else 0.0
             seed = _next_seed() if p_drop > 0.0 else 0
             dm = None
-            if tape is not None and p_drop > 0.0 and os.environ.get("DVQ_ATTN_DROP_MASK", "1") == "1":
+            if tape is not None and p_drop > 0.0:
                 dm = K.attn_causal_drop_mask(x2d, b, t, nh)
             y, lse = K.attn_causal_fwd_fused(qkv, cols, b, t, nh, 1.0 / math.sqrt(hs), p_drop, seed, drop_mask=dm)
             out = self.proj.fwd(y, _child(tape, "proj"))
@@ -169,9 +167,9 @@ class CausalSelfAttention(nn.Module):
             # kernels instead of each hashing every element again (19 of ~30 vector-ALU issue slots per score).  With the first-generation
             # kernels this bought nothing (84.14 vs 84.06 ms per step: they waited on LDS refills and barriers,
             # profiles/r04_attn_bwd_probe.txt); with the round-6 kernels (csrc/attention2.hip) the backward is 0.301 instead of 0.437 ms
-            # per layer.  DVQ_ATTN_DROP_MASK=0: rehash
+            # per layer.
             dm = None
-            if tape is not None and p_drop > 0.0 and os.environ.get("DVQ_ATTN_DROP_MASK", "1") == "1":
+            if tape is not None and p_drop > 0.0:
                 dm = K.attn_causal_drop_mask(q, b, t, nh)
             y, lse = K.attn_causal_fwd(q, k, v, b, t, nh, 1.0 / math.sqrt(hs), p_drop, seed, drop_mask=dm)
             if tape is not None:
@@ -211,11 +209,8 @@ class CausalSelfAttention(nn.Module):
             dq, dk, dv = K.attn_causal_bwd(q, k, v, s_["y"], dy, s_["lse"], b, t, nh, 1.0 / math.sqrt(hs), p_drop, seed,
                                            drop_mask=s_.get("drop_mask"))
             dx = self.query.bwd(dq, tape.child("q"))
-            if os.environ.get("DVQ_LINEAR_ADDEND", "0") == "1":
-                # accumulating in the GEMM epilogues (dvq_gemm_nt_res) instead of two add kernels measured SLOWER: 82.2 vs 80.9 ms per
-                # step -- the HBM-bound adds overlap the weight-gradient GEMMs on the side stream, the epilogue work does not
-                dx = self.key.bwd(dk, tape.child("k"), addend=dx)
-                return self.value.bwd(dv, tape.child("v"), addend=dx)
+            # (accumulating in the GEMM epilogues instead of two add kernels measured SLOWER: 82.2 vs 80.9 ms per step -- the HBM-bound
+            #  adds overlap the weight-gradient GEMMs on the side stream, the epilogue work does not)
             dx = K.add(dx, self.key.bwd(dk, tape.child("k")))
             return K.add(dx, self.value.bwd(dv, tape.child("v")))
         dyf, vf, qf = dy.reshape(-1), v.reshape(-1), q.reshape(-1)
@@ -260,7 +255,7 @@ class CausalSelfAttention(nn.Module):
                 K.gemm_tn(dflat[i * c:], x2d, m, c, c, c3, c, c, out=_grad_buf(lin.weight), colsum=_grad_buf(lin.bias))
 
         dx = K.gemm_nt(dqkv, pk["wt"], m, c, c3, c3, c3, c)
-        if m >= 1024 and rt.side_wgrad_enabled() and os.environ.get("DVQ_LINEAR_SIDE", "1") != "0":
+        if m >= 1024 and rt.side_wgrad_enabled():
             rt.run_on_side(wgrad, dqkv, x2d)
         else:
             wgrad()
@@ -391,7 +386,7 @@ class DecodeState:
         # sampler is launch-bound (24 layers x ~12 small kernels per token), a replay costs one launch.  DVQ_DECODE_GRAPH=0: eager
         self.t_pos = torch.zeros(1, dtype=torch.long, device=dev)
         self.t_con = torch.zeros(1, dtype=torch.long, device=dev)
-        self.use_graph = os.environ.get("DVQ_DECODE_GRAPH", "1") != "0"
+        self.use_graph = rt.switch("DVQ_DECODE_GRAPH") != "0"
         self._steps = {}
         self._stacks = {}
         self._sig = self._weights_signature()
@@ -438,7 +433,7 @@ class DecodeState:
         blocks, caches = (g.position_transformer, self.pos_cache) if which == "pos" else (g.content_transformer, self.con_cache)
         c, cd = g.config.n_embd, rt.compute_dtype()
         nh = blocks[0].attn.n_head
-        if (getattr(self, "_no_stack", False) or os.environ.get("DVQ_DECODE_STACK", "1") == "0" or cd != torch.bfloat16 or
+        if (getattr(self, "_no_stack", False) or rt.switch("DVQ_DECODE_STACK") == "0" or cd != torch.bfloat16 or
                 not K.decode_stack_ok(self.b, c, nh, blocks[0].mlp[0].out_features, self.max_rows)):
             return None
         ent = self._stacks.get(which)
@@ -473,7 +468,7 @@ class DecodeState:
                 x = _block_append_dev(blk, x, cache, t_dev)
             return x
         return K.decode_stack(ent["table"], ent["n"], x.contiguous(), ent["nh"], ent["f"], self.max_rows, t_dev, ent["eps"], ent["scratch"],
-                              int(os.environ.get("DVQ_DECODE_WGS", "0")), table_host=ent["host"])
+                              int(rt.switch("DVQ_DECODE_WGS")), table_host=ent["host"])
 
     def _step(self, key, body, inputs):
         """run `body(*static_inputs)`: eagerly the first time (creates weight caches, kernel attributes), then captured once and
@@ -489,21 +484,19 @@ class DecodeState:
             return body(*ent["static"])
         if ent["graph"] is None:
             # replayed as a launch list (csrc/cmdlist.hip: the recorded launches re-issued on this lane's stream, ~2 us of host time
-            # each) unless DVQ_DECODE_REPLAY=graph: hipGraphLaunch of a ~130-node token step costs ~0.8 ms of host time on ROCm 7.2,
-            # which capped concurrent lanes at 1250 token steps / s whatever their number (profiles/r06_sampler_lanes.txt)
-            as_list = os.environ.get("DVQ_DECODE_REPLAY", "list") == "list"
-            gr = torch.cuda.CUDAGraph(keep_graph=True) if as_list else torch.cuda.CUDAGraph()
+            # each): hipGraphLaunch of a ~130-node token step costs ~0.8 ms of host time on ROCm 7.2, which capped concurrent lanes at
+            # 1250 token steps / s whatever their number (profiles/r06_sampler_lanes.txt)
+            gr = torch.cuda.CUDAGraph(keep_graph=True)
             # thread-local capture mode: another sampling lane (Dualformer.sample_many runs one host thread per stream) may launch and
             # allocate on ITS stream while this one records
             with torch.cuda.graph(gr, capture_error_mode="thread_local"):
                 ent["out"] = body(*ent["static"])
             ent["graph"], ent["list"] = gr, None
-            if as_list:
-                from ._lib import DvqError
-                try:
-                    ent["list"] = K.CmdList(gr)
-                except DvqError:          # a node kind the list cannot re-issue (a torch memcpy): this body replays as a hipGraph
-                    ent["list"] = None
+            from ._lib import DvqError
+            try:
+                ent["list"] = K.CmdList(gr)
+            except DvqError:              # a node kind the list cannot re-issue (a torch memcpy): this body replays as a hipGraph
+                pass
         if ent.get("list") is not None:
             cur = torch.cuda.current_stream()
             ent["list"].replay(cur, cur)

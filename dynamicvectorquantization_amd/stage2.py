@@ -9,8 +9,6 @@ the same library.
 """
 from __future__ import annotations
 
-import os
-
 import torch
 import torch.nn as nn
 
@@ -433,12 +431,11 @@ class _SamplerMixin:
     def _draw_rule(self, logits2d, temperature, sample, k, p, rule, cfg=None):
         """one token per row under constraint `rule` = (kind, sampled positions or None, done flags): ONE fused launch
         (kernels.sample_constrained: mask rules + top-k / top-p + softmax + multinomial / top-1) when the logits are on the device;
-        DVQ_SAMPLER=torch (or a vocabulary beyond the kernel's 2048 columns) keeps the op-by-op path the golden tests pin.
+        CPU logits, other dtypes or a vocabulary beyond the kernel's 2048 columns keep the op-by-op path the golden tests pin.
         cfg = classifier-free-guidance scale or None: the rows are [conditional ; unconditional] pairs, each pair draws from the
         guided logits (kernels.sample_guided) and its token is returned in both of its rows"""
         kind, sampled, done = rule
-        if logits2d.is_cuda and logits2d.shape[1] <= 2048 and logits2d.dtype in (torch.float32, torch.bfloat16) and \
-                os.environ.get("DVQ_SAMPLER", "fused") != "torch":
+        if logits2d.is_cuda and logits2d.shape[1] <= 2048 and logits2d.dtype in (torch.float32, torch.bfloat16):
             # {seed, counter} of the kernel's counter-based generator, keyed by torch's seed: a later torch.manual_seed() /
             # seed_everything() restarts the stream (same seed -> same samples, like the op-by-op path's torch generator)
             seed = torch.initial_seed() & 0x7FFFFFFFFFFFFFFF

@@ -21,10 +21,6 @@ import torch.distributed as dist
 from . import kernels as K
 from . import runtime as rt
 
-_FORCE_DP = os.environ.get("DVQ_FORCE_DP", "0") == "1"
-_NOOP_COLL = os.environ.get("DVQ_DP_NOOP_COLLECTIVES", "0") == "1"      # debugging: exchange points without the RCCL calls
-_NO_HOOK = os.environ.get("DVQ_DP_NO_HOOK", "0") == "1"                 # debugging: no all-reduce launch from inside the backward
-
 
 # ---- LR schedules (models/stage1/utils.py:6-24) ----------------------------------------------------
 def _fn_linear_warmup(warmup_steps, step):
@@ -195,7 +191,7 @@ class GradBuckets:
 
     def _active(self):
         # DVQ_FORCE_DP=1: exchange even in a one-rank group (exercises the RCCL / capture-break path on a single GPU)
-        return dist.is_available() and dist.is_initialized() and (dist.get_world_size(self.pg) > 1 or _FORCE_DP)
+        return dist.is_available() and dist.is_initialized() and (dist.get_world_size(self.pg) > 1 or rt.force_dp())
 
     def reduce_range(self, lo, hi):
         """start averaging flat_g[lo:hi] over ranks NOW (asynchronously, on RCCL's stream) -- called from inside the
@@ -213,7 +209,7 @@ class GradBuckets:
         chunks = [self.fp.flat_g[a:min(hi, a + step)] for a in range(lo, hi, step)]
 
         def launch():        # eager even when the step is being captured (rt.graph_break): RCCL runs on its own stream
-            if _NOOP_COLL:
+            if rt.switch("DVQ_DP_NOOP_COLLECTIVES") == "1":        # debugging: exchange points without the RCCL calls
                 self.launched += len(chunks)
                 return
             for c in chunks:
@@ -362,12 +358,12 @@ class Trainer:
         self.opts, self.scheds = model.configure_optimizers()
         self.buckets = [GradBuckets(o.flatten()) for o in self.opts]
         broadcast_model(model)             # identical start on every rank (DDP's parameter / buffer broadcast), not just equal seeds
-        self.check_every = int(os.environ.get("DVQ_DP_CHECK_EVERY", "0"))
+        self.check_every = int(rt.switch("DVQ_DP_CHECK_EVERY"))
         import inspect
         # Lightning passes optimizer_idx only to modules that declare it (two-optimizer stage 1); stage 2 has one optimizer
         self._takes_opt_idx = "optimizer_idx" in inspect.signature(model.training_step).parameters
         if use_graph is None:
-            use_graph = os.environ.get("DVQ_STEP_GRAPH", "1") != "0"
+            use_graph = rt.switch("DVQ_STEP_GRAPH") != "0"
         self.use_graph = bool(use_graph) and bool(getattr(model, "GRAPH_SAFE", False))
         self.graph_after = graph_after
         self._graph = None            # dict(sg, sig, static, losses)
@@ -519,7 +515,7 @@ class Trainer:
         (GradBuckets.reduce_params), the closing reduce() covers what is left.  Only the optimizer whose backward is about to
         run is armed."""
         gb = self.buckets[oi]
-        armed = gb._active() and not _NO_HOOK
+        armed = gb._active() and rt.switch("DVQ_DP_NO_HOOK") != "1"
         for mod in self.model.modules():
             if hasattr(mod, "_grad_hook"):
                 mod._grad_hook = gb.reduce_params if armed else None

@@ -235,7 +235,6 @@ def test_two_stream_loss_schedule_matches_single_stream(dev, mode, monkeypatch):
     the step the single-stream schedule gives: every image's values are independent of the batch it is evaluated in.  Compared on
     ONE step from identical parameters (later steps carry Adam's sign-level amplification of rounding noise and code flips, which the
     golden tests bound separately): both losses and every parameter gradient at the moment its optimizer steps."""
-    from dynamicvectorquantization_amd import losses as L
     from dynamicvectorquantization_amd import runtime as rt
     from dynamicvectorquantization_amd.config import instantiate_from_config
     from dynamicvectorquantization_amd.trainer import Trainer
@@ -243,8 +242,8 @@ def test_two_stream_loss_schedule_matches_single_stream(dev, mode, monkeypatch):
     c, g = TRAIN_STEP["small"], GEOM["small"]
     res = []
     for two_stream in (True, False):
-        monkeypatch.setattr(L, "_GEN_SIDE", two_stream)
-        monkeypatch.setattr(L, "_LOSS_PREFETCH", two_stream)
+        monkeypatch.setenv("DVQ_GEN_SIDE", "1" if two_stream else "0")
+        monkeypatch.setenv("DVQ_LOSS_PREFETCH", "1" if two_stream else "0")
         with rt.compute_dtype_ctx(mode):
             torch.manual_seed(0)
             model = instantiate_from_config(model_config(**g, loss="full", ndf=c["ndf"])).to(dev)

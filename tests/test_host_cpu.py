@@ -449,3 +449,71 @@ def test_csrc_environment_switches_are_listed_and_documented():
     table = doc[doc.index("| variable | effect |"):doc.index("**Retired switches.**")]
     for name in sorted(CSRC_GETENV_SWITCHES | CSRC_PROBE_SWITCHES):
         assert re.search(r"\b%s\b" % name, table), f"{name} is read in csrc/ but has no row in the switch table of docs/design/03-kernels.md"
+
+
+# the environment names the Python package reads that are paths or build inputs, not switches: read where they are used
+PY_ENV_NOT_SWITCHES = {"DVQ_IMAGENET_ROOT", "DVQ_VGG16_WEIGHTS", "DVQ_LPIPS_LIN_WEIGHTS", "DVQ_USE_PROBES_LIB", "DVQ_BUILD_EXTRA_FLAGS"}
+
+
+def _switch_table():
+    doc = open(os.path.join(REPO, "docs", "design", "03-kernels.md")).read()
+    return doc[doc.index("| variable | effect |"):doc.index("**Retired switches.**")]
+
+
+def test_python_environment_reads_go_through_the_registry():
+    """every DVQ_* name the package's modules read from the environment is a row of runtime.SWITCHES, read through runtime.switch(),
+    or one of the five path / build-input names; nothing else in the package touches os.environ / getenv"""
+    from dynamicvectorquantization_amd import losses
+    from dynamicvectorquantization_amd import runtime as rt
+    pkg = os.path.join(REPO, "dynamicvectorquantization_amd")
+    # the three reads whose argument is no string literal: the accessor's own, and LPIPS' two weight files (named by class attributes)
+    indirect = {("runtime.py", "name"): set(), ("losses.py", "self.ENV_VGG"): {losses.LPIPS.ENV_VGG}, ("losses.py", "self.ENV_LIN"): {losses.LPIPS.ENV_LIN}}
+    direct, through_switch, seen_indirect = set(), set(), set()
+    for f in sorted(os.listdir(pkg)):
+        if not f.endswith(".py"):
+            continue
+        text = open(os.path.join(pkg, f)).read()
+        reads = re.findall(r"(?:\bos\.environ(?:\.get)?|\bgetenv)\s*[(\[]\s*([^,)\]]*)", text)
+        assert len(reads) == len(re.findall(r"\bos\.environ\b|\bgetenv\b", text)), f"{f}: an environment access that is no plain read"
+        for arg in (a.strip() for a in reads):
+            lit = re.fullmatch(r'"(DVQ_[A-Z0-9_]+)"', arg)
+            if lit:
+                direct.add(lit.group(1))
+            else:
+                assert (f, arg) in indirect, f"{f}: environment read of {arg!r}"
+                seen_indirect.add((f, arg))
+                direct |= indirect[(f, arg)]
+        through_switch |= set(re.findall(r'\bswitch\("(DVQ_[A-Z0-9_]+)"\)', text))
+    assert seen_indirect == set(indirect)
+    assert direct == PY_ENV_NOT_SWITCHES, "a DVQ_* read that bypasses runtime.switch()"
+    assert through_switch == set(rt.SWITCHES), "runtime.SWITCHES and the switch() calls of the package differ"
+    assert not (through_switch & PY_ENV_NOT_SWITCHES)
+
+
+def test_python_switches_have_a_doc_row():
+    from dynamicvectorquantization_amd import runtime as rt
+    table = _switch_table()
+    for name, (default, what) in sorted(rt.SWITCHES.items()):
+        assert isinstance(default, str) and what
+        assert re.search(r"\b%s\b" % name, table), f"{name} is in runtime.SWITCHES but has no row in the switch table of docs/design/03-kernels.md"
+
+
+def test_switch_accessor_reads_the_environment_at_call_time(monkeypatch):
+    from dynamicvectorquantization_amd import runtime as rt
+    with pytest.raises(KeyError):
+        rt.switch("DVQ_NOT_A_SWITCH")
+    for name, (default, _) in rt.SWITCHES.items():
+        monkeypatch.delenv(name, raising=False)
+        assert rt.switch(name) == default
+    monkeypatch.setenv("DVQ_GEN_SIDE", "0")              # set long after runtime was imported
+    assert rt.switch("DVQ_GEN_SIDE") == "0"
+    monkeypatch.setenv("DVQ_DECODE_WGS", "96")
+    assert rt.switch("DVQ_DECODE_WGS") == "96"
+    monkeypatch.delenv("DVQ_GEN_SIDE")
+    assert rt.switch("DVQ_GEN_SIDE") == "1"
+    # set_fuse_gn_prologue(), once called, overrides the environment
+    monkeypatch.setattr(rt, "_fuse_gn", None)
+    monkeypatch.setenv("DVQ_FUSE_GN", "1")
+    assert rt.fuse_gn_prologue() is True
+    rt.set_fuse_gn_prologue(False)
+    assert rt.fuse_gn_prologue() is False
