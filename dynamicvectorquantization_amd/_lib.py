@@ -188,6 +188,11 @@ SIGNATURES = {
     "dvq_vq_ortho_scratch_bytes": (sz, []),
     "dvq_vq_ortho_sumsq": (i32, [vp, i64, f32, vp, vp, vp]),
     "dvq_vq_rownorm_bwd": (i32, [vp, vp, vp, vp, f32, i64, i64, vp, vp]),
+    "dvq_imagelog_workspace_bytes": (sz, [i64]),
+    "dvq_grain_overlay": (i32, [vp, vp, vp, i32, i64, i64, i64, i64, i64, C.c_uint32, C.c_uint32, f32, vp, vp, sz, vp]),
+    "dvq_grain_lines": (i32, [vp, vp, i32, i64, i64, i64, i64, i64, vp]),
+    "dvq_image_grid_shape": (i32, [i64, i64, i64, i64, i64, C.POINTER(i64), C.POINTER(i64)]),
+    "dvq_image_grid_u8": (i32, [vp, i64, i64, i64, i64, i64, i64, i32, vp, sz, vp, sz, vp]),
 }
 
 

@@ -58,6 +58,11 @@ TARGET_ALIASES = {
     "modules.dynamic_modules.label_provider.ClassForContentOnlyPositionAwareSOSProvider":
         (_P + "stage2", "ClassForContentOnlyPositionAwareSOSProvider"),
     "modules.dynamic_modules.label_provider.ClassAwareSOSProvider": (_P + "stage2", "ClassAwareSOSProvider"),
+    "modules.dynamic_modules.utils.draw_dual_grain_256res_color": (_P + "imagelog", "draw_dual_grain_256res_color"),
+    "modules.dynamic_modules.utils.draw_triple_grain_256res_color": (_P + "imagelog", "draw_triple_grain_256res_color"),
+    "modules.dynamic_modules.utils.draw_dual_grain_256res": (_P + "imagelog", "draw_dual_grain_256res"),
+    "modules.dynamic_modules.utils.draw_triple_grain_256res": (_P + "imagelog", "draw_triple_grain_256res"),
+    "modules.dynamic_modules.utils.instantiate_from_config": (_P + "config", "instantiate_from_config"),
     "utils.utils.instantiate_from_config": (_P + "config", "instantiate_from_config"),
     "data.build.DataModuleFromConfig": (_P + "data", "DataModuleFromConfig"),
     "data.imagenet.ImageNetTrain": (_P + "data", "ImageNetTrain"),

@@ -748,6 +748,39 @@ class DualGrainVQModel(nn.Module):
     def get_code_emb_with_depth(self, code):
         return self.quantize.get_codebook_entry(code)
 
+    @torch.no_grad()
+    def log_images(self, batch, max_images=None, **kwargs):
+        """the reference's picture panels, in its key order (dqvae_dual_entropy.py:244-256, dqvae_dual_feat.py:180-189,
+        dqvae_triple_feat.py:201-215): one forward over the whole batch, the grain pictures drawn by kernels on the device
+        (imagelog.draw_*).  `max_images`: draw only the first that many grain pictures (ImageLogger keeps no more of any panel).
+        Nothing the training step reads is left changed: no EMA update in eval mode, the Gumbel search's generator state is put back."""
+        from . import imagelog as IL
+        x = self.get_input(batch, self.image_key).to(next(self.parameters()).device)
+        if x.dtype != torch.float32 or not x.is_contiguous():
+            x = x.float().contiguous()
+        last = self.__dict__.get("_last")
+        rng = getattr(self.quantize, "_rng_state", None)            # MaskVectorQuantize: device {seed, counter} of its Gumbel draws
+        rng_saved = rng.clone() if rng is not None else None
+        try:
+            xrec, _, grain, _, x_entropy = self._forward5(x)
+        finally:
+            self._last = last
+            if hasattr(self.quantize, "_rng_state"):               # as found: the old values, or not created yet
+                self.quantize._rng_state = rng.copy_(rng_saved) if rng is not None else None
+        n = x.shape[0] if max_images is None else max(1, min(int(max_images), x.shape[0]))
+        log = {"inputs": x, "reconstructions": xrec}
+        xs, gs = x[:n], grain[:n].contiguous()
+        if self.N_GRAINS == 3:
+            log["grain"] = IL.draw_triple_grain_256res(images=xs.clone(), indices=gs)
+            log["grain_color"] = IL.draw_triple_grain_256res_color(images=xs, indices=gs)
+        elif self.USES_ENTROPY:
+            log["grain_map"] = IL.draw_dual_grain_256res_color(images=xs, indices=gs, scaler=0.7)
+            if x_entropy is not None:
+                log["entropy_map"] = IL.draw_dual_grain_256res_color(images=xs, indices=IL.normalize_scores(x_entropy)[:n], scaler=0.7)
+        else:
+            log["grain_color"] = IL.draw_dual_grain_256res_color(images=xs, indices=gs, scaler=0.7)
+        return log
+
 
 class DualGrainFeatVQModel(DualGrainVQModel):
     """models/stage1_dynamic/dqvae_dual_feat.py: the same autoencoder without the entropy branch (feature router);

@@ -1410,3 +1410,71 @@ def tokens_unpack(codes, grain_bits, hw1, hw2, order, codes6, lc, lf, n_fine_cel
                                   lc, lf, _p(cc), _p(cp), _p(fc), _p(fp), _s()), "dvq_tokens_unpack")
     return {"coarse_content": cc, "fine_content": fc, "coarse_position": cp, "fine_position": fp,
             "coarse_segment": torch.zeros_like(cc), "fine_segment": torch.ones_like(fc)}
+
+
+# ---------------------------------------------------------------------------------------------
+# training-time image logging (csrc/imagelog.hip, docs/design/18-image-logging.md)
+# ---------------------------------------------------------------------------------------------
+def imagelog_workspace(segments, device):
+    """uint8 workspace of dvq_imagelog_workspace_bytes(segments) bytes (partial minima / maxima; segments = batch size for the overlay,
+    1 for the grid)"""
+    return torch.empty(int(lib().dvq_imagelog_workspace_bytes(int(segments))), dtype=torch.uint8, device=device)
+
+
+def _grain_args(name, x, m):
+    if x.dim() != 4 or x.shape[1] != 3 or x.dtype != torch.float32:
+        raise _lib.DvqError(f"{name}: images must be fp32 [B,3,H,W], got {x.dtype} {tuple(x.shape)}")
+    if m.dim() != 3 or m.shape[0] != x.shape[0]:
+        raise _lib.DvqError(f"{name}: map must be [B,h,w] with the images' batch size, got {tuple(m.shape)} for {tuple(x.shape)}")
+
+
+def grain_overlay(x, grain=None, score=None, levels=2, low=(5, 39, 175), high=(255, 0, 0), scaler=0.9, ws=None, out=None):
+    """x fp32 NCHW [B,3,H,W]; grain int64 [B,h,w] (levels 2 or 3) OR score fp32 [B,h,w] in [0,1] -> fp32 [B,3,H,W] holding k / 255:
+    the image normalised by its own range, blended towards the cell's colour (include/dvq_hip.h, dvq_grain_overlay)"""
+    m = grain if grain is not None else score
+    if (grain is None) == (score is None):
+        raise _lib.DvqError("grain_overlay: pass a grain map or a score map, not both or neither")
+    _grain_args("grain_overlay", x, m)
+    if m.dtype != (torch.int64 if grain is not None else torch.float32):
+        raise TypeError(f"grain_overlay: a grain map is int64, a score map fp32; got {m.dtype}")
+    b, _, hh, ww = x.shape
+    if ws is None:
+        ws = imagelog_workspace(b, x.device)
+    if out is None:
+        out = torch.empty_like(x)
+    rgb = [(int(c[0]) << 16) | (int(c[1]) << 8) | int(c[2]) for c in (low, high)]
+    check(lib().dvq_grain_overlay(_p(x), _p(grain), _p(score), int(levels), b, hh, ww, m.shape[1], m.shape[2], rgb[0], rgb[1],
+                                  float(scaler), _p(out), _p(ws), ws.numel(), _s()), "dvq_grain_overlay")
+    return out
+
+
+def grain_lines_(x, grain, levels):
+    """in place: -1 on the cell borders and the subdivision lines of grain >= 1 (and == 2) cells; x fp32 [B,3,H,W], grain int64 [B,h,w]"""
+    _grain_args("grain_lines_", x, grain)
+    if grain.dtype != torch.int64:
+        raise TypeError(f"grain_lines_: the grain map is int64, got {grain.dtype}")
+    b, _, hh, ww = x.shape
+    check(lib().dvq_grain_lines(_p(x), _p(grain), int(levels), b, hh, ww, grain.shape[1], grain.shape[2], _s()), "dvq_grain_lines")
+    return x
+
+
+def image_grid_shape(n, h, w, nrow=4, padding=2):
+    gh, gw = C.c_int64(0), C.c_int64(0)
+    check(lib().dvq_image_grid_shape(int(n), int(h), int(w), int(nrow), int(padding), C.byref(gh), C.byref(gw)), "dvq_image_grid_shape")
+    return int(gh.value), int(gw.value)
+
+
+def image_grid_u8(x, nrow=4, padding=2, clamp=True, ws=None, out=None):
+    """x fp32 [N,C,H,W], C in {1, 3} -> uint8 [GH,GW,3]: make_grid(nrow, padding, normalize=True) * 255, truncated (include/dvq_hip.h,
+    dvq_image_grid_u8)"""
+    if x.dim() != 4 or x.dtype != torch.float32:
+        raise _lib.DvqError(f"image_grid_u8: images must be fp32 [N,C,H,W], got {x.dtype} {tuple(x.shape)}")
+    n, c, hh, ww = x.shape
+    gh, gw = image_grid_shape(n, hh, ww, nrow, padding)
+    if ws is None:
+        ws = imagelog_workspace(1, x.device)
+    if out is None:
+        out = torch.empty(gh, gw, 3, dtype=torch.uint8, device=x.device)
+    check(lib().dvq_image_grid_u8(_p(x), n, c, hh, ww, int(nrow), int(padding), int(bool(clamp)), _p(out), out.numel(), _p(ws), ws.numel(),
+                                  _s()), "dvq_image_grid_u8")
+    return out

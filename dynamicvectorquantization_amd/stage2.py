@@ -347,6 +347,50 @@ class Dualformer(_SamplerMixinBase, nn.Module):
         with torch.no_grad():
             return self._step(batch, batch_idx, "val")
 
+    LOG_IMAGES_N = 4
+
+    @torch.no_grad()
+    def log_images(self, batch, temperature=None, top_k=None, top_p=None, top_k_pos=None, top_p_pos=None, sampler_state=None, **kwargs):
+        """dqtransformer_uncond_entropy.py:250-300 (the class variant, dqtransformer_class2_entropy.py:252-301, differs only in what
+        get_xc returns as conditioning: the labels): two sampling passes over N = 4 start tokens -- fine positions transferred from the
+        sampled coarse ones, then everything from scratch -- and, during epoch 0, the inputs and their reconstructions through the
+        token streams.  `sampler_state`: a device {seed, counter} pair (int64 [2]) the draws advance INSTEAD of this model's own
+        sampler stream, so that a log event leaves the training run's random streams where they were (ImageLogger passes its own)."""
+        log = dict()
+        n = self.LOG_IMAGES_N
+        dev = next(self.transformer.parameters()).device
+        if "tokens" in batch:                   # a token batch holds no images: samples only
+            x, c = None, self.get_tc(batch)[1][:n]
+        else:
+            x, c = self.get_xc(batch, n)
+            x = x.to(dev)
+        cond = self.encode_to_c(c.to(dev))
+        kw = dict(temperature=temperature if temperature is not None else 1.0, sample=True,
+                  top_k=top_k if top_k is not None else 300, top_p=top_p if top_p is not None else 1.0,
+                  top_k_pos=top_k_pos if top_k_pos is not None else 100, top_p_pos=top_p_pos if top_p_pos is not None else 1.0,
+                  process=True)
+        own = {k: self.__dict__.get(k) for k in ("_sampler_state", "_sampler_seed")}
+        if sampler_state is not None:           # _draw_rule keeps a state whose recorded seed is torch's current one
+            self.__dict__["_sampler_state"] = sampler_state
+            self.__dict__["_sampler_seed"] = torch.initial_seed() & 0x7FFFFFFFFFFFFFFF
+        try:
+            with torch.random.fork_rng(devices=[dev]):          # draws that take the op-by-op path (torch.multinomial) stay out of the run's streams too
+                log["samples_fixed_fine_position"] = self.decode_to_img(*self.sample_from_scratch(*cond, fix_fine_position=True, **kw))
+                log["samples_from_scratch"] = self.decode_to_img(*self.sample_from_scratch(*cond, fix_fine_position=False, **kw))
+        finally:
+            if sampler_state is not None:
+                for k, v in own.items():
+                    if v is None:
+                        self.__dict__.pop(k, None)
+                    else:
+                        self.__dict__[k] = v
+        if self.current_epoch == 0 and x is not None:
+            _, z_out = self.encode_to_z(x)
+            log["inputs"] = x
+            log["reconstructions"] = self.decode_to_img(z_out["coarse_content"], z_out["fine_content"], z_out["coarse_position"],
+                                                        z_out["fine_position"])
+        return log
+
 
 # ---- sampling (dqtransformer_uncond_entropy.py:302-561, models/stage2/utils.py:22-40) ---------------------------------------
 def top_k_logits(logits, k):

@@ -615,10 +615,12 @@ class Trainer:
         os.replace(tmp, path)
 
     @torch.no_grad()
-    def validate(self, batches):
+    def validate(self, batches, image_logger=None):
         """Lightning's validation loop (train.py:233-262 runs it every `check_val_every_n_epoch`): eval mode, `validation_step` on every
         batch, the logged scalars averaged over the batches -- and over the ranks under data parallelism (`sync_dist=True` of
-        dqvae_dual_entropy.py:185-201) -- train mode restored.  -> {name: float}"""
+        dqvae_dual_entropy.py:185-201) -- train mode restored.  -> {name: float}
+        `image_logger` (imagelog.ImageLogger): offered every validation batch with split "val" (on_validation_batch_end of the
+        reference's CaptionImageLogger)"""
         m = self.model
         was_training = m.training
         m.eval()
@@ -627,6 +629,8 @@ class Trainer:
             for i, b in enumerate(batches):
                 m._logged = {}
                 m.validation_step(b, i)
+                if image_logger is not None:
+                    image_logger.maybe_log(m, b, i, split="val")
                 for k, v in m._logged.items():
                     if torch.is_tensor(v) and v.numel() == 1 or isinstance(v, (int, float)):
                         sums[k] = sums.get(k, 0.0) + (v.detach().double() if torch.is_tensor(v) else float(v))
@@ -644,12 +648,14 @@ class Trainer:
             vec /= dist.get_world_size()
         return {k: float(x) for k, x in zip(keys, vec.cpu())}
 
-    def fit(self, batch_fn, ckpt_path=None, save_every=0, is_rank0=True, val_fn=None, val_every=0, save_top_k=0):
+    def fit(self, batch_fn, ckpt_path=None, save_every=0, is_rank0=True, val_fn=None, val_every=0, save_top_k=0, image_logger=None):
         """`ckpt_path` + `save_every` (steps): rank 0 rewrites last.ckpt periodically, so a preempted run resumes with `-r`.
         `val_fn()` -> iterable of validation batches, run every `val_every` steps and after the last one; with a `monitor` on the model
         (the YAMLs say `monitor: val_rec_loss`) the `save_top_k` best checkpoints by that metric are kept next to last.ckpt as
         `epoch=<e>-<monitor>=<value>.ckpt` -- pytorch_lightning.callbacks.ModelCheckpoint(monitor, save_top_k, save_last=True, mode="min")
-        of the reference's train.py:152-183"""
+        of the reference's train.py:152-183.
+        `image_logger` (imagelog.ImageLogger; None = no pictures, the default): offered every batch after its train step and every
+        validation batch; flushed before fit returns, also when a step raises"""
         self.model.train()
         best = []                                     # (value, path), ascending
         monitor = getattr(self.model, "monitor", None)
@@ -669,7 +675,7 @@ class Trainer:
             del best[save_top_k:]
 
         def run_validation(step):
-            metrics = self.validate(val_fn())
+            metrics = self.validate(val_fn(), image_logger=image_logger if is_rank0 else None)
             self.last_val_metrics = metrics
             if is_rank0 and metrics:
                 print(f"validation @ step {step + 1}: " + " ".join(f"{k}={v:.5f}" for k, v in metrics.items()), flush=True)
@@ -687,13 +693,22 @@ class Trainer:
                         os.remove(old)
                 del best[save_top_k:]
 
-        for step in range(int(self.model.global_step), self.max_steps):
-            losses = self.train_step(batch_fn(step), step)
-            if self.log_every and step % self.log_every == 0:
-                print(f"step {step}: " + " ".join(f"{float(l):.5f}" for l in losses), flush=True)
-            if ckpt_path and save_every and is_rank0 and (step + 1) % save_every == 0 and step + 1 < self.max_steps:
-                self.save_checkpoint(ckpt_path)
-            if val_fn is not None and val_every and ((step + 1) % val_every == 0 or step + 1 == self.max_steps):
-                run_validation(step)
+        if not is_rank0:
+            image_logger = None
+        try:
+            for step in range(int(self.model.global_step), self.max_steps):
+                batch = batch_fn(step)
+                losses = self.train_step(batch, step)
+                if image_logger is not None:
+                    image_logger.maybe_log(self.model, batch, step, split="train")
+                if self.log_every and step % self.log_every == 0:
+                    print(f"step {step}: " + " ".join(f"{float(l):.5f}" for l in losses), flush=True)
+                if ckpt_path and save_every and is_rank0 and (step + 1) % save_every == 0 and step + 1 < self.max_steps:
+                    self.save_checkpoint(ckpt_path)
+                if val_fn is not None and val_every and ((step + 1) % val_every == 0 or step + 1 == self.max_steps):
+                    run_validation(step)
+        finally:
+            if image_logger is not None:
+                image_logger.flush()
         if ckpt_path and is_rank0:
             self.save_checkpoint(ckpt_path)

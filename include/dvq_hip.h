@@ -46,7 +46,9 @@ const char* dvq_last_error(void);
  * written in csrc ("conv3x3_halo_kernel", "conv_nt_pipe_kernel", ...; no template arguments, no fold / reduce / transpose helpers), noted
  * at the dispatch branch that launches it.  "" when nothing was noted (those entry points clear it first).  For timing labels. */
 const char* dvq_last_kernel(void);
-int dvq_version(void);     /* 115: dvq_vq_sample_argmax (+ dvq_vq_trained_prepare), dvq_vq_gumbel_noise, dvq_vq_codebook_grad, dvq_vq_mask_ratio,
+int dvq_version(void);     /* 116: dvq_grain_overlay, dvq_grain_lines, dvq_image_grid_u8 (+ dvq_image_grid_shape, dvq_imagelog_workspace_bytes):
+                            * training-time image logging;
+                            * 115: dvq_vq_sample_argmax (+ dvq_vq_trained_prepare), dvq_vq_gumbel_noise, dvq_vq_codebook_grad, dvq_vq_mask_ratio,
                             * dvq_vq_rownorm / _ortho_sumsq / _rownorm_bwd (gradient-trained codebook: Gumbel search, codebook gradient, orthogonality term);
                             * 114: dvq_tokens_pack, dvq_tokens_unpack (token shards: stored code maps <-> stage-2 streams);
                             * 113: dvq_last_kernel (kernel family of a conv call), dvq_attn_causal_ok / dvq_attn_full_ok / dvq_decode_stack_ok;
@@ -718,6 +720,37 @@ size_t dvq_vq_ortho_scratch_bytes(void);
 int dvq_vq_ortho_sumsq(float* g, int64_t K, float scale, void* scratch, float* out, dvq_stream_t stream);
 int dvq_vq_rownorm_bwd(const float* w, const float* inv, const float* dw, const float* coef_dev, float scale, int64_t K, int64_t D,
                        float* grad, dvq_stream_t stream);
+
+/* ---- training-time image logging (csrc/imagelog.hip, docs/design/18-image-logging.md) ----------------------------------------------
+ * The reference's panels and grid (modules/dynamic_modules/utils.py:41-161, utils/logger.py:137-147) computed on the device.  Every
+ * value is fp32 IEEE, each product / sum / quotient rounded on its own, true divisions, float -> byte conversions truncate; the only
+ * reductions are minima and maxima: outputs are bitwise reproducible.  Inputs are expected finite.
+ * ws: dvq_imagelog_workspace_bytes(segments) bytes of partial extrema, segments = B for the overlay, 1 for the grid (smaller:
+ * DVQ_EWORKSPACE).  Tensors of 2^31 elements or more are refused (DVQ_ESHAPE).
+ *
+ * dvq_grain_overlay: x fp32 NCHW [B][3][H][W]; EITHER grain int64 [B][h][w] with levels in {2, 3} OR score fp32 [B][h][w] in [0, 1]
+ * (the other pointer NULL); low_rgb / high_rgb 0xRRGGBB; scaler in [0, 1].  out fp32 [B][3][H][W] = k / 255 with, per image,
+ *   lo, hi = min / max of the image, d = float32(max(double(hi) - double(lo), 1e-5)), p = (uint8)(((v - lo) / d) * 255);
+ *   colour c: levels 2: high_c * g + low_c * (1 - g) in integers (exactly low or high for g in {0, 1}); levels 3 (s = float(g) / 2)
+ *   and scores (s): (uint8)(float(high_c) * s + float(low_c) * (1 - s));
+ *   k = (uint8)(float(p) + scaler * float(int(c) - int(p)))      [PIL's Image.blend]
+ * The cell size is H / h: DVQ_ESHAPE unless h divides H, w divides W and H / h == W / w.
+ * dvq_grain_lines: in place on x fp32 [B][3][H][W]: -1 on the top row and left column of every cell, for grain >= 1 on the row and
+ * column at cell / 2, for grain == 2 on those at cell / 4 and cell - cell / 4 (draw_dual_grain_256res / draw_triple_grain_256res).
+ * dvq_image_grid_u8: x fp32 [N][C][H][W], C in {1, 3} -> out uint8 [GH][GW][3] (a one-channel input is repeated), torchvision's
+ * make_grid(nrow, padding, normalize=True, pad_value=0) followed by (uint8)(g * 255): optional clamp to [-1, 1], lo / hi over the WHOLE
+ * tensor, d as above, g = (v - lo) / d.  Image k sits at row (k / xmaps) * (H + padding) + padding, column (k % xmaps) * (W + padding)
+ * + padding, xmaps = min(nrow, N); padding and empty cells are 0; N == 1 gives the image itself, unpadded.  dvq_image_grid_shape
+ * reports GH, GW; out_bytes < GH * GW * 3: DVQ_EWORKSPACE. */
+size_t dvq_imagelog_workspace_bytes(int64_t segments);
+int dvq_grain_overlay(const float* x, const int64_t* grain, const float* score, int levels, int64_t B, int64_t H, int64_t W, int64_t h,
+                      int64_t w, uint32_t low_rgb, uint32_t high_rgb, float scaler, float* out, void* ws, size_t ws_bytes,
+                      dvq_stream_t stream);
+int dvq_grain_lines(float* x, const int64_t* grain, int levels, int64_t B, int64_t H, int64_t W, int64_t h, int64_t w,
+                    dvq_stream_t stream);
+int dvq_image_grid_shape(int64_t N, int64_t H, int64_t W, int64_t nrow, int64_t padding, int64_t* grid_h, int64_t* grid_w);
+int dvq_image_grid_u8(const float* x, int64_t N, int64_t C, int64_t H, int64_t W, int64_t nrow, int64_t padding, int clamp, uint8_t* out,
+                      size_t out_bytes, void* ws, size_t ws_bytes, dvq_stream_t stream);
 
 #ifdef __cplusplus
 }

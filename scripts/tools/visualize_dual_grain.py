@@ -2,7 +2,9 @@
 """Grain maps and sequence-length statistics of a (trained) DQ-VAE -- the reference's scripts/tools/visualize_dual_grain.py
 (:27-61) on the HIP path: same --yaml_path / --model_path / --batch_size / --image_save_path; images come from --images
 (folder or .npy) or --synthetic N.  Prints mean / variance / max / min of the per-image token count (1 per coarse cell, 4 per
-fine cell) and stores the grain maps as .npy (+ a PNG overlay per batch when PIL is available).
+fine cell) and stores the grain maps as .npy plus, per batch, the reference's colour overlay `grain_images_<i>.png`
+(draw_dual_grain_256res_color at scaler 0.7, drawn and laid out 8 per row on the device; the grid is stretched to its own value range
+like the training logger's pictures, where torchvision's save_image writes the values as they are).
 
     python scripts/tools/visualize_dual_grain.py --yaml_path configs/stage1/dqvae-entropy-dual-r05_imagenet.yml \\
         --model_path last.ckpt --images /data/val_images --image_save_path out/
@@ -42,18 +44,27 @@ def main():
         images = calibrate.load_images(opt.images, size, opt.limit)
     else:
         ap.error("give --images <folder|.npy> or --synthetic N")
+    from dynamicvectorquantization_amd import kernels as K
+    from dynamicvectorquantization_amd.imagelog import draw_dual_grain_256res_color, draw_triple_grain_256res_color
+    draw = draw_triple_grain_256res_color if getattr(model, "N_GRAINS", 2) == 3 else draw_dual_grain_256res_color
+    if opt.image_save_path:
+        os.makedirs(opt.image_save_path, exist_ok=True)
+        from PIL import Image
     grains = []
     with torch.no_grad():
-        for i in range(0, images.shape[0], opt.batch_size):
+        for n, i in enumerate(range(0, images.shape[0], opt.batch_size)):
             x = torch.from_numpy(images[i:i + opt.batch_size]).cuda()
             out = model(x)
             grains.append(out[2].cpu().numpy())
+            if opt.image_save_path:
+                grain_map = draw(images=x, indices=out[2], scaler=0.7)
+                grid = K.image_grid_u8(grain_map, nrow=8, padding=2, clamp=False)
+                Image.fromarray(grid.cpu().numpy()).save(os.path.join(opt.image_save_path, f"grain_images_{n}.png"))
     grains = np.concatenate(grains)
     stats = calibrate.sequence_length_stats(grains)
     for k in ("mean", "variance", "max", "min"):
         print(f"{k}: ", stats[k])
     if opt.image_save_path:
-        os.makedirs(opt.image_save_path, exist_ok=True)
         np.save(os.path.join(opt.image_save_path, "grain_indices.npy"), grains)
 
 

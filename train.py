@@ -54,6 +54,10 @@ def get_parser():
     p.add_argument("--logdir", type=str, default="logs")
     p.add_argument("--save_every", type=int, default=0,
                    help="rewrite checkpoints/last.ckpt every N steps (0: once per epoch) -- atomic, rank 0 only")
+    p.add_argument("--log_images_every", type=int, default=0,
+                   help="write picture grids of the model's log_images every N batches to <logdir>/images/<split>/ (0: never; the "
+                        "reference's CaptionImageLogger uses 50)")
+    p.add_argument("--log_images_max", type=int, default=16, help="images per picture grid (4 per row)")
     return p
 
 
@@ -241,8 +245,12 @@ def run(rank, world, opt, unknown):
                         g = torch.Generator().manual_seed(opt.seed + 31 * i)
                         b["class_label"] = torch.randint(0, n_classes, (bs,), generator=g).to(dev)
                     yield b
+    image_logger = None
+    if opt.log_images_every > 0 and rank == 0:        # utils/logger.py:57-147 of the reference (train.py:214-221: every 50 batches, 16 images, clamp)
+        from dynamicvectorquantization_amd.imagelog import ImageLogger
+        image_logger = ImageLogger(logdir, batch_frequency=opt.log_images_every, max_images=opt.log_images_max, clamp=True, seed=opt.seed)
     trainer.fit(batch_fn, ckpt_path=ckpt_path, save_every=opt.save_every or opt.steps_per_epoch, is_rank0=rank == 0, val_fn=val_fn,
-                val_every=opt.check_val_every_n_epoch * opt.steps_per_epoch, save_top_k=opt.save_n)
+                val_every=opt.check_val_every_n_epoch * opt.steps_per_epoch, save_top_k=opt.save_n, image_logger=image_logger)
     if rank == 0:
         print("saved", ckpt_path)
     if world > 1:
