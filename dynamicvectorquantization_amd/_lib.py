@@ -165,6 +165,9 @@ SIGNATURES = {
     "dvq_image_desc_bytes": (sz, []),
     "dvq_image_batch_transform": (i32, [vp, vp, vp, vp, i64, i32, i32, vp, vp]),
     "dvq_adamw_dev": (i32, [vp, vp, vp, vp, i64, vp, vp]),
+    "dvq_grad_sqnorm_workspace_bytes": (sz, [i64]),
+    "dvq_grad_sqnorm": (i32, [vp, i64, f32, i32, vp, sz, vp, vp]),
+    "dvq_adamw_clip_dev": (i32, [vp, vp, vp, vp, i64, vp, vp, vp]),
     "dvq_set_f32x8": (i32, [vp, f32, f32, f32, f32, f32, f32, f32, f32, vp]),
     "dvq_sample_rows": (i32, [vp, i64, i64, vp, vp]),
     "dvq_add_uniform": (i32, [vp, i64, f32, vp, vp]),

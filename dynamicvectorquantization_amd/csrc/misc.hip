@@ -578,6 +578,103 @@ __global__ __launch_bounds__(256) void adam_dev_kernel(float* __restrict__ p, co
     }
 }
 
+// ---- global gradient norm, clip coefficient, finite flag (torch.nn.utils.clip_grad_norm_ once per optimizer) ----------------
+// Stage 1: workgroup c owns g[c * SQNORM_CHUNK, min(n, (c + 1) * SQNORM_CHUNK)) and stores ONE fp64 partial; the number of partials
+// and the order of every addition depend on n alone (never on the grid, the CU count or the arrival order of workgroups), so every
+// data-parallel rank gets bit-identical statistics from its bit-identical all-reduced buffer.  Element i of a chunk goes to thread
+// (i / 4) % 256, accumulator i % 4 -- also when the base pointer is not 16-byte aligned (VEC = false: same assignment, 4-byte loads).
+// Squares are formed in fp64 (exact for fp32 inputs): a finite buffer cannot produce a non-finite sum, an Inf / NaN element always does.
+constexpr int64_t SQNORM_CHUNK = 32768;
+
+template <bool VEC>
+__global__ __launch_bounds__(256) void grad_sqnorm_partial_kernel(const float* __restrict__ g, int64_t n,
+                                                                  double* __restrict__ partial) {
+    __shared__ double part[4];
+    const int64_t begin = (int64_t)blockIdx.x * SQNORM_CHUNK;
+    const int64_t rest = n - begin;
+    const int len = (int)(rest < SQNORM_CHUNK ? rest : SQNORM_CHUNK);      // 1 .. SQNORM_CHUNK: the grid has cdiv(n, CHUNK) blocks
+    const float* gc = g + begin;
+    const int nvec = len >> 2;
+    double a0 = 0.0, a1 = 0.0, a2 = 0.0, a3 = 0.0;
+#pragma unroll 8
+    for (int q = threadIdx.x; q < nvec; q += 256) {
+        float x0, x1, x2, x3;
+        if (VEC) {
+            const f32x4 x = *reinterpret_cast<const f32x4*>(gc + 4 * q);
+            x0 = x[0]; x1 = x[1]; x2 = x[2]; x3 = x[3];
+        } else {
+            x0 = gc[4 * q]; x1 = gc[4 * q + 1]; x2 = gc[4 * q + 2]; x3 = gc[4 * q + 3];
+        }
+        a0 += (double)x0 * (double)x0;
+        a1 += (double)x1 * (double)x1;
+        a2 += (double)x2 * (double)x2;
+        a3 += (double)x3 * (double)x3;
+    }
+    const int tail = 4 * nvec + (int)threadIdx.x;                          // len % 4 leftover elements: threads 0..2
+    if (threadIdx.x < 3 && tail < len) a0 += (double)gc[tail] * (double)gc[tail];
+    double acc = wave_sum((a0 + a1) + (a2 + a3));
+    if ((threadIdx.x & 63) == 0) part[threadIdx.x >> 6] = acc;
+    __syncthreads();
+    if (threadIdx.x == 0) partial[blockIdx.x] = (part[0] + part[1]) + (part[2] + part[3]);
+}
+
+// Stage 2 (one workgroup): thread t adds partials t, t + 256, ... in increasing index, then the same fixed tree as stage 1.
+// gstat (32 bytes, 8-byte aligned): [0..7] fp64 norm, [8] fp32 coef, [12] int32 finite, [16] int32 skipped (running count, only
+// ever incremented here), [20] int32 skip-this-step, [24] fp32 clip, [28] int32 guard -- the last two echo the launch arguments.
+__global__ __launch_bounds__(256) void grad_sqnorm_final_kernel(const double* __restrict__ partial, int64_t nparts, float clip,
+                                                                int skip_nonfinite, void* __restrict__ gstat) {
+    __shared__ double part[4];
+    double acc = 0.0;
+    for (int64_t i = threadIdx.x; i < nparts; i += 256) acc += partial[i];
+    acc = wave_sum(acc);
+    if ((threadIdx.x & 63) == 0) part[threadIdx.x >> 6] = acc;
+    __syncthreads();
+    if (threadIdx.x != 0) return;
+    const double sq = (part[0] + part[1]) + (part[2] + part[3]);
+    const bool finite = __builtin_isfinite(sq);
+    const double norm = sqrt(sq);
+    float coef = 1.f;
+    if (clip > 0.f) {
+        // min(1, clip / (norm + 1e-6)) as torch's clamp(max=1) computes it: a NaN norm gives a NaN coefficient, an infinite one 0
+        const double c = (double)clip / (norm + 1e-6);
+        coef = (float)(c > 1.0 ? 1.0 : c);
+    }
+    const int skip = (skip_nonfinite && !finite) ? 1 : 0;
+    *reinterpret_cast<double*>(gstat) = norm;
+    float* gf = reinterpret_cast<float*>(gstat);
+    int* gi = reinterpret_cast<int*>(gstat);
+    gf[2] = coef;
+    gi[3] = finite ? 1 : 0;
+    if (skip) gi[4] += 1;
+    gi[5] = skip;
+    gf[6] = clip;
+    gi[7] = skip_nonfinite ? 1 : 0;
+}
+
+// adam_dev_kernel on the clipped gradient g * coef (g itself is not rewritten); nothing is touched when the guard says skip.
+// coef and the skip flag are one wave-uniform load each; coef == 1 makes the multiply exact, i.e. the update is adam_dev_kernel's
+// BIT FOR BIT (tests/test_gpu_gradclip.py holds it to that).  Which products the compiler fuses into an fma in adam_dev_kernel is
+// its choice (-ffp-contract=fast), and it chose differently once `gv` was itself a product -- so the roundings are spelled out
+// here, contraction off, as adam_dev_kernel's generated code has them: m' = fma(1 - b1, g, b1 * m), v' = b2 * v + ((1 - b2) * g) * g,
+// p' = p * decay - (step * m') / fma(sqrt(v'), 1 / sqrt(bc2), eps).
+__global__ __launch_bounds__(256) void adam_clip_dev_kernel(float* __restrict__ p, const float* __restrict__ g,
+                                                            float* __restrict__ m, float* __restrict__ v, int64_t n,
+                                                            const float* __restrict__ hyper, const float* __restrict__ gstat) {
+    if (reinterpret_cast<const int*>(gstat)[5] != 0) return;
+    const float coef = gstat[2];
+    const float step_size = hyper[0], beta1 = hyper[1], beta2 = hyper[2], eps = hyper[3], inv_sqrt_bc2 = hyper[4],
+                decay_mul = hyper[5];
+    for (int64_t e = (int64_t)blockIdx.x * 256 + threadIdx.x; e < n; e += (int64_t)gridDim.x * 256) {
+#pragma clang fp contract(off)
+        const float gv = g[e] * coef;
+        const float mm = __builtin_fmaf(1.f - beta1, gv, beta1 * m[e]);
+        const float vv = beta2 * v[e] + ((1.f - beta2) * gv) * gv;
+        m[e] = mm;
+        v[e] = vv;
+        p[e] = p[e] * decay_mul - (step_size * mm) / __builtin_fmaf(sqrtf(vv), inv_sqrt_bc2, eps);
+    }
+}
+
 struct F32x8 {
     float v[8];
 };
@@ -1019,6 +1116,38 @@ int dvq_adamw_dev(float* p, const float* g, float* m, float* v, int64_t n, const
     DVQ_REQUIRE(p && g && m && v && hyper && n > 0, DVQ_EINVAL, "dvq_adamw_dev: bad arguments");
     adam_dev_kernel<<<dim3(nblocks(n, 1024)), dim3(256), 0, (hipStream_t)stream>>>(p, g, m, v, n, hyper);
     DVQ_CHECK_LAUNCH("adamw_dev");
+    return DVQ_OK;
+}
+
+size_t dvq_grad_sqnorm_workspace_bytes(int64_t n) { return n > 0 ? (size_t)cdiv64(n, SQNORM_CHUNK) * sizeof(double) : 0; }
+
+int dvq_grad_sqnorm(const float* g, int64_t n, float clip, int skip_nonfinite, void* workspace, size_t workspace_bytes,
+                    void* gstat, dvq_stream_t stream) {
+    DVQ_REQUIRE(g && workspace && gstat && n > 0, DVQ_EINVAL, "dvq_grad_sqnorm: bad arguments");
+    DVQ_REQUIRE(clip >= 0.f && clip <= 3.402823466e38f, DVQ_EINVAL, "dvq_grad_sqnorm: clip must be finite and >= 0 (0 = off)");
+    DVQ_REQUIRE(workspace_bytes >= dvq_grad_sqnorm_workspace_bytes(n), DVQ_EINVAL,
+                "dvq_grad_sqnorm: workspace of %zu bytes, %zu needed", workspace_bytes, dvq_grad_sqnorm_workspace_bytes(n));
+    DVQ_REQUIRE(((uintptr_t)g & 3) == 0 && ((uintptr_t)workspace & 7) == 0 && ((uintptr_t)gstat & 7) == 0, DVQ_EINVAL,
+                "dvq_grad_sqnorm: g must be 4-byte, workspace and gstat 8-byte aligned");
+    const int64_t nparts = cdiv64(n, SQNORM_CHUNK);
+    DVQ_REQUIRE(nparts <= 0x7fffffff, DVQ_EINVAL, "dvq_grad_sqnorm: n too large");
+    if (((uintptr_t)g & 15) == 0)
+        grad_sqnorm_partial_kernel<true><<<dim3((unsigned)nparts), dim3(256), 0, (hipStream_t)stream>>>(g, n, (double*)workspace);
+    else
+        grad_sqnorm_partial_kernel<false><<<dim3((unsigned)nparts), dim3(256), 0, (hipStream_t)stream>>>(g, n, (double*)workspace);
+    DVQ_CHECK_LAUNCH("grad_sqnorm_partial");
+    grad_sqnorm_final_kernel<<<dim3(1), dim3(256), 0, (hipStream_t)stream>>>((const double*)workspace, nparts, clip,
+                                                                            skip_nonfinite, gstat);
+    DVQ_CHECK_LAUNCH("grad_sqnorm_final");
+    return DVQ_OK;
+}
+
+int dvq_adamw_clip_dev(float* p, const float* g, float* m, float* v, int64_t n, const float* hyper, const void* gstat,
+                       dvq_stream_t stream) {
+    DVQ_REQUIRE(p && g && m && v && hyper && gstat && n > 0, DVQ_EINVAL, "dvq_adamw_clip_dev: bad arguments");
+    adam_clip_dev_kernel<<<dim3(nblocks(n, 1024)), dim3(256), 0, (hipStream_t)stream>>>(p, g, m, v, n, hyper,
+                                                                                        (const float*)gstat);
+    DVQ_CHECK_LAUNCH("adamw_clip_dev");
     return DVQ_OK;
 }
 

@@ -1207,6 +1207,39 @@ def adamw_dev(p, g, m, v, hyper):
     check(lib().dvq_adamw_dev(_p(p), _p(g), _p(m), _p(v), p.numel(), _p(hyper), _s()), "dvq_adamw_dev")
 
 
+GRAD_SQNORM_CHUNK = 32768      # elements per fp64 partial of grad_sqnorm (SQNORM_CHUNK of csrc/misc.hip)
+
+
+def grad_sqnorm_workspace_bytes(n) -> int:
+    return int(lib().dvq_grad_sqnorm_workspace_bytes(int(n)))
+
+
+def grad_stats_block(device):
+    """the 32-byte statistics block of grad_sqnorm / adamw_clip_dev (include/dvq_hip.h) before any step: norm 0, coef 1, finite,
+    skipped 0"""
+    return torch.tensor([0, 0, 0x3F800000, 1, 0, 0, 0, 0], dtype=torch.int32, device=device)
+
+
+def grad_sqnorm(g, workspace, gstat, clip=0.0, skip_nonfinite=False):
+    """gstat <- {norm, clip coefficient, finite flag, skipped count} of the flat fp32 gradient buffer g; two launches, no host read"""
+    assert g.dtype == torch.float32 and gstat.dtype == torch.int32 and gstat.numel() == 8
+    check(lib().dvq_grad_sqnorm(_p(g), g.numel(), float(clip), int(bool(skip_nonfinite)), _p(workspace),
+                                workspace.numel() * workspace.element_size(), _p(gstat), _s()), "dvq_grad_sqnorm")
+    return gstat
+
+
+def read_grad_stats(gstat) -> dict:
+    """host copy of a statistics block (synchronises: never inside a step)"""
+    h = gstat.cpu()
+    return {"norm": float(h.view(torch.float64)[0]), "coef": float(h.view(torch.float32)[2]), "finite": bool(int(h[3])),
+            "skipped": int(h[4])}
+
+
+def adamw_clip_dev(p, g, m, v, hyper, gstat):
+    """adamw_dev on g * coef, skipped when the guard of grad_sqnorm said so (coef / skip read from gstat on the device)"""
+    check(lib().dvq_adamw_clip_dev(_p(p), _p(g), _p(m), _p(v), p.numel(), _p(hyper), _p(gstat), _s()), "dvq_adamw_clip_dev")
+
+
 def set_f32x8(dst, values):
     """dst[0:8] <- values (by-value launch arguments: safe to call with the host running many steps ahead)"""
     vals = [float(x) for x in values] + [0.0] * (8 - len(values))

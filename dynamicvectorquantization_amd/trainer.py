@@ -105,6 +105,36 @@ class HipAdam(torch.optim.Optimizer):
         super().__init__(params, dict(lr=lr, betas=betas, eps=eps, weight_decay=weight_decay))
         self.flat = None
         self._fstate = None
+        self._guard = None            # set_grad_guard: dict(clip, skip, ws, gstat)
+
+    def set_grad_guard(self, clip_val=0.0, skip_nonfinite=False):
+        """Global-norm gradient clipping (torch.nn.utils.clip_grad_norm_ over ALL parameter groups of this optimizer, as Lightning's
+        `gradient_clip_val` applies it) and / or a non-finite step guard (docs/design/19-gradient-clipping.md).
+          clip_val > 0:    every step uses g * min(1, clip_val / (||g|| + 1e-6)); the gradient buffer itself is not rewritten;
+          skip_nonfinite:  a step whose sum g^2 is not finite leaves p, m, v untouched and counts in grad_stats()["skipped"].  The step
+                           count (bias corrections) and the LR schedule still advance: the host never learns of the skip.
+        Norm, coefficient and flag are computed and consumed on the device (two extra launches per step, none when both are off).
+        The workspace is allocated here, never inside step(): a captured step sees no allocation."""
+        clip_val = float(clip_val)
+        if not (math.isfinite(clip_val) and clip_val >= 0.0):
+            raise ValueError(f"gradient clip value must be finite and >= 0 (0 = off), got {clip_val}")
+        if self.flat is None:
+            raise ValueError("set_grad_guard works on a flattened HipAdam only (call flatten() first): the per-tensor path has no "
+                             "single gradient buffer to take the norm of")
+        skip_nonfinite = bool(skip_nonfinite)
+        if clip_val == 0.0 and not skip_nonfinite:
+            self._guard = None
+            return
+        old = self._guard
+        g = self.flat.flat_g
+        self._guard = {"clip": clip_val, "skip": skip_nonfinite,
+                       "ws": old["ws"] if old else torch.empty(K.grad_sqnorm_workspace_bytes(g.numel()) // 8, dtype=torch.float64, device=g.device),
+                       "gstat": old["gstat"] if old else K.grad_stats_block(g.device)}
+
+    def grad_stats(self):
+        """{"norm", "coef", "finite", "skipped"} of the last step() -- a host read (synchronises): call it outside the step only.
+        None when neither clipping nor the guard is enabled."""
+        return K.read_grad_stats(self._guard["gstat"]) if self._guard else None
 
     def flatten(self) -> FlatParams:
         if self.flat is None:
@@ -145,11 +175,17 @@ class HipAdam(torch.optim.Optimizer):
                 self.prepare_step()
             self._prepared = False
             st["step"] += 1
+            gd = self._guard
+            if gd is not None:             # norm / coefficient / finite flag of the WHOLE buffer (all groups), on the device
+                K.grad_sqnorm(self.flat.flat_g, gd["ws"], gd["gstat"], gd["clip"], gd["skip"])
             for gi, (off, n) in enumerate(self._segments):
                 if n == 0:
                     continue
                 sl = slice(off, off + n)
-                K.adamw_dev(self.flat.flat_p[sl], self.flat.flat_g[sl], st["m"][sl], st["v"][sl], self._hyper[gi])
+                if gd is not None:
+                    K.adamw_clip_dev(self.flat.flat_p[sl], self.flat.flat_g[sl], st["m"][sl], st["v"][sl], self._hyper[gi], gd["gstat"])
+                else:
+                    K.adamw_dev(self.flat.flat_p[sl], self.flat.flat_g[sl], st["m"][sl], st["v"][sl], self._hyper[gi])
             rt.bump_group_epoch(id(self))      # only this optimizer's packed weights are stale
             return
         for group in self.param_groups:
@@ -353,10 +389,16 @@ class Trainer:
     stay eager between segments, the optimizer reads its hyper-parameters from device memory, batches are copied into
     static input buffers.  `DVQ_STEP_GRAPH=0` (or use_graph=False) keeps every step eager."""
 
-    def __init__(self, model, max_steps, log_every=0, use_graph=None, graph_after=3):
+    def __init__(self, model, max_steps, log_every=0, use_graph=None, graph_after=3, gradient_clip_val=0.0, skip_nonfinite=False):
         self.model, self.max_steps, self.log_every = model, max_steps, log_every
         self.opts, self.scheds = model.configure_optimizers()
         self.buckets = [GradBuckets(o.flatten()) for o in self.opts]
+        # Lightning's Trainer(gradient_clip_val=...): global-norm clipping once per optimizer; skip_nonfinite: a step whose gradient
+        # holds an Inf / NaN changes neither parameters nor Adam moments (HipAdam.set_grad_guard).  Both off (the default): no extra launch, dvq_adamw_dev as ever
+        self.gradient_clip_val, self.skip_nonfinite = float(gradient_clip_val), bool(skip_nonfinite)
+        if self.gradient_clip_val != 0.0 or self.skip_nonfinite:
+            for o in self.opts:
+                o.set_grad_guard(self.gradient_clip_val, self.skip_nonfinite)
         broadcast_model(model)             # identical start on every rank (DDP's parameter / buffer broadcast), not just equal seeds
         self.check_every = int(rt.switch("DVQ_DP_CHECK_EVERY"))
         import inspect
@@ -441,7 +483,8 @@ class Trainer:
             else:
                 items.append((k, repr(v)))
         world = dist.get_world_size() if dist.is_available() and dist.is_initialized() else 1
-        return (tuple(items), bool(m.training), rt.compute_dtype(), rt.impl(), rt.fuse_gn_prologue(), world, extra)
+        guard = (self.gradient_clip_val, self.skip_nonfinite)           # launch arguments of the recorded norm kernels
+        return (tuple(items), bool(m.training), rt.compute_dtype(), rt.impl(), rt.fuse_gn_prologue(), world, extra, guard)
 
     def _py_state(self):
         return ([o._fstate["step"] for o in self.opts], [s["scheduler"].state_dict() for s in self.scheds],
@@ -507,6 +550,22 @@ class Trainer:
 
     def drop_graph(self):
         self._graph, self._stable, self._last_sig = None, 0, None
+
+    def set_grad_guard(self, gradient_clip_val=0.0, skip_nonfinite=False):
+        """change the setting of every optimizer between steps (the skip counters survive a change of values, not switching both
+        off); a recorded step with other settings is not replayed: the signature differs, the step is recorded again"""
+        for o in self.opts:
+            o.set_grad_guard(gradient_clip_val, skip_nonfinite)
+        self.gradient_clip_val, self.skip_nonfinite = float(gradient_clip_val), bool(skip_nonfinite)
+
+    @property
+    def grad_guard_enabled(self):
+        return any(getattr(o, "_guard", None) is not None for o in self.opts)
+
+    def grad_stats(self):
+        """one {"norm", "coef", "finite", "skipped"} per optimizer (None for one without clipping / guard), of the last step --
+        eager or replayed.  A host read: outside the step only."""
+        return [o.grad_stats() if getattr(o, "_guard", None) is not None else None for o in self.opts]
 
     def _arm_overlap(self, oi):
         """Gradient exchange overlapped with the backward: every module of the model that declares `_grad_hook` calls it with the
@@ -578,10 +637,13 @@ class Trainer:
         st["step"] = step
 
     def state_dict(self):
-        return {"state_dict": self.model.state_dict(), "global_step": int(self.model.global_step),
-                "epoch": int(getattr(self.model, "current_epoch", 0)),
-                "optimizer_states": [self._optimizer_state_dict(o) for o in self.opts],
-                "lr_schedulers": [s["scheduler"].state_dict() for s in self.scheds]}
+        sd = {"state_dict": self.model.state_dict(), "global_step": int(self.model.global_step),
+              "epoch": int(getattr(self.model, "current_epoch", 0)),
+              "optimizer_states": [self._optimizer_state_dict(o) for o in self.opts],
+              "lr_schedulers": [s["scheduler"].state_dict() for s in self.scheds]}
+        if self.grad_guard_enabled:          # only then: a run without the feature writes the checkpoint it always wrote
+            sd["grad_guard"] = {"skipped": [(st["skipped"] if st else 0) for st in self.grad_stats()]}
+        return sd
 
     @torch.no_grad()
     def load_state_dict(self, ckpt, strict=True):
@@ -606,6 +668,13 @@ class Trainer:
             for g, lr in zip(s["scheduler"].optimizer.param_groups, s["scheduler"].get_last_lr()):
                 g["lr"] = lr
         self.model.global_step = int(ckpt.get("global_step", 0))
+        # skipped-step counters of the non-finite guard: restored where this trainer has the guard's statistics block, absent key
+        # (a checkpoint written without the feature) = counters stay as they are
+        skipped = ckpt.get("grad_guard", {}).get("skipped", [])
+        if len(skipped) == len(self.opts):
+            for o, n in zip(self.opts, skipped):
+                if getattr(o, "_guard", None) is not None:
+                    o._guard["gstat"][4] = int(n)
 
     def save_checkpoint(self, path):
         """atomic write (temp file + rename): a crash while saving never destroys the previous last.ckpt"""
@@ -702,7 +771,11 @@ class Trainer:
                 if image_logger is not None:
                     image_logger.maybe_log(self.model, batch, step, split="train")
                 if self.log_every and step % self.log_every == 0:
-                    print(f"step {step}: " + " ".join(f"{float(l):.5f}" for l in losses), flush=True)
+                    line = f"step {step}: " + " ".join(f"{float(l):.5f}" for l in losses)      # float(l) synchronises
+                    if self.grad_guard_enabled:
+                        line += "".join(f" | opt{i} gnorm={st['norm']:.4g} coef={st['coef']:.4g} skipped={st['skipped']}"
+                                        for i, st in enumerate(self.grad_stats()) if st)
+                    print(line, flush=True)
                 if ckpt_path and save_every and is_rank0 and (step + 1) % save_every == 0 and step + 1 < self.max_steps:
                     self.save_checkpoint(ckpt_path)
                 if val_fn is not None and val_every and ((step + 1) % val_every == 0 or step + 1 == self.max_steps):

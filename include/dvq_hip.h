@@ -607,6 +607,25 @@ int dvq_label_dropout(const int64_t* labels, int64_t B, float p, int64_t null_la
  * hyper[8] = {lr / (1 - beta1^t), beta1, beta2, eps, 1 / sqrt(1 - beta2^t), 1 - lr * weight_decay, unused, unused}.
  * Same update as dvq_adamw (models/stage1_dynamic/dqvae_dual_entropy.py:228-232 Adam, dqtransformer_uncond_entropy.py:92-128 AdamW). */
 int dvq_adamw_dev(float* p, const float* g, float* m, float* v, int64_t n, const float* hyper, dvq_stream_t stream);
+/* Global gradient norm of one optimizer's flat gradient buffer, with the clip coefficient of torch.nn.utils.clip_grad_norm_ and a
+ * finite flag (Lightning's --gradient_clip_val, applied once per optimizer; docs/design/19-gradient-clipping.md).  Two launches, no
+ * atomics, no host read: (1) one fp64 partial of sum g^2 per fixed 32768-element chunk into `workspace`
+ * (dvq_grad_sqnorm_workspace_bytes(n), caller-owned), (2) one workgroup adds the partials in a fixed order and writes
+ *   gstat (32 bytes, 8-byte aligned) = { double norm = sqrt(sum g^2);
+ *                                        float coef = clip > 0 ? min(1, clip / (norm + 1e-6)) : 1;
+ *                                        int32 finite = isfinite(sum g^2);
+ *                                        int32 skipped += (skip_nonfinite && !finite);     running count, never reset here
+ *                                        int32 skip = (skip_nonfinite && !finite);         read by dvq_adamw_clip_dev
+ *                                        float clip; int32 skip_nonfinite }                echo of the arguments
+ * The order of every addition depends on n alone: equal buffers give bit-equal results on every device and every launch.  Squares
+ * are taken in fp64, so `finite` is false iff an element is Inf / NaN.  clip must be finite and >= 0 (0 = no clipping). */
+size_t dvq_grad_sqnorm_workspace_bytes(int64_t n);
+int dvq_grad_sqnorm(const float* g, int64_t n, float clip, int skip_nonfinite, void* workspace, size_t workspace_bytes,
+                    void* gstat, dvq_stream_t stream);
+/* dvq_adamw_dev on the gradient g * gstat.coef (g is not rewritten); returns without touching p, m, v when gstat.skip is set.
+ * With coef == 1 the results are bit-identical to dvq_adamw_dev. */
+int dvq_adamw_clip_dev(float* p, const float* g, float* m, float* v, int64_t n, const float* hyper, const void* gstat,
+                       dvq_stream_t stream);
 /* dst[0..7] <- the eight scalars (passed by value in the launch: no pageable host copy, no host buffer to keep alive) */
 int dvq_set_f32x8(float* dst, float v0, float v1, float v2, float v3, float v4, float v5, float v6, float v7,
                   dvq_stream_t stream);

@@ -11,6 +11,8 @@ path, without pytorch_lightning / OmegaConf:
 * learning rate = ngpu * batch_size * base_learning_rate (train.py:248-257);
 * data: the BASELINE configs run on synthetic batches (`--synthetic`, default); a real
   `data:` section is instantiated only when its target is importable.
+* `--gradient_clip_val X` (Lightning's Trainer flag): global-norm gradient clipping once per optimizer; `--skip_nonfinite_grads`:
+  a step whose gradient holds an Inf / NaN leaves parameters and Adam moments untouched (docs/design/19-gradient-clipping.md).
 Unsupported Trainer flags are accepted and ignored with a warning, like unknown Lightning flags would be.
 """
 from __future__ import annotations
@@ -58,7 +60,18 @@ def get_parser():
                    help="write picture grids of the model's log_images every N batches to <logdir>/images/<split>/ (0: never; the "
                         "reference's CaptionImageLogger uses 50)")
     p.add_argument("--log_images_max", type=int, default=16, help="images per picture grid (4 per row)")
+    p.add_argument("--gradient_clip_val", type=float, default=0.0,
+                   help="clip the global gradient norm of each optimizer to this value (Lightning's Trainer flag; 0: off).  With -r the "
+                        "value given on this command line applies: it is not stored in the saved configs")
+    p.add_argument("--skip_nonfinite_grads", action="store_true",
+                   help="skip the optimizer step (parameters and Adam moments untouched) when a gradient holds an Inf / NaN")
     return p
+
+
+def split_unknown(unknown):
+    """arguments the parser did not take -> (`key.sub=value` config overrides, Trainer flags that are ignored with a warning)"""
+    dot = [u for u in unknown if "=" in u and not u.startswith("--")]
+    return dot, [u for u in unknown if u not in dot]
 
 
 def _gpu_ids(spec: str, n_visible: int):
@@ -93,8 +106,7 @@ def run(rank, world, opt, unknown):
     rt.set_compute_dtype(opt.precision)
     torch.manual_seed(opt.seed)
 
-    dot = [u for u in unknown if "=" in u and not u.startswith("--")]
-    ignored = [u for u in unknown if u not in dot]
+    dot, ignored = split_unknown(unknown)
     if ignored and rank == 0:
         print(f"[train.py] ignoring unsupported Trainer flags: {ignored}")
     # -r <logdir | checkpoint>: continue IN that logdir with the configs it saved (train.py:73-89 of the reference), -b adds to them
@@ -188,7 +200,8 @@ def run(rank, world, opt, unknown):
         token_iter = _token_batches()
 
     total = model.training_steps if opt.max_steps < 0 else min(opt.max_steps, model.training_steps)
-    trainer = Trainer(model, max_steps=total, log_every=10 if rank == 0 else 0)
+    trainer = Trainer(model, max_steps=total, log_every=10 if rank == 0 else 0, gradient_clip_val=opt.gradient_clip_val,
+                      skip_nonfinite=opt.skip_nonfinite_grads)
     pool = [torch.from_numpy(synth.half_flat_images(bs, size, seed=opt.seed + 977 * rank + i)).to(dev) for i in range(4)]
 
     image_key = getattr(model, "image_key", None) or getattr(model, "first_stage_key", "image")
