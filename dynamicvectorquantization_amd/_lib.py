@@ -168,6 +168,8 @@ SIGNATURES = {
     "dvq_grad_sqnorm_workspace_bytes": (sz, [i64]),
     "dvq_grad_sqnorm": (i32, [vp, i64, f32, i32, vp, sz, vp, vp]),
     "dvq_adamw_clip_dev": (i32, [vp, vp, vp, vp, i64, vp, vp, vp]),
+    "dvq_ema_update": (i32, [vp, vp, i64, vp, vp, vp]),
+    "dvq_swap_f32": (i32, [vp, vp, i64, vp]),
     "dvq_set_f32x8": (i32, [vp, f32, f32, f32, f32, f32, f32, f32, f32, vp]),
     "dvq_sample_rows": (i32, [vp, i64, i64, vp, vp]),
     "dvq_add_uniform": (i32, [vp, i64, f32, vp, vp]),

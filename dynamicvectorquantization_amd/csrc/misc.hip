@@ -1,5 +1,5 @@
 // Small HBM-bound kernels of the DQ-VAE path (gfx950): softmax rows, transposes, dual-grain merge,
-// residual/bias adds, pooling, casts, weight (un)packing, image layout changes, L1 loss, Adam.
+// residual/bias adds, pooling, casts, weight (un)packing, image layout changes, L1 loss, Adam, weight EMA.
 // Each cites the reference call site it replaces in include/dvq_hip.h.
 #include <stdarg.h>
 
@@ -675,6 +675,78 @@ __global__ __launch_bounds__(256) void adam_clip_dev_kernel(float* __restrict__ 
     }
 }
 
+// ---- weight EMA (docs/design/20-weight-ema.md) ----------------------------------------------------------------------------------
+// e <- e - om * (e - p), om = rec[0] = 1 - decay of THIS step, read from device memory like adam_dev_kernel's hyper-parameters (the
+// host forms 1 - d in fp64 and rounds once; a recorded step replays with the current decay).  One rounding for e - p, one fma:
+// p == e gives e back bit for bit.  Elementwise: element i depends on e[i], p[i], om alone -- never on the grid or on arrival order.
+// The guard's skip flag (gstat of grad_sqnorm_final_kernel, may be NULL) returns before any access, as adam_clip_dev_kernel does.
+// VEC: 16-byte accesses, two per thread and array in flight, the n % 4 tail by threads 0..2 of block 0; !VEC: 4-byte accesses.
+__device__ __forceinline__ float ema_elem(float e, float p, float om) { return __builtin_fmaf(-om, e - p, e); }
+
+__device__ __forceinline__ f32x4 ema_vec(f32x4 e, f32x4 p, float om) {
+    return f32x4{ema_elem(e[0], p[0], om), ema_elem(e[1], p[1], om), ema_elem(e[2], p[2], om), ema_elem(e[3], p[3], om)};
+}
+
+template <bool VEC>
+__global__ __launch_bounds__(256) void ema_update_kernel(float* __restrict__ e, const float* __restrict__ p, int64_t n,
+                                                         const float* __restrict__ rec, const int* __restrict__ gstat) {
+    if (gstat != nullptr && gstat[5] != 0) return;
+    const float om = rec[0];
+    const int64_t stride = (int64_t)gridDim.x * 256;
+    int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
+    if (VEC) {
+        const int64_t nvec = n >> 2;
+        f32x4* ev = reinterpret_cast<f32x4*>(e);
+        const f32x4* pv = reinterpret_cast<const f32x4*>(p);
+        for (; i + stride < nvec; i += 2 * stride) {
+            const f32x4 e0 = ev[i], e1 = ev[i + stride], p0 = pv[i], p1 = pv[i + stride];
+            ev[i] = ema_vec(e0, p0, om);
+            ev[i + stride] = ema_vec(e1, p1, om);
+        }
+        if (i < nvec) ev[i] = ema_vec(ev[i], pv[i], om);
+        const int64_t t = 4 * nvec + threadIdx.x;
+        if (blockIdx.x == 0 && threadIdx.x < 3 && t < n) e[t] = ema_elem(e[t], p[t], om);
+    } else {
+        for (; i < n; i += stride) e[i] = ema_elem(e[i], p[i], om);
+    }
+}
+
+// a <-> b in one pass, no third buffer (every element is read into a register before its slot is overwritten); same access scheme
+template <bool VEC>
+__global__ __launch_bounds__(256) void swap_f32_kernel(float* __restrict__ a, float* __restrict__ b, int64_t n) {
+    const int64_t stride = (int64_t)gridDim.x * 256;
+    int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
+    if (VEC) {
+        const int64_t nvec = n >> 2;
+        f32x4* av = reinterpret_cast<f32x4*>(a);
+        f32x4* bv = reinterpret_cast<f32x4*>(b);
+        for (; i + stride < nvec; i += 2 * stride) {
+            const f32x4 a0 = av[i], a1 = av[i + stride], b0 = bv[i], b1 = bv[i + stride];
+            av[i] = b0;
+            av[i + stride] = b1;
+            bv[i] = a0;
+            bv[i + stride] = a1;
+        }
+        if (i < nvec) {
+            const f32x4 a0 = av[i], b0 = bv[i];
+            av[i] = b0;
+            bv[i] = a0;
+        }
+        const int64_t t = 4 * nvec + threadIdx.x;
+        if (blockIdx.x == 0 && threadIdx.x < 3 && t < n) {
+            const float x = a[t], y = b[t];
+            a[t] = y;
+            b[t] = x;
+        }
+    } else {
+        for (; i < n; i += stride) {
+            const float x = a[i], y = b[i];
+            a[i] = y;
+            b[i] = x;
+        }
+    }
+}
+
 struct F32x8 {
     float v[8];
 };
@@ -1148,6 +1220,37 @@ int dvq_adamw_clip_dev(float* p, const float* g, float* m, float* v, int64_t n, 
     adam_clip_dev_kernel<<<dim3(nblocks(n, 1024)), dim3(256), 0, (hipStream_t)stream>>>(p, g, m, v, n, hyper,
                                                                                         (const float*)gstat);
     DVQ_CHECK_LAUNCH("adamw_clip_dev");
+    return DVQ_OK;
+}
+
+static inline bool ranges_overlap_f32(const float* a, const float* b, int64_t n) {
+    const uintptr_t lo = (uintptr_t)a < (uintptr_t)b ? (uintptr_t)a : (uintptr_t)b;
+    const uintptr_t hi = (uintptr_t)a < (uintptr_t)b ? (uintptr_t)b : (uintptr_t)a;
+    return hi - lo < (uintptr_t)n * sizeof(float);
+}
+
+int dvq_ema_update(float* e, const float* p, int64_t n, const float* rec, const void* gstat, dvq_stream_t stream) {
+    DVQ_REQUIRE(e && p && rec && n > 0, DVQ_EINVAL, "dvq_ema_update: bad arguments");
+    DVQ_REQUIRE((((uintptr_t)e | (uintptr_t)p | (uintptr_t)rec | (uintptr_t)gstat) & 3) == 0, DVQ_EINVAL,
+                "dvq_ema_update: e, p, rec and gstat must be 4-byte aligned");
+    DVQ_REQUIRE(!ranges_overlap_f32(e, p, n), DVQ_EINVAL, "dvq_ema_update: e and p overlap");
+    if ((((uintptr_t)e | (uintptr_t)p) & 15) == 0)
+        ema_update_kernel<true><<<dim3(nblocks(n >> 2, 512)), dim3(256), 0, (hipStream_t)stream>>>(e, p, n, rec, (const int*)gstat);
+    else
+        ema_update_kernel<false><<<dim3(nblocks(n, 1024)), dim3(256), 0, (hipStream_t)stream>>>(e, p, n, rec, (const int*)gstat);
+    DVQ_CHECK_LAUNCH("ema_update");
+    return DVQ_OK;
+}
+
+int dvq_swap_f32(float* a, float* b, int64_t n, dvq_stream_t stream) {
+    DVQ_REQUIRE(a && b && n > 0, DVQ_EINVAL, "dvq_swap_f32: bad arguments");
+    DVQ_REQUIRE((((uintptr_t)a | (uintptr_t)b) & 3) == 0, DVQ_EINVAL, "dvq_swap_f32: a and b must be 4-byte aligned");
+    DVQ_REQUIRE(!ranges_overlap_f32(a, b, n), DVQ_EINVAL, "dvq_swap_f32: the two ranges overlap");
+    if ((((uintptr_t)a | (uintptr_t)b) & 15) == 0)
+        swap_f32_kernel<true><<<dim3(nblocks(n >> 2, 512)), dim3(256), 0, (hipStream_t)stream>>>(a, b, n);
+    else
+        swap_f32_kernel<false><<<dim3(nblocks(n, 1024)), dim3(256), 0, (hipStream_t)stream>>>(a, b, n);
+    DVQ_CHECK_LAUNCH("swap_f32");
     return DVQ_OK;
 }
 

@@ -305,9 +305,36 @@ def evaluate_likelihood(model, batches, per_image: bool = False) -> dict:
     return s
 
 
-def load_stage2_model(yaml_path: str, model_path: str = "", device="cuda", seed: int = 0):
-    """the Dualformer of a stage-2 YAML, weights from a checkpoint when given, in eval mode on `device` (seeded initialisation, like
-    load_model).  Returns (model, image size of its first stage)."""
+def checkpoint_state_dict(ckpt, use_ema: bool = False):
+    """the model state dict of a checkpoint: ckpt["state_dict"] of a Lightning-style file, or the bare dict itself.  use_ema: a COPY
+    with the averaged weights ckpt["ema"]["state_dict"] (Trainer(ema_decay=...), docs/design/20-weight-ema.md) laid over it -- exactly
+    the listed names are replaced, everything else (buffers, forward-updated codebooks, frozen parts) stays; the input is not
+    modified.  KeyError when the checkpoint has no "ema" key, or an averaged tensor has no counterpart of its name and shape."""
+    sd = ckpt["state_dict"] if "state_dict" in ckpt else ckpt
+    if not use_ema:
+        return sd
+    ema = ckpt.get("ema") if "state_dict" in ckpt else None
+    if not isinstance(ema, dict) or "state_dict" not in ema:
+        raise KeyError("checkpoint has no \"ema\" key: it was written without --ema_decay (or is an export_ema.py output, whose "
+                       "state_dict already is the averaged model)")
+    out = dict(sd)
+    for name, t in ema["state_dict"].items():
+        if name not in sd:
+            raise KeyError(f"EMA tensor {name!r} has no counterpart in the checkpoint's state_dict")
+        if tuple(t.shape) != tuple(sd[name].shape):
+            raise KeyError(f"EMA tensor {name!r} has shape {tuple(t.shape)}, the state_dict's has {tuple(sd[name].shape)}")
+        out[name] = t
+    return out
+
+
+def load_checkpoint_state_dict(model_path: str, use_ema: bool = False):
+    """checkpoint_state_dict of a file (loaded to the CPU)"""
+    return checkpoint_state_dict(torch.load(model_path, map_location="cpu"), use_ema=use_ema)
+
+
+def load_stage2_model(yaml_path: str, model_path: str = "", device="cuda", seed: int = 0, use_ema: bool = False):
+    """the Dualformer of a stage-2 YAML, weights from a checkpoint when given (use_ema: its averaged weights), in eval mode on
+    `device` (seeded initialisation, like load_model).  Returns (model, image size of its first stage)."""
     from . import config as cfg
     conf = cfg.load_yaml(yaml_path)
     torch.manual_seed(seed)
@@ -315,8 +342,7 @@ def load_stage2_model(yaml_path: str, model_path: str = "", device="cuda", seed:
     if not hasattr(model, "score"):
         raise ValueError(f"{yaml_path}: not a stage-2 (DQ-Transformer) model")
     if model_path:
-        sd = torch.load(model_path, map_location="cpu")
-        model.load_state_dict(sd["state_dict"] if "state_dict" in sd else sd, strict=False)
+        model.load_state_dict(load_checkpoint_state_dict(model_path, use_ema), strict=False)
     fs = conf.model.params.first_stage_config.params
     size = fs.get("image_size") or fs.encoderconfig.params.resolution
     return model.eval().to(device), int(size)
@@ -382,17 +408,16 @@ def image_batches(batch_size: int, size: int, device, images: str | None = None,
         raise ValueError("no image source: give images=<folder|.npy> or synthetic=N")
 
 
-def load_model(yaml_path: str, model_path: str = "", device="cuda", seed: int = 0):
+def load_model(yaml_path: str, model_path: str = "", device="cuda", seed: int = 0, use_ema: bool = False):
     """the model of a stage-1 YAML (config.instantiate_from_config), weights from a checkpoint ({"state_dict": ...} or a bare state
-    dict) when given, in eval mode on `device`.  The initialisation is seeded, so that runs without a checkpoint evaluate the same
+    dict) when given -- with use_ema its averaged weights (checkpoint_state_dict) --, in eval mode on `device`.  The initialisation is seeded, so that runs without a checkpoint evaluate the same
     random weights.  Returns (model, image size)."""
     from . import config as cfg
     conf = cfg.load_yaml(yaml_path)
     torch.manual_seed(seed)
     model = cfg.instantiate_from_config(conf.model)
     if model_path:
-        sd = torch.load(model_path, map_location="cpu")
-        model.load_state_dict(sd["state_dict"] if "state_dict" in sd else sd)
+        model.load_state_dict(load_checkpoint_state_dict(model_path, use_ema))
     params = conf.model.params
     size = int(params.get("image_size", 256)) if hasattr(params, "get") else 256
     return model.eval().to(device), size
@@ -403,6 +428,8 @@ def add_eval_args(ap) -> None:
     --codebook_size) and the image source / compute dtype"""
     ap.add_argument("--yaml_path", type=str, required=True)
     ap.add_argument("--model_path", type=str, default="", help="checkpoint; empty: the YAML's freshly initialised weights")
+    ap.add_argument("--use_ema", action="store_true",
+                    help="evaluate the averaged weights stored under the checkpoint's \"ema\" key (train.py --ema_decay)")
     ap.add_argument("--batch_size", type=int, default=100)
     ap.add_argument("--dataset_type", type=str, default="ffhq", choices=["ffhq", "imagenet"],
                     help="imagenet: $DVQ_IMAGENET_ROOT/val; ffhq needs --images (no FFHQ loader)")

@@ -1240,6 +1240,22 @@ def adamw_clip_dev(p, g, m, v, hyper, gstat):
     check(lib().dvq_adamw_clip_dev(_p(p), _p(g), _p(m), _p(v), p.numel(), _p(hyper), _p(gstat), _s()), "dvq_adamw_clip_dev")
 
 
+def ema_update(e, p, rec, gstat=None):
+    """e <- e - rec[0] * (e - p) over flat fp32 buffers; rec[0] = 1 - decay lives in device memory (replay-safe), gstat: the guard's
+    statistics block or None -- a step the guard skipped leaves e untouched (docs/design/20-weight-ema.md)"""
+    assert e.dtype == torch.float32 and p.dtype == torch.float32 and rec.dtype == torch.float32 and e.numel() == p.numel()
+    assert e.is_contiguous() and p.is_contiguous() and rec.numel() >= 1
+    check(lib().dvq_ema_update(_p(e), _p(p), e.numel(), _p(rec), _p(gstat) if gstat is not None else None, _s()), "dvq_ema_update")
+    return e
+
+
+def swap_f32(a, b):
+    """exchange the contents of two non-overlapping flat fp32 buffers in one launch (no temporary)"""
+    assert a.dtype == torch.float32 and b.dtype == torch.float32 and a.numel() == b.numel()
+    assert a.is_contiguous() and b.is_contiguous()
+    check(lib().dvq_swap_f32(_p(a), _p(b), a.numel(), _s()), "dvq_swap_f32")
+
+
 def set_f32x8(dst, values):
     """dst[0:8] <- values (by-value launch arguments: safe to call with the host running many steps ahead)"""
     vals = [float(x) for x in values] + [0.0] * (8 - len(values))

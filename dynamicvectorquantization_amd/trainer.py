@@ -10,6 +10,7 @@ Covers what train.py + Lightning 1.5.6 do for the DQ-VAE path (train.py:227-270,
 """
 from __future__ import annotations
 
+import contextlib
 import math
 from functools import partial
 
@@ -96,6 +97,15 @@ class FlatParams:
 
 
 # ---- optimizer ------------------------------------------------------------------------------------------
+def ema_decay_at(n, decay, warmup=True):
+    """decay of the n-th weight-EMA update (n = 1 for the first): min(decay, (1 + n) / (10 + n)), the `num_updates` warm-up of
+    tf.train.ExponentialMovingAverage and of taming / latent-diffusion's LitEma; `decay` itself with warmup=False"""
+    n, decay = int(n), float(decay)
+    if not warmup:
+        return decay
+    return min(decay, (1.0 + n) / (10.0 + n))
+
+
 class HipAdam(torch.optim.Optimizer):
     """torch.optim.Adam / AdamW semantics (no amsgrad; `weight_decay` is decoupled like AdamW, 0 = plain Adam).  With
     `flatten()` (done by the Trainer) all parameter groups live in ONE flat buffer pair, each group a contiguous segment
@@ -104,8 +114,50 @@ class HipAdam(torch.optim.Optimizer):
     def __init__(self, params, lr=1e-3, betas=(0.9, 0.999), eps=1e-8, weight_decay=0.0):
         super().__init__(params, dict(lr=lr, betas=betas, eps=eps, weight_decay=weight_decay))
         self.flat = None
+        self.flat_e = None
         self._fstate = None
         self._guard = None            # set_grad_guard: dict(clip, skip, ws, gstat)
+        self._ema = None              # set_weight_ema: dict(decay, warmup, rec, last); the shadow buffer is self.flat_e
+
+    def set_weight_ema(self, decay=0.0, warmup=True):
+        """Exponential moving average of this optimizer's parameters (docs/design/20-weight-ema.md): after every step()
+        flat_e <- flat_e - (1 - d_n) * (flat_e - flat_p), d_n = ema_decay_at(n, decay, warmup), one launch over the whole flat buffer.
+        decay == 0 switches it off and frees the shadow buffer.  `1 - d_n` is uploaded by prepare_step() into a device record, so a
+        recorded step follows the schedule; with a grad guard set, a skipped step leaves flat_e untouched too (the update count still
+        advances, like Adam's step count).  The buffers are allocated here, never inside step()."""
+        decay = float(decay)
+        if not (math.isfinite(decay) and 0.0 <= decay < 1.0):
+            raise ValueError(f"EMA decay must be finite and in [0, 1) (0 = off), got {decay}")
+        if self.flat is None:
+            raise ValueError("set_weight_ema works on a flattened HipAdam only (call flatten() first): the per-tensor path has no "
+                             "single parameter buffer to average")
+        if decay == 0.0:
+            self._ema, self.flat_e = None, None
+            self._fstate.pop("ema_updates", None)
+            return
+        old = self._ema
+        if old is None:
+            self.flat_e = self.flat.flat_p.clone()
+            self._fstate["ema_updates"] = 0
+        self._ema = {"decay": decay, "warmup": bool(warmup), "last": None,
+                     "rec": old["rec"] if old else torch.zeros(8, dtype=torch.float32, device=self.flat.flat_p.device)}
+        self._prepared = False
+
+    @property
+    def ema_num_updates(self):
+        """EMA updates applied so far (0 with the feature off)"""
+        return int(self._fstate.get("ema_updates", 0)) if self._fstate else 0
+
+    def ema_tensors(self):
+        """{id(p): view of the shadow buffer with p's logical shape} (FlatParams._view: a channel-last-stored conv weight comes out
+        [Cout, Cin, KH, KW]); {} with the feature off"""
+        if self._ema is None:
+            return {}
+        out, off = {}, 0
+        for p in self.flat.params:
+            out[id(p)] = FlatParams._view(self.flat_e, off, p)
+            off += p.numel()
+        return out
 
     def set_grad_guard(self, clip_val=0.0, skip_nonfinite=False):
         """Global-norm gradient clipping (torch.nn.utils.clip_grad_norm_ over ALL parameter groups of this optimizer, as Lightning's
@@ -165,6 +217,10 @@ class HipAdam(torch.optim.Optimizer):
             lr = float(g["lr"])
             bc1, bc2 = 1.0 - b1 ** t, 1.0 - b2 ** t
             K.set_f32x8(self._hyper[gi], [lr / bc1, b1, b2, g["eps"], 1.0 / math.sqrt(bc2), 1.0 - lr * g.get("weight_decay", 0.0)])
+        em = self._ema
+        if em is not None:                 # 1 - d of the NEXT EMA update, in fp64 here, rounded to fp32 once on its way to the device
+            em["last"] = ema_decay_at(self._fstate["ema_updates"] + 1, em["decay"], em["warmup"])
+            K.set_f32x8(em["rec"], [1.0 - em["last"]])
         self._prepared = True
 
     @torch.no_grad()
@@ -186,6 +242,9 @@ class HipAdam(torch.optim.Optimizer):
                     K.adamw_clip_dev(self.flat.flat_p[sl], self.flat.flat_g[sl], st["m"][sl], st["v"][sl], self._hyper[gi], gd["gstat"])
                 else:
                     K.adamw_dev(self.flat.flat_p[sl], self.flat.flat_g[sl], st["m"][sl], st["v"][sl], self._hyper[gi])
+            if self._ema is not None:      # ONE launch over the whole buffer (all groups), after Adam; follows the guard's skip
+                K.ema_update(self.flat_e, self.flat.flat_p, self._ema["rec"], gd["gstat"] if gd is not None else None)
+                st["ema_updates"] += 1
             rt.bump_group_epoch(id(self))      # only this optimizer's packed weights are stale
             return
         for group in self.param_groups:
@@ -389,7 +448,8 @@ class Trainer:
     stay eager between segments, the optimizer reads its hyper-parameters from device memory, batches are copied into
     static input buffers.  `DVQ_STEP_GRAPH=0` (or use_graph=False) keeps every step eager."""
 
-    def __init__(self, model, max_steps, log_every=0, use_graph=None, graph_after=3, gradient_clip_val=0.0, skip_nonfinite=False):
+    def __init__(self, model, max_steps, log_every=0, use_graph=None, graph_after=3, gradient_clip_val=0.0, skip_nonfinite=False,
+                 ema_decay=0.0, ema_warmup=True):
         self.model, self.max_steps, self.log_every = model, max_steps, log_every
         self.opts, self.scheds = model.configure_optimizers()
         self.buckets = [GradBuckets(o.flatten()) for o in self.opts]
@@ -399,7 +459,15 @@ class Trainer:
         if self.gradient_clip_val != 0.0 or self.skip_nonfinite:
             for o in self.opts:
                 o.set_grad_guard(self.gradient_clip_val, self.skip_nonfinite)
+        # weight EMA (docs/design/20-weight-ema.md): shadow weights of optimizer 0 -- the autoencoder in stage 1, the transformer in
+        # stage 2 -- for validation, checkpoints and the tools; an averaged discriminator has no use.  Off (the default): no buffer,
+        # no launch, the checkpoint as ever
+        self.ema_decay, self.ema_warmup = float(ema_decay), bool(ema_warmup)
+        self._in_ema_scope = False
+        self._warned_no_ema = False
         broadcast_model(model)             # identical start on every rank (DDP's parameter / buffer broadcast), not just equal seeds
+        if self.ema_decay != 0.0:          # after the broadcast: flat_e starts as a copy of the weights every rank holds
+            self.opts[0].set_weight_ema(self.ema_decay, self.ema_warmup)
         self.check_every = int(rt.switch("DVQ_DP_CHECK_EVERY"))
         import inspect
         # Lightning passes optimizer_idx only to modules that declare it (two-optimizer stage 1); stage 2 has one optimizer
@@ -414,6 +482,8 @@ class Trainer:
 
     # ---- one step ------------------------------------------------------------------------------------------------
     def train_step(self, batch, batch_idx):
+        if self._in_ema_scope:
+            raise RuntimeError("train_step inside ema_scope(): the parameters hold the averaged weights, a step would train those")
         out = self._train_step(batch, batch_idx)
         if self.check_every and (int(self.model.global_step) % self.check_every) == 0 and not replicas_equal(self.model):
             raise RuntimeError(f"data-parallel replicas diverged at global step {self.model.global_step}")
@@ -484,16 +554,21 @@ class Trainer:
                 items.append((k, repr(v)))
         world = dist.get_world_size() if dist.is_available() and dist.is_initialized() else 1
         guard = (self.gradient_clip_val, self.skip_nonfinite)           # launch arguments of the recorded norm kernels
-        return (tuple(items), bool(m.training), rt.compute_dtype(), rt.impl(), rt.fuse_gn_prologue(), world, extra, guard)
+        sig = (tuple(items), bool(m.training), rt.compute_dtype(), rt.impl(), rt.fuse_gn_prologue(), world, extra, guard)
+        # whether the EMA launch is part of the step; the decay is device data and not part of the signature
+        return sig + (("ema",) if self.ema_enabled else ())
 
     def _py_state(self):
         return ([o._fstate["step"] for o in self.opts], [s["scheduler"].state_dict() for s in self.scheds],
-                [[g["lr"] for g in o.param_groups] for o in self.opts], int(self.model.global_step))
+                [[g["lr"] for g in o.param_groups] for o in self.opts], int(self.model.global_step),
+                [o._fstate.get("ema_updates") for o in self.opts])
 
     def _set_py_state(self, st):
-        steps, scheds, lrs, gstep = st
-        for o, t, lr in zip(self.opts, steps, lrs):
+        steps, scheds, lrs, gstep, ema_counts = st
+        for o, t, lr, ne in zip(self.opts, steps, lrs, ema_counts):
             o._fstate["step"] = t
+            if ne is not None:             # the capture's dry run counted an EMA update that did not happen
+                o._fstate["ema_updates"] = ne
             for g, v in zip(o.param_groups, lr):
                 g["lr"] = v
         for s, sd in zip(self.scheds, scheds):
@@ -538,6 +613,8 @@ class Trainer:
         # host-side bookkeeping the recorded launches do not carry
         for o, sc in zip(self.opts, self.scheds):
             o._fstate["step"] += 1
+            if o._ema is not None:
+                o._fstate["ema_updates"] += 1
             o._prepared = False
             sc["scheduler"].step()
             # the replay rewrote this optimizer's parameters: whatever an EAGER forward (eval / encode / validation_step) packed
@@ -566,6 +643,52 @@ class Trainer:
         """one {"norm", "coef", "finite", "skipped"} per optimizer (None for one without clipping / guard), of the last step --
         eager or replayed.  A host read: outside the step only."""
         return [o.grad_stats() if getattr(o, "_guard", None) is not None else None for o in self.opts]
+
+    # ---- weight EMA ------------------------------------------------------------------------------------------------
+    @property
+    def ema_enabled(self):
+        return getattr(self.opts[0], "_ema", None) is not None
+
+    def set_weight_ema(self, ema_decay=0.0, ema_warmup=True):
+        """switch the weight EMA of optimizer 0 between steps (0 = off: the shadow buffer is freed; on again: it starts from the
+        current weights).  A step recorded under the other setting is not replayed: the signature differs"""
+        if self._in_ema_scope:
+            raise RuntimeError("set_weight_ema inside ema_scope()")
+        self.opts[0].set_weight_ema(ema_decay, ema_warmup)
+        self.ema_decay, self.ema_warmup = float(ema_decay), bool(ema_warmup)
+
+    def _swap_ema(self):
+        o = self.opts[0]
+        K.swap_f32(o.flat.flat_p, o.flat_e)
+        rt.bump_group_epoch(id(o))         # whatever was packed or prepared from these parameters is stale
+        rt.bump_codebook_epoch()
+
+    @contextlib.contextmanager
+    def ema_scope(self):
+        """look through the averaged weights: the contents of flat_p and flat_e are exchanged on entry and exchanged back on exit
+        (also when the body raises).  Every Parameter.data is a view of flat_p, so no pointer moves and a recorded step stays
+        valid; the exchange is exact, so the training weights come back bit for bit.  Tensors the forward pass updates (the EMA
+        codebook, BatchNorm statistics) are not averaged: the model sees their live values.  No-op with the feature off."""
+        if not self.ema_enabled:
+            yield self
+            return
+        if self._in_ema_scope:
+            raise RuntimeError("ema_scope() does not nest")
+        if rt.capturing():
+            raise RuntimeError("ema_scope() inside a step capture")
+        self._swap_ema()
+        self._in_ema_scope = True
+        try:
+            yield self
+        finally:
+            self._in_ema_scope = False
+            self._swap_ema()
+
+    def _ema_state_dict(self):
+        """{name: cpu tensor} of the averaged parameters under the names of model.state_dict(), contiguous in logical shape"""
+        views = self.opts[0].ema_tensors()
+        names = {id(t): k for k, t in self.model.state_dict(keep_vars=True).items()}
+        return {names[i]: v.detach().cpu().contiguous().clone() for i, v in views.items() if i in names}
 
     def _arm_overlap(self, oi):
         """Gradient exchange overlapped with the backward: every module of the model that declares `_grad_hook` calls it with the
@@ -643,6 +766,12 @@ class Trainer:
               "lr_schedulers": [s["scheduler"].state_dict() for s in self.scheds]}
         if self.grad_guard_enabled:          # only then: a run without the feature writes the checkpoint it always wrote
             sd["grad_guard"] = {"skipped": [(st["skipped"] if st else 0) for st in self.grad_stats()]}
+        if self.ema_enabled:                 # likewise; the reference's loaders read ["state_dict"] only
+            if self._in_ema_scope:
+                raise RuntimeError("state_dict() inside ema_scope(): live and averaged weights are exchanged")
+            o = self.opts[0]
+            sd["ema"] = {"decay": float(o._ema["decay"]), "warmup": bool(o._ema["warmup"]), "num_updates": o.ema_num_updates,
+                         "state_dict": self._ema_state_dict()}
         return sd
 
     @torch.no_grad()
@@ -675,6 +804,31 @@ class Trainer:
             for o, n in zip(self.opts, skipped):
                 if getattr(o, "_guard", None) is not None:
                     o._guard["gstat"][4] = int(n)
+        # weight EMA: the shadow weights are restored through the views and the count with them; the decay of THIS run applies (as
+        # with the clipping flags).  A checkpoint written without the feature: the average starts from the loaded weights
+        if self.ema_enabled:
+            o = self.opts[0]
+            o.flat_e.copy_(o.flat.flat_p)
+            o._fstate["ema_updates"] = 0
+            o._prepared = False
+            ema = ckpt.get("ema")
+            if ema is None:
+                if not self._warned_no_ema:
+                    import warnings
+                    warnings.warn("checkpoint has no \"ema\" key: the weight EMA starts from the loaded weights, update count 0")
+                    self._warned_no_ema = True
+            else:
+                names = {id(t): k for k, t in self.model.state_dict(keep_vars=True).items()}
+                for i, view in o.ema_tensors().items():
+                    t = ema["state_dict"].get(names.get(i))
+                    if t is None:
+                        if strict:
+                            raise KeyError(f"checkpoint's EMA state lacks parameter {names.get(i)!r}")
+                        continue
+                    if tuple(t.shape) != tuple(view.shape):
+                        raise ValueError(f"EMA state of {names[i]}: shape {tuple(t.shape)} != {tuple(view.shape)}")
+                    view.copy_(t.to(view.device))
+                o._fstate["ema_updates"] = int(ema.get("num_updates", 0))
 
     def save_checkpoint(self, path):
         """atomic write (temp file + rename): a crash while saving never destroys the previous last.ckpt"""
@@ -695,15 +849,16 @@ class Trainer:
         m.eval()
         sums, n = {}, 0
         try:
-            for i, b in enumerate(batches):
-                m._logged = {}
-                m.validation_step(b, i)
-                if image_logger is not None:
-                    image_logger.maybe_log(m, b, i, split="val")
-                for k, v in m._logged.items():
-                    if torch.is_tensor(v) and v.numel() == 1 or isinstance(v, (int, float)):
-                        sums[k] = sums.get(k, 0.0) + (v.detach().double() if torch.is_tensor(v) else float(v))
-                n += 1
+            with self.ema_scope():           # weight EMA on: metrics and pictures of the averaged model; a no-op otherwise
+                for i, b in enumerate(batches):
+                    m._logged = {}
+                    m.validation_step(b, i)
+                    if image_logger is not None:
+                        image_logger.maybe_log(m, b, i, split="val")
+                    for k, v in m._logged.items():
+                        if torch.is_tensor(v) and v.numel() == 1 or isinstance(v, (int, float)):
+                            sums[k] = sums.get(k, 0.0) + (v.detach().double() if torch.is_tensor(v) else float(v))
+                    n += 1
         finally:
             m.train(was_training)
             m._logged = {}
@@ -747,7 +902,7 @@ class Trainer:
             metrics = self.validate(val_fn(), image_logger=image_logger if is_rank0 else None)
             self.last_val_metrics = metrics
             if is_rank0 and metrics:
-                print(f"validation @ step {step + 1}: " + " ".join(f"{k}={v:.5f}" for k, v in metrics.items()), flush=True)
+                print(f"validation @ step {step + 1}{' (EMA weights)' if self.ema_enabled else ''}: " + " ".join(f"{k}={v:.5f}" for k, v in metrics.items()), flush=True)
             if not (ckpt_path and is_rank0 and save_top_k and monitor and monitor in metrics):
                 return
             val = metrics[monitor]
@@ -775,6 +930,8 @@ class Trainer:
                     if self.grad_guard_enabled:
                         line += "".join(f" | opt{i} gnorm={st['norm']:.4g} coef={st['coef']:.4g} skipped={st['skipped']}"
                                         for i, st in enumerate(self.grad_stats()) if st)
+                    if self.ema_enabled:                  # host-side value of the step just taken: no device read
+                        line += f" | ema_d={self.opts[0]._ema['last']:.6g}"
                     print(line, flush=True)
                 if ckpt_path and save_every and is_rank0 and (step + 1) % save_every == 0 and step + 1 < self.max_steps:
                     self.save_checkpoint(ckpt_path)

@@ -626,6 +626,15 @@ int dvq_grad_sqnorm(const float* g, int64_t n, float clip, int skip_nonfinite, v
  * With coef == 1 the results are bit-identical to dvq_adamw_dev. */
 int dvq_adamw_clip_dev(float* p, const float* g, float* m, float* v, int64_t n, const float* hyper, const void* gstat,
                        dvq_stream_t stream);
+/* Weight EMA (shadow weights for evaluation, tf.train.ExponentialMovingAverage / taming's LitEma; docs/design/20-weight-ema.md):
+ *   e[i] <- e[i] - om * (e[i] - p[i]),  om = rec[0] = 1 - decay of this step, READ FROM DEVICE MEMORY (rec: 8 floats, [0] used), so a
+ * step captured as a hipGraph replays with the decay of the current step.  The host forms 1 - decay in fp64 and rounds it once.
+ * gstat: NULL, or the statistics block of dvq_grad_sqnorm -- when its skip field is set the kernel returns before touching memory,
+ * like dvq_adamw_clip_dev.  16-byte accesses when e and p are both 16-byte aligned, 4-byte ones otherwise.  No atomics; equal
+ * inputs give bit-equal outputs on every launch; p == e leaves e bit for bit.  e and p must not overlap. */
+int dvq_ema_update(float* e, const float* p, int64_t n, const float* rec, const void* gstat, dvq_stream_t stream);
+/* exchange the contents of two non-overlapping fp32 buffers in one launch, without a third buffer (overlap: DVQ_EINVAL) */
+int dvq_swap_f32(float* a, float* b, int64_t n, dvq_stream_t stream);
 /* dst[0..7] <- the eight scalars (passed by value in the launch: no pageable host copy, no host buffer to keep alive) */
 int dvq_set_f32x8(float* dst, float v0, float v1, float v2, float v3, float v4, float v5, float v6, float v7,
                   dvq_stream_t stream);

@@ -2,6 +2,7 @@
 """Unconditional sampling to PNG files -- the reference's scripts/sample_images/sample_dynamic_uncond.py (:21-102): the same sampler
 and flags as scripts/sample_val/sample_dynamic_uncond.py, but every sample is written as its own min-max normalised image
 `<out>/[fixed_]TopK-..._image/batch_<i>_<j>.png` (torchvision.utils.save_image(..., normalize=True) there) and no pickles.
+`--use_ema` samples from the averaged weights of a checkpoint trained with `train.py --ema_decay`, as in the twin script.
 
     python scripts/sample_images/sample_dynamic_uncond.py --yaml_path configs/stage2/uncond_imagenet_p6c18.yml \\
         --model_path last.ckpt --batch_size 50 --sample_num 500 --top_k 300 --top_k_pos 1024

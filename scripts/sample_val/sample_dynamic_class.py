@@ -93,8 +93,8 @@ def main():
     if not hasattr(model, "guided_conditioning"):
         raise SystemExit(f"{opt.yaml_path}: not a class-conditional model")
     if opt.model_path:
-        sd = torch.load(opt.model_path, map_location="cpu")
-        model.load_state_dict(sd["state_dict"] if "state_dict" in sd else sd)
+        from dynamicvectorquantization_amd.evaluate import load_checkpoint_state_dict
+        model.load_state_dict(load_checkpoint_state_dict(opt.model_path, opt.use_ema))
     model = model.eval().cuda()
     classes = parse_classes(opt.classes, model.n_classes)
     labels = np.repeat(np.asarray(classes, dtype=np.int64), opt.per_class)

@@ -41,6 +41,8 @@ def get_parser():
     parser = argparse.ArgumentParser()
     parser.add_argument("--yaml_path", type=str, default="")
     parser.add_argument("--model_path", type=str, default="")
+    parser.add_argument("--use_ema", action="store_true", default=False,
+                        help="sample from the averaged weights under the checkpoint's \"ema\" key (train.py --ema_decay)")
     parser.add_argument("--sample_with_fixed_pos", action="store_true", default=False)
     parser.add_argument("--save_image", action="store_true", default=False)
     parser.add_argument("--batch_size", type=int, default=50)
@@ -91,8 +93,8 @@ def main(per_image_png=False):
         torch.manual_seed(opt.seed)
     model = cfg.instantiate_from_config(cfg.load_yaml(opt.yaml_path).model)
     if opt.model_path:
-        sd = torch.load(opt.model_path, map_location="cpu")
-        model.load_state_dict(sd["state_dict"] if "state_dict" in sd else sd)
+        from dynamicvectorquantization_amd.evaluate import load_checkpoint_state_dict
+        model.load_state_dict(load_checkpoint_state_dict(opt.model_path, opt.use_ema))
     model = model.eval().cuda()
 
     total_batch = (opt.sample_num + opt.batch_size - 1) // opt.batch_size

@@ -27,7 +27,7 @@ def main():
     source = E.image_source(opt, ap)
     from dynamicvectorquantization_amd import runtime as rt
     rt.set_compute_dtype(opt.dtype)
-    model, size = E.load_model(opt.yaml_path, opt.model_path, "cuda")
+    model, size = E.load_model(opt.yaml_path, opt.model_path, "cuda", use_ema=opt.use_ema)
     k = codebook_of(model.quantize)[1]
     if opt.codebook_size is not None and opt.codebook_size != k:
         print(f"warning: --codebook_size {opt.codebook_size} differs from the model's {k} codes", file=sys.stderr)

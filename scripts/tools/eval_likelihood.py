@@ -77,7 +77,7 @@ def main():
     import numpy as np
     from dynamicvectorquantization_amd import runtime as rt
     rt.set_compute_dtype(opt.dtype)
-    model, size = E.load_stage2_model(opt.yaml_path, opt.model_path, "cuda")
+    model, size = E.load_stage2_model(opt.yaml_path, opt.model_path, "cuda", use_ema=opt.use_ema)
     if opt.tokens:
         from dynamicvectorquantization_amd import tokens as T
         ds = T.TokenShardDataset(opt.tokens)

@@ -35,7 +35,7 @@ def main():
     source = E.image_source(opt, ap)
     from dynamicvectorquantization_amd import runtime as rt
     rt.set_compute_dtype(opt.dtype)
-    model, size = E.load_model(opt.yaml_path, opt.model_path, "cuda")
+    model, size = E.load_model(opt.yaml_path, opt.model_path, "cuda", use_ema=opt.use_ema)
     on_batch = None
     if opt.dump_dir:
         from PIL import Image

@@ -53,7 +53,7 @@ def parse_views(spec, ap):
     return views
 
 
-def load_first_stage(yaml_path, model_path, device):
+def load_first_stage(yaml_path, model_path, device, use_ema=False):
     """the DQ-VAE of a stage-1 YAML, or of a stage-2 YAML's first_stage_config (a stage-2 checkpoint's first_stage_model.* entries
     load too).  -> (model in eval mode, image size)"""
     import torch
@@ -66,8 +66,7 @@ def load_first_stage(yaml_path, model_path, device):
     torch.manual_seed(0)
     model = cfg.instantiate_from_config(mconf)
     if model_path:
-        sd = torch.load(model_path, map_location="cpu")
-        sd = sd["state_dict"] if "state_dict" in sd else sd
+        sd = E.load_checkpoint_state_dict(model_path, use_ema)
         inner = {k[len("first_stage_model."):]: v for k, v in sd.items() if k.startswith("first_stage_model.")}
         model.load_state_dict(inner or sd)
     size = mconf.params.get("image_size") or mconf.params.encoderconfig.params.resolution
@@ -140,7 +139,7 @@ def main():
     from dynamicvectorquantization_amd import runtime as rt
     rt.set_compute_dtype(opt.dtype)
     dev = torch.device("cuda")
-    model, size = load_first_stage(opt.yaml_path, opt.model_path, dev)
+    model, size = load_first_stage(opt.yaml_path, opt.model_path, dev, use_ema=opt.use_ema)
     hw1, hw2 = T.first_stage_grid(model, size, dev)
 
     ds = None

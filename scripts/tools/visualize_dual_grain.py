@@ -20,6 +20,7 @@ def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--yaml_path", type=str, required=True)
     ap.add_argument("--model_path", type=str, default="")
+    ap.add_argument("--use_ema", action="store_true", help="the averaged weights under the checkpoint's \"ema\" key (train.py --ema_decay)")
     ap.add_argument("--batch_size", type=int, default=4)
     ap.add_argument("--image_save_path", type=str, default="")
     ap.add_argument("--images", type=str, default=None)
@@ -34,8 +35,8 @@ def main():
     conf = cfg.load_yaml(opt.yaml_path)
     model = cfg.instantiate_from_config(conf.model)
     if opt.model_path:
-        sd = torch.load(opt.model_path, map_location="cpu")
-        model.load_state_dict(sd["state_dict"] if "state_dict" in sd else sd)
+        from dynamicvectorquantization_amd.evaluate import load_checkpoint_state_dict
+        model.load_state_dict(load_checkpoint_state_dict(opt.model_path, opt.use_ema))
     model = model.eval().cuda()
     size = int(conf.model.params.get("image_size", 256)) if hasattr(conf.model.params, "get") else 256
     if opt.synthetic > 0:

@@ -13,6 +13,8 @@ path, without pytorch_lightning / OmegaConf:
   `data:` section is instantiated only when its target is importable.
 * `--gradient_clip_val X` (Lightning's Trainer flag): global-norm gradient clipping once per optimizer; `--skip_nonfinite_grads`:
   a step whose gradient holds an Inf / NaN leaves parameters and Adam moments untouched (docs/design/19-gradient-clipping.md).
+* `--ema_decay D` (0: off): an exponential moving average of the weights of optimizer 0, used for validation and stored under the
+  checkpoint's "ema" key; `--ema_no_warmup` drops the (1 + n) / (10 + n) warm-up of the decay (docs/design/20-weight-ema.md).
 Unsupported Trainer flags are accepted and ignored with a warning, like unknown Lightning flags would be.
 """
 from __future__ import annotations
@@ -65,6 +67,12 @@ def get_parser():
                         "value given on this command line applies: it is not stored in the saved configs")
     p.add_argument("--skip_nonfinite_grads", action="store_true",
                    help="skip the optimizer step (parameters and Adam moments untouched) when a gradient holds an Inf / NaN")
+    p.add_argument("--ema_decay", type=float, default=0.0,
+                   help="decay of the weight EMA of optimizer 0 (autoencoder / transformer), e.g. 0.9999; 0: off.  Validation and the "
+                        "monitored checkpoints then use the averaged weights, the checkpoint stores them under \"ema\".  With -r the "
+                        "value given on this command line applies")
+    p.add_argument("--ema_no_warmup", action="store_true",
+                   help="use --ema_decay from the first update on, without the min(decay, (1 + n) / (10 + n)) warm-up")
     return p
 
 
@@ -201,7 +209,7 @@ def run(rank, world, opt, unknown):
 
     total = model.training_steps if opt.max_steps < 0 else min(opt.max_steps, model.training_steps)
     trainer = Trainer(model, max_steps=total, log_every=10 if rank == 0 else 0, gradient_clip_val=opt.gradient_clip_val,
-                      skip_nonfinite=opt.skip_nonfinite_grads)
+                      skip_nonfinite=opt.skip_nonfinite_grads, ema_decay=opt.ema_decay, ema_warmup=not opt.ema_no_warmup)
     pool = [torch.from_numpy(synth.half_flat_images(bs, size, seed=opt.seed + 977 * rank + i)).to(dev) for i in range(4)]
 
     image_key = getattr(model, "image_key", None) or getattr(model, "first_stage_key", "image")
