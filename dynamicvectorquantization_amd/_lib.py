@@ -10,6 +10,9 @@ HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.path.join(HERE, "libdvq_hip_probes.so" if os.environ.get("DVQ_USE_PROBES_LIB", "0") == "1" else "libdvq_hip.so")
 
 F32, BF16 = 0, 1
+# DVQ_IMPL_* of include/dvq_hip.h: kernel choice of ConvDesc.impl, dvq_gemm_nt and dvq_gemm_tn
+(IMPL_AUTO, IMPL_NAIVE, IMPL_MFMA, IMPL_REGSTAGE, IMPL_HALO, IMPL_WIDE, IMPL_WIDE_PIPE, IMPL_WIDE_PIPE_4WAVE, IMPL_WIDE_PIPE_192,
+ IMPL_CONV_PIPE, IMPL_8PHASE) = range(11)
 
 vp, i64, i32, f32, sz = C.c_void_p, C.c_int64, C.c_int32, C.c_float, C.c_size_t
 
@@ -65,10 +68,8 @@ SIGNATURES = {
     "dvq_gn_bwd_partial_bytes": (sz, [i64, i64, i64]),
     "dvq_gn_bwd_reduce": (i32, [vp, vp, i32, i64, i64, i64, i32, vp, vp, vp, i32, vp, vp, vp, vp, vp]),
     "dvq_gn_bwd_dx": (i32, [vp, vp, i32, i64, i64, i64, i32, vp, vp, vp, i32, vp, vp, vp, vp]),
-    "dvq_conv2d_fwd": (i32, [C.POINTER(ConvDesc), vp, vp, vp, vp, vp, vp]),
+    "dvq_conv2d_fwd": (i32, [C.POINTER(ConvDesc), vp, vp, vp, vp, vp, vp, vp, i32, i32, vp]),
     "dvq_conv3x3_fused_ok": (i32, [C.POINTER(ConvDesc)]),
-    "dvq_conv2d_fwd_ex": (i32, [C.POINTER(ConvDesc), vp, vp, vp, vp, vp, vp, vp, i32, vp]),
-    "dvq_conv2d_wgrad_oihw_ex": (i32, [C.POINTER(ConvDesc), vp, vp, i64, i64, vp, vp, i32, vp, vp]),
     "dvq_split_bf16_planes": (i32, [vp, vp, vp, i64, i64, i64, vp]),
     "dvq_conv3x3_x3_ok": (i32, [C.POINTER(ConvDesc), i32]),
     "dvq_conv3x3_x3_scratch_bytes": (i64, [C.POINTER(ConvDesc), i32]),
@@ -77,9 +78,7 @@ SIGNATURES = {
     "dvq_conv2d_wgrad_x3_scratch_bytes": (i64, [C.POINTER(ConvDesc)]),
     "dvq_conv2d_wgrad_oihw_x3": (i32, [C.POINTER(ConvDesc), vp, vp, i64, i64, vp, vp, i32, vp, i64, vp]),
     "dvq_gn_scale_shift": (i32, [vp, vp, vp, i64, i64, i64, i32, f32, vp, vp, vp]),
-    "dvq_conv2d_dgrad": (i32, [C.POINTER(ConvDesc), vp, vp, vp, vp, vp]),
-    "dvq_conv2d_fwd_act": (i32, [C.POINTER(ConvDesc), vp, vp, vp, vp, i32, vp]),
-    "dvq_conv2d_dgrad_mask": (i32, [C.POINTER(ConvDesc), vp, vp, vp, vp, vp, i32, vp]),
+    "dvq_conv2d_dgrad": (i32, [C.POINTER(ConvDesc), vp, vp, vp, vp, vp, i32, vp]),
     "dvq_set_workspace": (i32, [vp, i64]),
     "dvq_workspace_release": (i32, [vp]),
     "dvq_cmdlist_create": (i32, [vp, C.POINTER(vp)]),
@@ -105,8 +104,7 @@ SIGNATURES = {
     "dvq_maxpool2x2_relu_bwd": (i32, [vp, vp, vp, i32, i64, i64, i64, i64, vp, vp]),
     "dvq_lpips_head": (i32, [vp, vp, vp, i32, i64, i64, i64, vp, f32, vp, vp]),
     "dvq_lpips_head_drop": (i32, [vp, vp, vp, i32, i64, i64, i64, vp, f32, vp, f32, C.c_uint64, vp]),
-    "dvq_conv2d_wgrad": (i32, [C.POINTER(ConvDesc), vp, vp, vp, vp, vp]),
-    "dvq_conv2d_wgrad_oihw": (i32, [C.POINTER(ConvDesc), vp, vp, i64, i64, vp, vp, i32, vp]),
+    "dvq_conv2d_wgrad": (i32, [C.POINTER(ConvDesc), vp, vp, i64, i64, vp, vp, i32, vp, vp]),
     "dvq_pack_weights_multi": (i32, [vp, i64, i64, vp]),
     "dvq_linear_pack_multi": (i32, [vp, i64, i64, vp]),
     "dvq_pack_weight": (i32, [vp, i64, i64, i64, i64, i64, i64, i32, vp, vp, vp]),
@@ -114,9 +112,7 @@ SIGNATURES = {
     "dvq_nchw_to_nhwc_pad": (i32, [vp, i64, i64, i64, i64, i64, i32, vp, vp]),
     "dvq_nhwc_pad_to_nchw": (i32, [vp, i32, i64, i64, i64, i64, i64, vp, vp]),
     "dvq_gemm_nt": (i32, [vp, vp, vp, i32, i64, i64, i64, i64, i64, i64, i64, i64, i64, i64, f32, vp, i32, i32, vp]),
-    "dvq_gemm_nt_res": (i32, [vp, vp, vp, vp, i32, i64, i64, i64, i64, i64, i64, i64, i64, i64, i64, f32, vp, i32, vp]),
-    "dvq_gemm_tn": (i32, [vp, vp, vp, i32, i64, i64, i64, i64, i64, i64, i64, i64, i64, i64, i32, vp]),
-    "dvq_gemm_tn_colsum": (i32, [vp, vp, vp, vp, i32, i64, i64, i64, i64, i64, i64, i32, vp]),
+    "dvq_gemm_tn": (i32, [vp, vp, vp, vp, i32, i64, i64, i64, i64, i64, i64, i64, i64, i64, i64, i32, vp]),
     "dvq_softmax_rows": (i32, [vp, i32, i64, i64, f32, vp, vp]),
     "dvq_softmax_rows_bwd": (i32, [vp, vp, i32, i64, i64, f32, vp, vp]),
     "dvq_transpose": (i32, [vp, i32, i64, i64, i64, vp, vp]),

@@ -2648,7 +2648,7 @@ __global__ __launch_bounds__(64 * NW) void gemm_nt_skinny_kernel(NtParams p) {
 }
 
 // -------------------------------------------------------------------------------------------------
-// naive kernels (any shape; used for validation, tiny shapes and as the loud fallback of impl=1)
+// naive kernels (any shape; used for validation, tiny shapes and as the loud fallback of DVQ_IMPL_NAIVE)
 // -------------------------------------------------------------------------------------------------
 template <typename T>
 __global__ void naive_nt_kernel(NtParams p) {
@@ -2745,177 +2745,239 @@ __global__ void naive_tn_kernel(TnParams p) {
 }
 
 // -------------------------------------------------------------------------------------------------
-// launch helpers
+// launch helpers: per kernel an eligibility predicate and a launcher; launch_nt / launch_tn try the kernels in priority order
 // -------------------------------------------------------------------------------------------------
+// preferred impl codes (include/dvq_hip.h) ask for a kernel and take the automatic choice on a shape that kernel does not run
+bool impl_preferred(int impl) {
+    return impl == DVQ_IMPL_WIDE || impl == DVQ_IMPL_WIDE_PIPE || impl == DVQ_IMPL_WIDE_PIPE_4WAVE || impl == DVQ_IMPL_WIDE_PIPE_192 ||
+           impl == DVQ_IMPL_8PHASE;
+}
+
+// every MFMA kernel: whole vectors along K on both operands
+template <typename T>
+bool nt_mfma_ok(const NtParams& p) {
+    constexpr int VN = Vec<T>::N;
+    bool mfma_ok = p.Ktot % VN == 0 && p.ldb % VN == 0 && p.lda % VN == 0 && (p.stride == 1 || p.stride == 2);
+    if (p.mode == MODE_GEMM) mfma_ok = mfma_ok && (p.sA % VN == 0) && (p.sB % VN == 0);
+    return mfma_ok;
+}
+
+// The four 256-wide kernels (bf16, nt_mfma_ok shapes): plain GEMMs under every code that reaches them; convolutions only under the
+// automatic choice; a residual only under the automatic choice, DVQ_IMPL_WIDE_PIPE and DVQ_IMPL_8PHASE.
+// 256 x 256 macro tiles pay off on long reductions that fill the chip for several rounds (8192^3: 1036 vs 812 TFLOP/s);
+// on the StackGPT shapes (K = 1024 .. 4096, 324 .. 1296 tiles) the 128 x 128 kernel is faster (tools/gemm_probe.py),
+// so the automatic choice is conservative.
+bool nt_wide_ok(const NtParams& p, int impl) {
+    // a 1 x 1 / stride 1 / unpadded convolution (forward, or input gradient through the transposed pack) IS a plain GEMM
+    const bool conv1x1 = p.mode != MODE_GEMM && p.Ktot == (int)p.lda && p.KW == 1 && p.stride == 1 && p.pad_t == 0 && p.pad_l == 0 &&
+                         p.up == 0 && p.LH == p.DH && p.LW == p.DW && p.par == 0;
+    return (p.mode == MODE_GEMM || (conv1x1 && impl == DVQ_IMPL_AUTO)) &&
+           (p.R == nullptr || impl == DVQ_IMPL_AUTO || impl == DVQ_IMPL_WIDE_PIPE || impl == DVQ_IMPL_8PHASE) &&
+           p.ldc % Vec<bf16_t>::N == 0 && p.M >= 256 && p.Ncols >= 256;
+}
+
+// the pipelined main loops among them (wide_pipe, 8-phase): faster than both the 128 x 128 kernel and the plain wide one on every
+// tools/gemm_probe.py shape (679 / 775 / 865 / 870 / 1141 against 575 / 640 / 594 / 779 / 840 and 535 / 593 / 636 / 695 / 1050 TFLOP/s)
+bool nt_wide_pipe_ok(const NtParams& p) {
+    return p.Ncols % 8 == 0 && p.Ktot % 64 == 0 && (int64_t)p.M * p.lda < (1ll << 30) && (int64_t)p.Ncols * p.ldb < (1ll << 30);
+}
+
+// the 8-phase main loop (counted vmcnt, seven half-tiles ahead): long reductions over several rounds of tiles -- 8192^3 runs at
+// 1375 TFLOP/s against 1129 for the kernel below and 1332 for hipBLASLt's best solution on the same box (tools/gemm8p_probe.py);
+// its prologue (112 KiB before the first MFMA) and lock-step rounds lose at K <= 4096 / a single round (4096^3: 1181 vs 1280)
+int launch_nt_8phase(NtParams p, int64_t batch, hipStream_t s) {
+    const int64_t wgm = cdiv64(p.M, WT), wgn = cdiv64(p.Ncols, WT);
+    p.gm = (int)wgm;
+    p.gn = (int)wgn;
+    dvq_note_kernel("gemm_nt_8phase_kernel");
+    dvq_ensure_dynamic_lds((const void*)gemm_nt_8phase_kernel, 8 * 128 * GROW);
+    gemm_nt_8phase_kernel<<<dim3((unsigned)(wgm * wgn), 1, (unsigned)batch), dim3(512), 8 * 128 * GROW, s>>>(p);
+    DVQ_CHECK_LAUNCH("gemm_nt_8phase");
+    return DVQ_OK;
+}
+
+// experiment: 4 waves x (4 x 4 tiles), one wave per SIMD
+int launch_nt_wide_pipe4(NtParams p, int64_t batch, hipStream_t s) {
+    const int64_t wgm = cdiv64(p.M, WT), wgn = cdiv64(p.Ncols, WT);
+    p.gm = (int)wgm;
+    p.gn = (int)wgn;
+    dvq_note_kernel("gemm_nt_wide_pipe_kernel");
+    dvq_ensure_dynamic_lds((const void*)gemm_nt_wide_pipe_kernel<2, 2, 4>, 2 * WSTAGEB);
+    gemm_nt_wide_pipe_kernel<2, 2, 4><<<dim3((unsigned)(wgm * wgn), 1, (unsigned)batch), dim3(256), 2 * WSTAGEB, s>>>(p);
+    DVQ_CHECK_LAUNCH("gemm_nt_wide_pipe4");
+    return DVQ_OK;
+}
+
+// rows: 256 or 192 as the impl code asks, 0 = whichever needs less tile-row-time over the 256 CUs (rounds x rows)
+int launch_nt_wide_pipe(NtParams p, int64_t batch, int rows, hipStream_t s) {
+    const int64_t wgm = cdiv64(p.M, WT), wgn = cdiv64(p.Ncols, WT);
+    dvq_note_kernel("gemm_nt_wide_pipe_kernel");
+    const int64_t wgm192 = cdiv64(p.M, 192);
+    const int64_t cost256 = cdiv64(wgm * wgn * batch, 256) * 256, cost192 = cdiv64(wgm192 * wgn * batch, 256) * 192;
+    p.gn = (int)wgn;
+    if (rows == 192 || (rows == 0 && cost192 * 10 < cost256 * 8)) {
+        p.gm = (int)wgm192;
+        dvq_ensure_dynamic_lds((const void*)gemm_nt_wide_pipe_kernel<2, 2, 3>, 2 * (192 + 256) * GROW);
+        gemm_nt_wide_pipe_kernel<2, 2, 3><<<dim3((unsigned)(wgm192 * wgn), 1, (unsigned)batch), dim3(256), 2 * (192 + 256) * GROW, s>>>(p);
+    } else {
+        p.gm = (int)wgm;
+        dvq_ensure_dynamic_lds((const void*)gemm_nt_wide_pipe_kernel<4, 2, 2>, 2 * WSTAGEB);
+        gemm_nt_wide_pipe_kernel<4, 2, 2><<<dim3((unsigned)(wgm * wgn), 1, (unsigned)batch), dim3(512), 2 * WSTAGEB, s>>>(p);
+    }
+    DVQ_CHECK_LAUNCH("gemm_nt_wide_pipe");
+    return DVQ_OK;
+}
+
+int launch_nt_wide(NtParams p, int64_t batch, hipStream_t s) {
+    const int64_t wgm = cdiv64(p.M, WT), wgn = cdiv64(p.Ncols, WT);
+    p.gm = (int)wgm;
+    p.gn = (int)wgn;
+    dvq_note_kernel("gemm_nt_wide_kernel");
+    dvq_ensure_dynamic_lds((const void*)gemm_nt_wide_kernel, 2 * WSTAGEB);
+    gemm_nt_wide_kernel<<<dim3((unsigned)(wgm * wgn), 1, (unsigned)batch), dim3(512), 2 * WSTAGEB, s>>>(p);
+    DVQ_CHECK_LAUNCH("gemm_nt_wide");
+    return DVQ_OK;
+}
+
+// pipelined implicit-GEMM convolution (conv_nt_pipe_kernel, bf16): everything with 64-channel K slabs
+bool nt_conv_pipe_ok(const NtParams& p) {
+    const int khn = p.mode != MODE_GEMM && p.lda > 0 && p.KW > 0 ? (int)(p.Ktot / p.lda / p.KW) : 0;
+    const bool s2par = p.mode == MODE_TCONV && p.stride == 2;
+    bool pipe_ok = p.mode != MODE_GEMM && p.up == 0 && p.lda % 64 == 0 && p.ldb == p.Ktot &&
+                   p.Ncols % 8 == 0 && p.ldc % 8 == 0 && (p.stride == 1 || p.stride == 2) && khn >= 1 && khn * p.KW <= 16 &&
+                   (int64_t)khn * p.KW * p.lda == p.Ktot && p.bias_mode != 2 && p.alpha == 1.f &&
+                   ((int64_t)p.SH * p.SW * (p.M / ((int64_t)p.DH * p.DW)) + 2 * (4 * (int64_t)p.SW + 4)) * p.lda * 2 < 0x7fe00000ll &&
+                   (int64_t)p.Ncols * p.ldb * 2 < 0x7fe00000ll && p.M % ((int64_t)p.DH * p.DW) == 0;
+    if (s2par) pipe_ok = pipe_ok && p.DH % 2 == 0 && p.DW % 2 == 0 && p.M % 4 == 0;
+    return pipe_ok;
+}
+
+int launch_nt_conv_pipe(NtParams p, hipStream_t s) {
+    // tile choice (tools/conv_bench.py sweeps): 256 x 256 when that fills >= 3/4 of a round of 256 CUs,
+    // else 128 x 128 at two workgroups per CU; thin outputs 512 x 64
+    const int cfg = p.Ncols <= 16 ? 4 : p.Ncols <= 64 ? 3 : p.Ncols <= 128 ? 4 : (cdiv64(p.M, 256) * cdiv64(p.Ncols, 256) < 192 ? 4 : 1);
+    const int tm = cfg == 3 ? 512 : cfg == 4 ? 128 : 256, tn = cfg == 1 ? 256 : cfg == 3 ? 64 : 128;
+    if (p.mode == MODE_TCONV && p.stride == 2) {
+        p.par = 1;
+        p.par_tiles = (int)cdiv64(p.M / 4, tm);
+        p.gm = 4 * p.par_tiles;
+    } else {
+        p.par = 0;
+        p.gm = (int)cdiv64(p.M, tm);
+    }
+    p.gn = (int)cdiv64(p.Ncols, tn);
+    const int lds = 2 * (tm + tn) * GROW;
+    const dim3 grid((unsigned)((int64_t)p.gm * p.gn));
+    auto go = [&](auto kern) {
+        dvq_ensure_dynamic_lds((const void*)kern, lds);
+        kern<<<grid, dim3(cfg == 4 ? 256 : 512), lds, s>>>(p);
+    };
+    dvq_note_kernel("conv_nt_pipe_kernel");
+    const bool fwd = p.mode == MODE_FWD;
+    if (cfg == 4) fwd ? go(conv_nt_pipe_kernel<2, 2, 2, 2, MODE_FWD>) : go(conv_nt_pipe_kernel<2, 2, 2, 2, MODE_TCONV>);
+    else if (cfg == 1) fwd ? go(conv_nt_pipe_kernel<4, 2, 2, 4, MODE_FWD>) : go(conv_nt_pipe_kernel<4, 2, 2, 4, MODE_TCONV>);
+    else fwd ? go(conv_nt_pipe_kernel<8, 1, 2, 2, MODE_FWD>) : go(conv_nt_pipe_kernel<8, 1, 2, 2, MODE_TCONV>);
+    DVQ_CHECK_LAUNCH("conv_nt_pipe");
+    return DVQ_OK;
+}
+
+// 128 x 128 LDS-DMA kernel: every nt_mfma_ok shape
+template <typename T>
+int launch_nt_glds(NtParams p, int64_t batch, hipStream_t s) {
+    constexpr int VN = Vec<T>::N;
+    const bool tapu = p.mode != MODE_GEMM && ((p.lda / VN) % 8) == 0;
+    if (p.mode == MODE_TCONV && p.stride == 2 && p.up == 0 && tapu && p.DH % 2 == 0 && p.DW % 2 == 0 && p.ldc % VN == 0) {
+        // stride-2 input gradient: rows grouped by output parity class, each class contracts over its own taps only
+        p.par = 1;
+        p.par_tiles = (int)cdiv64(p.M / 4, TILE);
+        p.gm = 4 * p.par_tiles;
+    }
+    dim3 grid((unsigned)(p.gm * p.gn), 1, (unsigned)batch);
+    dvq_note_kernel("igemm_nt_glds_kernel");
+    auto go = [&](auto kern) {
+        dvq_ensure_dynamic_lds((const void*)kern, 2 * GSTAGEB);
+        kern<<<grid, dim3(256), 2 * GSTAGEB, s>>>(p);
+    };
+    constexpr bool F32 = sizeof(T) == 4;
+#ifdef DVQ_PROBES
+    {
+        static const int x3dbg = dvq_probe_env("DVQ_X3_DBG");
+        static bool x3set = false;
+        if (!x3set) {
+            x3set = true;
+            (void)hipMemcpyToSymbol(HIP_SYMBOL(g_x3_dbg), &x3dbg, sizeof(int));
+        }
+    }
+#endif
+    if (F32 && p.split3) {              // fp32x3: the split-bf16 instantiations (separate kernels: the exact-fp32 code is untouched)
+        if (p.mode == MODE_GEMM) go(igemm_nt_glds_kernel<T, MODE_GEMM, false, F32>);
+        else if (p.mode == MODE_FWD && tapu) go(igemm_nt_glds_kernel<T, MODE_FWD, true, F32>);
+        else if (p.mode == MODE_FWD) go(igemm_nt_glds_kernel<T, MODE_FWD, false, F32>);
+        else if (tapu) go(igemm_nt_glds_kernel<T, MODE_TCONV, true, F32>);
+        else go(igemm_nt_glds_kernel<T, MODE_TCONV, false, F32>);
+    } else if (p.mode == MODE_GEMM) go(igemm_nt_glds_kernel<T, MODE_GEMM, false>);
+    else if (p.mode == MODE_FWD && tapu) go(igemm_nt_glds_kernel<T, MODE_FWD, true>);
+    else if (p.mode == MODE_FWD) go(igemm_nt_glds_kernel<T, MODE_FWD, false>);
+    else if (tapu) go(igemm_nt_glds_kernel<T, MODE_TCONV, true>);
+    else go(igemm_nt_glds_kernel<T, MODE_TCONV, false>);
+    DVQ_CHECK_LAUNCH("igemm_nt_glds");
+    return DVQ_OK;
+}
+
+// register-staged 128 x 128 kernel
+template <typename T>
+int launch_nt_regstage(NtParams p, int64_t batch, hipStream_t s) {
+    dim3 grid((unsigned)(p.gm * p.gn), 1, (unsigned)batch);
+    dvq_note_kernel("igemm_nt_kernel");
+    dvq_ensure_dynamic_lds((const void*)igemm_nt_kernel<T>, 2 * STAGEB);
+    igemm_nt_kernel<T><<<grid, dim3(256), 2 * STAGEB, s>>>(p);
+    DVQ_CHECK_LAUNCH("igemm_nt");
+    return DVQ_OK;
+}
+
+template <typename T>
+int launch_nt_naive(NtParams p, int64_t batch, hipStream_t s) {
+    int64_t total = (int64_t)p.M * p.Ncols;
+    unsigned blocks = (unsigned)(cdiv64(total, 256) < 16384 ? cdiv64(total, 256) : 16384);
+    dvq_note_kernel("naive_nt_kernel");
+    naive_nt_kernel<T><<<dim3(blocks, 1, (unsigned)batch), dim3(256), 0, s>>>(p);
+    DVQ_CHECK_LAUNCH("naive_nt");
+    return DVQ_OK;
+}
+
+// Priority order: 8-phase, 4-wave pipe, wide pipe, plain wide, pipelined convolution, 128 x 128 LDS-DMA, register-staged, naive.
+// A preferred code stands in for the automatic heuristic of its kernel only; a required code returns DVQ_ESHAPE on a shape its kernel
+// does not run.
 template <typename T>
 int launch_nt(NtParams p, int64_t batch, int impl, hipStream_t s) {
-    constexpr int VN = Vec<T>::N;
     p.split3 = sizeof(T) == 4 && dvq_fp32_split() != 0;
     p.gm = (int)cdiv64(p.M, TILE);
     p.gn = (int)cdiv64(p.Ncols, TILE);
-    bool mfma_ok = p.Ktot % VN == 0 && p.ldb % VN == 0 && p.lda % VN == 0 && (p.stride == 1 || p.stride == 2);
-    if (p.mode == MODE_GEMM) mfma_ok = mfma_ok && (p.sA % VN == 0) && (p.sB % VN == 0);
-    DVQ_REQUIRE(!(impl >= 2 && impl != 5 && impl != 6 && impl != 7 && impl != 8 && impl != 9 && impl != 10 && !mfma_ok), DVQ_ESHAPE,
-                "igemm_nt: MFMA path needs K, lda, ldb multiples of %d (K=%d lda=%lld ldb=%lld) and stride 1/2", VN,
+    const bool mfma_ok = nt_mfma_ok<T>(p);
+    const bool auto_or_preferred = impl == DVQ_IMPL_AUTO || impl_preferred(impl);
+    DVQ_REQUIRE(mfma_ok || impl < DVQ_IMPL_MFMA || auto_or_preferred || impl == DVQ_IMPL_CONV_PIPE, DVQ_ESHAPE,
+                "igemm_nt: MFMA path needs K, lda, ldb multiples of %d (K=%d lda=%lld ldb=%lld) and stride 1/2", Vec<T>::N,
                 p.Ktot, (long long)p.lda, (long long)p.ldb);
-    DVQ_REQUIRE(!(impl == 3 && !mfma_ok), DVQ_ESHAPE, "igemm_nt: register-staged MFMA path unsupported for this shape");
-    const bool use_mfma = impl == 2 || impl == 3 || ((impl == 0 || impl == 5 || impl == 6 || impl == 7 || impl == 8 || impl == 9 || impl == 10) && mfma_ok && (int64_t)p.M * p.Ncols >= 1024);
+    const bool use_mfma = impl == DVQ_IMPL_MFMA || impl == DVQ_IMPL_REGSTAGE ||
+                          ((auto_or_preferred || impl == DVQ_IMPL_CONV_PIPE) && mfma_ok && (int64_t)p.M * p.Ncols >= 1024);
     if constexpr (sizeof(T) == 2) {
-        // 256 x 256 macro tiles pay off on long reductions that fill the chip for several rounds (8192^3: 1036 vs 812 TFLOP/s);
-        // on the StackGPT shapes (K = 1024 .. 4096, 324 .. 1296 tiles) the 128 x 128 kernel is faster (tools/gemm_probe.py),
-        // so the automatic choice is conservative.  impl == 5 forces the wide kernel (tests).
-        // a 1 x 1 / stride 1 / unpadded convolution (forward, or input gradient through the transposed pack) IS a plain GEMM
-        const bool conv1x1 = p.mode != MODE_GEMM && p.Ktot == (int)p.lda && p.KW == 1 && p.stride == 1 && p.pad_t == 0 && p.pad_l == 0 &&
-                             p.up == 0 && p.LH == p.DH && p.LW == p.DW && p.par == 0;
-        if ((impl == 0 || impl == 5 || impl == 6 || impl == 7 || impl == 8 || impl == 10) && mfma_ok && (p.mode == MODE_GEMM || (conv1x1 && impl == 0)) &&
-            (p.R == nullptr || impl == 0 || impl == 6 || impl == 10) && p.ldc % VN == 0 && p.M >= 256 && p.Ncols >= 256) {
-            const int64_t wgm = cdiv64(p.M, WT), wgn = cdiv64(p.Ncols, WT);
-            // pipelined main loop: faster than both the 128 x 128 kernel and the plain wide one on every tools/gemm_probe.py
-            // shape (679 / 775 / 865 / 870 / 1141 against 575 / 640 / 594 / 779 / 840 and 535 / 593 / 636 / 695 / 1050 TFLOP/s)
-            const bool pipe_ok = p.Ncols % 8 == 0 && p.Ktot % 64 == 0 && (int64_t)p.M * p.lda < (1ll << 30) &&
-                                 (int64_t)p.Ncols * p.ldb < (1ll << 30);
-            // the 8-phase main loop (counted vmcnt, seven half-tiles ahead): long reductions over several rounds of tiles -- 8192^3 runs at
-            // 1375 TFLOP/s against 1129 for the kernel below and 1332 for hipBLASLt's best solution on the same box (tools/gemm8p_probe.py);
-            // its prologue (112 KiB before the first MFMA) and lock-step rounds lose at K <= 4096 / a single round (4096^3: 1181 vs 1280)
-            if ((impl == 10 || (impl == 0 && p.Ktot >= 4096 && wgm * wgn * batch >= 512)) && pipe_ok) {
-                p.gm = (int)wgm;
-                p.gn = (int)wgn;
-                dvq_note_kernel("gemm_nt_8phase_kernel");
-                dvq_ensure_dynamic_lds((const void*)gemm_nt_8phase_kernel, 8 * 128 * GROW);
-                gemm_nt_8phase_kernel<<<dim3((unsigned)(wgm * wgn), 1, (unsigned)batch), dim3(512), 8 * 128 * GROW, s>>>(p);
-                DVQ_CHECK_LAUNCH("gemm_nt_8phase");
-                return DVQ_OK;
-            }
-            if (impl == 7 && pipe_ok) {            // experiment: 4 waves x (4 x 4 tiles), one wave per SIMD
-                p.gm = (int)wgm;
-                p.gn = (int)wgn;
-                dvq_note_kernel("gemm_nt_wide_pipe_kernel");
-                dvq_ensure_dynamic_lds((const void*)gemm_nt_wide_pipe_kernel<2, 2, 4>, 2 * WSTAGEB);
-                gemm_nt_wide_pipe_kernel<2, 2, 4><<<dim3((unsigned)(wgm * wgn), 1, (unsigned)batch), dim3(256), 2 * WSTAGEB, s>>>(p);
-                DVQ_CHECK_LAUNCH("gemm_nt_wide_pipe4");
-                return DVQ_OK;
-            }
-            if ((impl == 6 || impl == 8 || (impl == 0 && wgm * wgn * batch >= 128)) && pipe_ok) {
-                // 256- or 192-row tiles: whichever needs less tile-row-time over the 256 CUs (rounds x rows)
-                dvq_note_kernel("gemm_nt_wide_pipe_kernel");
-                const int64_t wgm192 = cdiv64(p.M, 192);
-                const int64_t cost256 = cdiv64(wgm * wgn * batch, 256) * 256, cost192 = cdiv64(wgm192 * wgn * batch, 256) * 192;
-                p.gn = (int)wgn;
-                if (impl == 8 || (impl != 6 && cost192 * 10 < cost256 * 8)) {
-                    p.gm = (int)wgm192;
-                    dvq_ensure_dynamic_lds((const void*)gemm_nt_wide_pipe_kernel<2, 2, 3>, 2 * (192 + 256) * GROW);
-                    gemm_nt_wide_pipe_kernel<2, 2, 3><<<dim3((unsigned)(wgm192 * wgn), 1, (unsigned)batch), dim3(256), 2 * (192 + 256) * GROW, s>>>(p);
-                } else {
-                    p.gm = (int)wgm;
-                    dvq_ensure_dynamic_lds((const void*)gemm_nt_wide_pipe_kernel<4, 2, 2>, 2 * WSTAGEB);
-                    gemm_nt_wide_pipe_kernel<4, 2, 2><<<dim3((unsigned)(wgm * wgn), 1, (unsigned)batch), dim3(512), 2 * WSTAGEB, s>>>(p);
-                }
-                DVQ_CHECK_LAUNCH("gemm_nt_wide_pipe");
-                return DVQ_OK;
-            }
-            if (p.mode == MODE_GEMM && p.R == nullptr && (impl == 5 || (p.Ktot >= 8192 && wgm * wgn * batch >= 768))) {
-                p.gm = (int)wgm;
-                p.gn = (int)wgn;
-                dvq_note_kernel("gemm_nt_wide_kernel");
-                dvq_ensure_dynamic_lds((const void*)gemm_nt_wide_kernel, 2 * WSTAGEB);
-                gemm_nt_wide_kernel<<<dim3((unsigned)(wgm * wgn), 1, (unsigned)batch), dim3(512), 2 * WSTAGEB, s>>>(p);
-                DVQ_CHECK_LAUNCH("gemm_nt_wide");
-                return DVQ_OK;
-            }
-        }
+        const int64_t wtiles = cdiv64(p.M, WT) * cdiv64(p.Ncols, WT) * batch;
+        const bool wide_ok = auto_or_preferred && mfma_ok && nt_wide_ok(p, impl);
+        const bool wide_pipe_ok = wide_ok && nt_wide_pipe_ok(p);
+        if (wide_pipe_ok && (impl == DVQ_IMPL_8PHASE || (impl == DVQ_IMPL_AUTO && p.Ktot >= 4096 && wtiles >= 512)))
+            return launch_nt_8phase(p, batch, s);
+        if (wide_pipe_ok && impl == DVQ_IMPL_WIDE_PIPE_4WAVE) return launch_nt_wide_pipe4(p, batch, s);
+        if (wide_pipe_ok && (impl == DVQ_IMPL_WIDE_PIPE || impl == DVQ_IMPL_WIDE_PIPE_192 || (impl == DVQ_IMPL_AUTO && wtiles >= 128)))
+            return launch_nt_wide_pipe(p, batch, impl == DVQ_IMPL_WIDE_PIPE_192 ? 192 : impl == DVQ_IMPL_WIDE_PIPE ? 256 : 0, s);
+        if (wide_ok && p.mode == MODE_GEMM && p.R == nullptr && (impl == DVQ_IMPL_WIDE || (p.Ktot >= 8192 && wtiles >= 768)))
+            return launch_nt_wide(p, batch, s);
+        const bool conv_pipe_ok = (impl == DVQ_IMPL_AUTO || impl == DVQ_IMPL_CONV_PIPE) && nt_conv_pipe_ok(p);
+        DVQ_REQUIRE(!(impl == DVQ_IMPL_CONV_PIPE && !conv_pipe_ok), DVQ_ESHAPE, "igemm_nt: shape not eligible for the pipelined convolution kernel");
+        if (conv_pipe_ok) return launch_nt_conv_pipe(p, s);
     }
-    if constexpr (sizeof(T) == 2) {
-        // pipelined implicit-GEMM convolution (conv_nt_pipe_kernel): everything with 64-channel K slabs; impl 9 forces it (tests)
-        const int khn = p.mode != MODE_GEMM && p.lda > 0 && p.KW > 0 ? (int)(p.Ktot / p.lda / p.KW) : 0;
-        const bool s2par = p.mode == MODE_TCONV && p.stride == 2;
-        bool pipe_ok = (impl == 0 || impl == 9) && p.mode != MODE_GEMM && p.up == 0 && p.lda % 64 == 0 && p.ldb == p.Ktot &&
-                       p.Ncols % 8 == 0 && p.ldc % 8 == 0 && (p.stride == 1 || p.stride == 2) && khn >= 1 && khn * p.KW <= 16 &&
-                       (int64_t)khn * p.KW * p.lda == p.Ktot && p.bias_mode != 2 && p.alpha == 1.f &&
-                       ((int64_t)p.SH * p.SW * (p.M / ((int64_t)p.DH * p.DW)) + 2 * (4 * (int64_t)p.SW + 4)) * p.lda * 2 < 0x7fe00000ll &&
-                       (int64_t)p.Ncols * p.ldb * 2 < 0x7fe00000ll && p.M % ((int64_t)p.DH * p.DW) == 0;
-        if (s2par) pipe_ok = pipe_ok && p.DH % 2 == 0 && p.DW % 2 == 0 && p.M % 4 == 0;
-        if (p.mode == MODE_FWD && p.stride == 2) pipe_ok = pipe_ok && true;
-        DVQ_REQUIRE(!(impl == 9 && !pipe_ok), DVQ_ESHAPE, "igemm_nt: shape not eligible for the pipelined convolution kernel");
-        if (pipe_ok) {
-            // tile choice (tools/conv_bench.py sweeps): 256 x 256 when that fills >= 3/4 of a round of 256 CUs,
-            // else 128 x 128 at two workgroups per CU; thin outputs 512 x 64
-            const int cfg = p.Ncols <= 16 ? 4 : p.Ncols <= 64 ? 3 : p.Ncols <= 128 ? 4 : (cdiv64(p.M, 256) * cdiv64(p.Ncols, 256) < 192 ? 4 : 1);
-            const int tm = cfg == 3 ? 512 : cfg == 4 ? 128 : 256, tn = cfg == 1 ? 256 : cfg == 3 ? 64 : 128;
-            if (s2par) {
-                p.par = 1;
-                p.par_tiles = (int)cdiv64(p.M / 4, tm);
-                p.gm = 4 * p.par_tiles;
-            } else {
-                p.par = 0;
-                p.gm = (int)cdiv64(p.M, tm);
-            }
-            p.gn = (int)cdiv64(p.Ncols, tn);
-            const int lds = 2 * (tm + tn) * GROW;
-            const dim3 grid((unsigned)((int64_t)p.gm * p.gn));
-            auto go = [&](auto kern) {
-                dvq_ensure_dynamic_lds((const void*)kern, lds);
-                kern<<<grid, dim3(cfg == 4 ? 256 : 512), lds, s>>>(p);
-            };
-            dvq_note_kernel("conv_nt_pipe_kernel");
-            const bool fwd = p.mode == MODE_FWD;
-            if (cfg == 4) fwd ? go(conv_nt_pipe_kernel<2, 2, 2, 2, MODE_FWD>) : go(conv_nt_pipe_kernel<2, 2, 2, 2, MODE_TCONV>);
-            else if (cfg == 1) fwd ? go(conv_nt_pipe_kernel<4, 2, 2, 4, MODE_FWD>) : go(conv_nt_pipe_kernel<4, 2, 2, 4, MODE_TCONV>);
-            else fwd ? go(conv_nt_pipe_kernel<8, 1, 2, 2, MODE_FWD>) : go(conv_nt_pipe_kernel<8, 1, 2, 2, MODE_TCONV>);
-            DVQ_CHECK_LAUNCH("conv_nt_pipe");
-            return DVQ_OK;
-        }
-    }
-    if (use_mfma && impl != 3) {
-        const bool tapu = p.mode != MODE_GEMM && ((p.lda / VN) % 8) == 0;
-        if (p.mode == MODE_TCONV && p.stride == 2 && p.up == 0 && tapu && p.DH % 2 == 0 && p.DW % 2 == 0 && p.ldc % VN == 0) {
-            // stride-2 input gradient: rows grouped by output parity class, each class contracts over its own taps only
-            p.par = 1;
-            p.par_tiles = (int)cdiv64(p.M / 4, TILE);
-            p.gm = 4 * p.par_tiles;
-        }
-        dim3 grid((unsigned)(p.gm * p.gn), 1, (unsigned)batch);
-        dvq_note_kernel("igemm_nt_glds_kernel");
-        auto go = [&](auto kern) {
-            dvq_ensure_dynamic_lds((const void*)kern, 2 * GSTAGEB);
-            kern<<<grid, dim3(256), 2 * GSTAGEB, s>>>(p);
-        };
-        constexpr bool F32 = sizeof(T) == 4;
-#ifdef DVQ_PROBES
-        {
-            static const int x3dbg = dvq_probe_env("DVQ_X3_DBG");
-            static bool x3set = false;
-            if (!x3set) {
-                x3set = true;
-                (void)hipMemcpyToSymbol(HIP_SYMBOL(g_x3_dbg), &x3dbg, sizeof(int));
-            }
-        }
-#endif
-        if (F32 && p.split3) {              // fp32x3: the split-bf16 instantiations (separate kernels: the exact-fp32 code is untouched)
-            if (p.mode == MODE_GEMM) go(igemm_nt_glds_kernel<T, MODE_GEMM, false, F32>);
-            else if (p.mode == MODE_FWD && tapu) go(igemm_nt_glds_kernel<T, MODE_FWD, true, F32>);
-            else if (p.mode == MODE_FWD) go(igemm_nt_glds_kernel<T, MODE_FWD, false, F32>);
-            else if (tapu) go(igemm_nt_glds_kernel<T, MODE_TCONV, true, F32>);
-            else go(igemm_nt_glds_kernel<T, MODE_TCONV, false, F32>);
-        } else if (p.mode == MODE_GEMM) go(igemm_nt_glds_kernel<T, MODE_GEMM, false>);
-        else if (p.mode == MODE_FWD && tapu) go(igemm_nt_glds_kernel<T, MODE_FWD, true>);
-        else if (p.mode == MODE_FWD) go(igemm_nt_glds_kernel<T, MODE_FWD, false>);
-        else if (tapu) go(igemm_nt_glds_kernel<T, MODE_TCONV, true>);
-        else go(igemm_nt_glds_kernel<T, MODE_TCONV, false>);
-        DVQ_CHECK_LAUNCH("igemm_nt_glds");
-    } else if (use_mfma) {
-        dim3 grid((unsigned)(p.gm * p.gn), 1, (unsigned)batch);
-        dvq_note_kernel("igemm_nt_kernel");
-        dvq_ensure_dynamic_lds((const void*)igemm_nt_kernel<T>, 2 * STAGEB);
-        igemm_nt_kernel<T><<<grid, dim3(256), 2 * STAGEB, s>>>(p);
-        DVQ_CHECK_LAUNCH("igemm_nt");
-    } else {
-        int64_t total = (int64_t)p.M * p.Ncols;
-        unsigned blocks = (unsigned)(cdiv64(total, 256) < 16384 ? cdiv64(total, 256) : 16384);
-        dvq_note_kernel("naive_nt_kernel");
-        naive_nt_kernel<T><<<dim3(blocks, 1, (unsigned)batch), dim3(256), 0, s>>>(p);
-        DVQ_CHECK_LAUNCH("naive_nt");
-    }
-    return DVQ_OK;
+    if (use_mfma && impl != DVQ_IMPL_REGSTAGE) return launch_nt_glds<T>(p, batch, s);
+    if (use_mfma) return launch_nt_regstage<T>(p, batch, s);
+    return launch_nt_naive<T>(p, batch, s);
 }
 
 // deterministic mode: C[e] += sum over the splits' partial slices, in split order (one thread per element: a fixed summation order)
@@ -2955,162 +3017,194 @@ static void tn_det_fold(const TnParams& p, int64_t span, hipStream_t s) {
                                                                            p.dws_bias, p.I);
 }
 
+// large plain weight-gradient GEMMs (bf16): 256 x 256 tiles, pipelined main loop; ~one resident workgroup per CU.
+// 1 x 1 weight gradients run on the patch kernel too, not on this one: 65536 x 256 x 256
+// 31 against 52 us, 16384 x 512 x 512 30 against 40 us -- a 256 x 256 tile leaves 64 workgroups for the whole chip
+bool tn_wide_ok(const TnParams& p) {
+    return !p.conv && p.taps == 1 && p.I >= 256 && p.J >= 256 && p.Mred >= 1024 &&
+           p.I % 8 == 0 && p.J % 8 == 0 && (int64_t)p.Mred * p.lda < (1ll << 30) && (int64_t)p.Mred * p.ldb < (1ll << 30) &&
+           (p.sA * 2) % 4 == 0 && (p.sB * 2) % 4 == 0;
+}
+
+// eight_phase: gemm_tn_8phase_kernel (DMA queue never drained; batch strides must be multiples of 16 bytes), else gemm_tn_wide_pipe_kernel
+int launch_tn_wide(TnParams p, int64_t batch, bool det, bool eight_phase, hipStream_t s) {
+    constexpr int BK = Vec<bf16_t>::BK;
+    p.itiles = (int)cdiv64(p.I, 256);
+    p.jtiles = (int)cdiv64(p.J, 256);
+    const int64_t wtiles = (int64_t)p.itiles * p.jtiles * batch;
+    // workgroups a wide TN product aims at.  Round 5: 128, not one per CU -- these weight gradients run on the side stream beside
+    // the input-gradient GEMMs (layers.Linear.bwd), so half a chip's worth of workgroups is what they get anyway, and half the
+    // splits mean half the partials to write and fold: StackGPT p6c18 step 79.9 -> 77.9 ms (64: 81.3 ms; same-box A/B,
+    // profiles/r05_stage2_ab.txt).
+    constexpr int wide_wgs = 128;
+    int64_t wsplits = wtiles >= wide_wgs ? 1 : wide_wgs / wtiles;
+    // >= 16 stages per workgroup: prologue, partial-tile store and fold amortised (8 / 4 / 32 measured slower on the 1 x 1
+    // weight gradients: 60 / 95 / 66 against 52 us at 65536 x 256 x 256)
+    const int64_t wmax = cdiv64(p.Mred, 16 * BK);
+    if (wsplits > wmax) wsplits = wmax;
+    const int64_t wmps = cdiv64(cdiv64(p.Mred, wsplits), BK) * BK;
+    p.m_per_split = (int)wmps;
+    p.nsplit = (int)cdiv64(p.Mred, wmps);
+    int64_t ws_bytes = 0;
+    char* wsp = (char*)dvq_workspace_stream(s, &ws_bytes);
+    const int64_t need = (int64_t)p.nsplit * wtiles * 65536 * 4 + (int64_t)p.nsplit * p.itiles * 256 * 4;
+    if (wsp != nullptr && ws_bytes >= need && (p.nsplit > 2 || (det && p.nsplit > 1)) && batch == 1) {     // many splits per tile: partials + fold, no atomics
+        p.ws = (float*)wsp;
+        p.ws_bias = (float*)(wsp + (int64_t)p.nsplit * wtiles * 65536 * 4);
+    } else if (det && p.nsplit > 1) {            // no scratch for the partials: one workgroup per tile walks the whole reduction
+        p.m_per_split = (int)(cdiv64(p.Mred, BK) * BK);
+        p.nsplit = 1;
+    }
+    if (eight_phase) {
+        dvq_note_kernel("gemm_tn_8phase_kernel");
+        dvq_ensure_dynamic_lds((const void*)gemm_tn_8phase_kernel, 8 * 64 * 256);
+        gemm_tn_8phase_kernel<<<dim3((unsigned)(p.itiles * p.jtiles * p.nsplit), 1, (unsigned)batch), dim3(512), 8 * 64 * 256, s>>>(p);
+        DVQ_CHECK_LAUNCH("gemm_tn_8phase");
+    } else {
+        dvq_note_kernel("gemm_tn_wide_pipe_kernel");
+        dvq_ensure_dynamic_lds((const void*)gemm_tn_wide_pipe_kernel, 2 * WTSTG);
+        gemm_tn_wide_pipe_kernel<<<dim3((unsigned)(p.itiles * p.jtiles * p.nsplit), 1, (unsigned)batch), dim3(512), 2 * WTSTG, s>>>(p);
+        DVQ_CHECK_LAUNCH("gemm_tn_wide_pipe");
+    }
+    if (p.ws != nullptr) {
+        gemm_tn_wide_reduce_kernel<<<dim3((unsigned)(wtiles * 256)), dim3(256), 0, s>>>(p);
+        DVQ_CHECK_LAUNCH("gemm_tn_wide_reduce");
+    }
+    return DVQ_OK;
+}
+
+// 8 x 8 output-pixel patches as reduction stages (conv_tn_patch_kernel, bf16, batch 1, not the thin J == 8 shapes)
+bool tn_patch_ok(const TnParams& p) {
+    return p.conv && !p.thin && p.I % 8 == 0 && p.J % 8 == 0 &&
+           p.pad_t <= 8 && p.pad_l <= 8 && p.Mred % (p.DH * p.DW) == 0 &&
+           (int64_t)(8 * p.stride + p.taps / p.KW + 10) * p.SW * p.ldb * 2 < (1ll << 30) && (int64_t)8 * p.DW * p.lda * 2 < (1ll << 30);
+}
+
+// split over patch ranges
+int launch_tn_patch(TnParams p, int64_t batch, bool det, hipStream_t s) {
+    const int64_t PH = cdiv64(p.DH, 8), PW = cdiv64(p.DW, 8);
+    const int64_t npatch = (p.Mred / ((int64_t)p.DH * p.DW)) * PH * PW;
+    const int64_t ptiles = (int64_t)p.itiles * p.jtiles * p.taps;
+    int64_t psplits = 512 / ptiles;          // workgroups the patch kernel aims at (sweep: 128 / 256 / 512 / 1024, profiles/)
+    if (psplits > npatch / 16) psplits = npatch / 16;       // >= 16 stages per workgroup: the 64-KiB atomic flush amortised
+    if (psplits < 1) psplits = 1;
+    int64_t pps = cdiv64(npatch, psplits);
+    p.m_per_split = (int)pps;
+    p.nsplit = (int)cdiv64(npatch, pps);
+    int64_t dspan = 0;
+    const bool dfold = det && p.nsplit > 1 && tn_det_setup(p, batch, s, &dspan);      // partials + fold in split order
+    if (det && p.nsplit > 1 && !dfold) {                                             // no scratch / strided C: unsplit
+        p.m_per_split = (int)npatch;
+        p.nsplit = 1;
+    }
+    dvq_note_kernel("conv_tn_patch_kernel");
+    dvq_ensure_dynamic_lds((const void*)conv_tn_patch_kernel, 2 * TSTAGEB);
+    conv_tn_patch_kernel<<<dim3((unsigned)(ptiles * p.nsplit)), dim3(256), 2 * TSTAGEB, s>>>(p);
+    DVQ_CHECK_LAUNCH("conv_tn_patch");
+    if (dfold) {
+        tn_det_fold(p, dspan, s);
+        DVQ_CHECK_LAUNCH("tn_det_fold");
+    }
+    return DVQ_OK;
+}
+
+// 128 x 128 tiles split along the reduction: the LDS-DMA + transpose-read kernel (bf16, tr) or the register-staged igemm_tn_kernel
+template <typename T>
+int launch_tn_tiles(TnParams p, int64_t batch, bool tr, bool det, hipStream_t s) {
+    constexpr int BK = Vec<T>::BK;
+    const int tapblk = p.thin ? 1 : p.taps;
+    const int64_t tiles = (int64_t)p.itiles * p.jtiles * tapblk * batch;
+    // 512 resident workgroups (2 per CU): aim at two full rounds, never slightly more than a round
+    // (thin: every workgroup ends with I x taps x 8 atomics on one small tile -- one round of 256 is enough)
+    int64_t splits = (p.thin ? 256 : 1024) / tiles;
+    const int64_t max_splits = cdiv64(p.Mred, 4 * BK);
+    if (splits > max_splits) splits = max_splits;
+    if (splits < 1) splits = 1;
+    int64_t mps = cdiv64(cdiv64(p.Mred, splits), BK) * BK;
+    splits = cdiv64(p.Mred, mps);
+    p.m_per_split = (int)mps;
+    p.nsplit = (int)splits;
+    dim3 grid((unsigned)(p.itiles * p.jtiles * tapblk * splits), 1, (unsigned)batch);
+    int64_t gspan = 0;
+    bool gfold = false;
+    if (det && p.nsplit > 1) {
+        gfold = tr && tn_det_setup(p, batch, s, &gspan);          // (the transpose-read kernel stores partials)
+        if (!gfold) {                                                                    // other kernels / no scratch: unsplit
+            p.m_per_split = (int)(cdiv64(p.Mred, BK) * BK);
+            p.nsplit = 1;
+            grid = dim3((unsigned)(p.itiles * p.jtiles * tapblk), 1, (unsigned)batch);
+        }
+    }
+    dvq_note_kernel(tr ? "igemm_tn_tr_kernel" : "igemm_tn_kernel");
+    if (tr) {
+        if (p.conv) {
+            dvq_ensure_dynamic_lds((const void*)igemm_tn_tr_kernel<true>, 2 * TSTAGEB);
+            igemm_tn_tr_kernel<true><<<grid, dim3(256), 2 * TSTAGEB, s>>>(p);
+        } else {
+            dvq_ensure_dynamic_lds((const void*)igemm_tn_tr_kernel<false>, 2 * TSTAGEB);
+            igemm_tn_tr_kernel<false><<<grid, dim3(256), 2 * TSTAGEB, s>>>(p);
+        }
+    } else if (sizeof(T) == 4 && p.split3) {          // fp32x3
+        constexpr bool F32 = sizeof(T) == 4;
+        if (p.conv) {
+            dvq_ensure_dynamic_lds((const void*)igemm_tn_kernel<T, true, F32>, 2 * GSTAGEB);
+            igemm_tn_kernel<T, true, F32><<<grid, dim3(256), 2 * GSTAGEB, s>>>(p);
+        } else {
+            dvq_ensure_dynamic_lds((const void*)igemm_tn_kernel<T, false, F32>, 2 * GSTAGEB);
+            igemm_tn_kernel<T, false, F32><<<grid, dim3(256), 2 * GSTAGEB, s>>>(p);
+        }
+    } else if (p.conv) {
+        dvq_ensure_dynamic_lds((const void*)igemm_tn_kernel<T, true>, 2 * GSTAGEB);
+        igemm_tn_kernel<T, true><<<grid, dim3(256), 2 * GSTAGEB, s>>>(p);
+    } else {
+        dvq_ensure_dynamic_lds((const void*)igemm_tn_kernel<T, false>, 2 * GSTAGEB);
+        igemm_tn_kernel<T, false><<<grid, dim3(256), 2 * GSTAGEB, s>>>(p);
+    }
+    DVQ_CHECK_LAUNCH("igemm_tn");
+    if (gfold) {
+        tn_det_fold(p, gspan, s);
+        DVQ_CHECK_LAUNCH("tn_det_fold");
+    }
+    return DVQ_OK;
+}
+
+template <typename T>
+int launch_tn_naive(TnParams p, int64_t batch, hipStream_t s) {
+    int64_t nout = (int64_t)p.I * p.taps * p.J + (p.colsumA ? p.I : 0);
+    unsigned blocks = (unsigned)(cdiv64(nout, 4) < 8192 ? cdiv64(nout, 4) : 8192);
+    dvq_note_kernel("naive_tn_kernel");
+    naive_tn_kernel<T><<<dim3(blocks, 1, (unsigned)batch), dim3(256), 0, s>>>(p);
+    DVQ_CHECK_LAUNCH("naive_tn");
+    return DVQ_OK;
+}
+
+// Priority order: naive (DVQ_IMPL_NAIVE, or the automatic choice on an unaligned / short reduction), wide 8-phase / wide pipe, patch stages,
+// transpose-read, register-staged.  Every code from DVQ_IMPL_MFMA up takes an MFMA kernel; all but the NT-only preferred codes
+// DVQ_IMPL_WIDE .. DVQ_IMPL_WIDE_PIPE_192 return DVQ_ESHAPE without the vector alignment.
 template <typename T>
 int launch_tn(TnParams p, int64_t batch, int impl, hipStream_t s) {
     constexpr int VN = Vec<T>::N;
-    constexpr int BK = Vec<T>::BK;
     p.split3 = sizeof(T) == 4 && dvq_fp32_split() != 0;
-    bool mfma_ok = p.lda % VN == 0 && p.ldb % VN == 0 && p.sA % VN == 0 && p.sB % VN == 0;
-    DVQ_REQUIRE(!(impl >= 2 && impl != 5 && impl != 6 && impl != 7 && impl != 8 && !mfma_ok), DVQ_ESHAPE, "igemm_tn: MFMA path needs lda, ldb multiples of %d", VN);
-    const bool use_mfma = impl >= 2 || (impl == 0 && mfma_ok && (int64_t)p.Mred >= 256);
-    if (use_mfma) {
-        p.itiles = (int)cdiv64(p.I, TILE);
-        p.jtiles = (int)cdiv64(p.J, TILE);
-        p.thin = (p.conv && sizeof(T) == 2 && impl != 3 && p.J == 8 && p.taps <= 16 && p.taps > 1) ? 1 : 0;
-        const int tapblk = p.thin ? 1 : p.taps;
-        const int64_t tiles = (int64_t)p.itiles * p.jtiles * tapblk * batch;
-        // 512 resident workgroups (2 per CU): aim at two full rounds, never slightly more than a round
-        // (thin: every workgroup ends with I x taps x 8 atomics on one small tile -- one round of 256 is enough)
-        int64_t splits = (p.thin ? 256 : 1024) / tiles;
-        const int64_t max_splits = cdiv64(p.Mred, 4 * BK);
-        if (splits > max_splits) splits = max_splits;
-        // opt-in: no fp32 atomics from more than one workgroup per output element.  bf16 operands only (the training path): the fp32
-        // parity-mode kernel keeps its splits and atomics (unsplit it would put 9 workgroups on a 4-M-row reduction)
-        const bool det = dvq_deterministic() != 0 && sizeof(T) == 2;
-        if (splits < 1) splits = 1;
-        int64_t mps = cdiv64(cdiv64(p.Mred, splits), BK) * BK;
-        splits = cdiv64(p.Mred, mps);
-        p.m_per_split = (int)mps;
-        p.nsplit = (int)splits;
-        dim3 grid((unsigned)(p.itiles * p.jtiles * tapblk * splits), 1, (unsigned)batch);
-        // 1 x 1 weight gradients run on the patch kernel too, not on the 256-wide plain-GEMM kernel: 65536 x 256 x 256
-        // 31 against 52 us, 16384 x 512 x 512 30 against 40 us -- a 256 x 256 tile leaves 64 workgroups for the whole chip
-        if (sizeof(T) == 2 && (impl == 0 || impl == 6) && !p.conv && p.taps == 1 && p.I >= 256 && p.J >= 256 && p.Mred >= 1024 &&
-            p.I % 8 == 0 && p.J % 8 == 0 && (int64_t)p.Mred * p.lda < (1ll << 30) && (int64_t)p.Mred * p.ldb < (1ll << 30) &&
-            (p.sA * 2) % 4 == 0 && (p.sB * 2) % 4 == 0) {
-            // large plain weight-gradient GEMMs: 256 x 256 tiles, pipelined main loop; ~one resident workgroup per CU
-            p.itiles = (int)cdiv64(p.I, 256);
-            p.jtiles = (int)cdiv64(p.J, 256);
-            const int64_t wtiles = (int64_t)p.itiles * p.jtiles * batch;
-            // workgroups a wide TN product aims at.  Round 5: 128, not one per CU -- these weight gradients run on the side stream beside
-            // the input-gradient GEMMs (layers.Linear.bwd), so half a chip's worth of workgroups is what they get anyway, and half the
-            // splits mean half the partials to write and fold: StackGPT p6c18 step 79.9 -> 77.9 ms (64: 81.3 ms; same-box A/B,
-            // profiles/r05_stage2_ab.txt).
-            constexpr int wide_wgs = 128;
-            int64_t wsplits = wtiles >= wide_wgs ? 1 : wide_wgs / wtiles;
-            // >= 16 stages per workgroup: prologue, partial-tile store and fold amortised (8 / 4 / 32 measured slower on the 1 x 1
-            // weight gradients: 60 / 95 / 66 against 52 us at 65536 x 256 x 256)
-            const int64_t wmax = cdiv64(p.Mred, 16 * BK);
-            if (wsplits > wmax) wsplits = wmax;
-            const int64_t wmps = cdiv64(cdiv64(p.Mred, wsplits), BK) * BK;
-            p.m_per_split = (int)wmps;
-            p.nsplit = (int)cdiv64(p.Mred, wmps);
-            int64_t ws_bytes = 0;
-            char* wsp = (char*)dvq_workspace_stream(s, &ws_bytes);
-            const int64_t need = (int64_t)p.nsplit * wtiles * 65536 * 4 + (int64_t)p.nsplit * p.itiles * 256 * 4;
-            if (wsp != nullptr && ws_bytes >= need && (p.nsplit > 2 || (det && p.nsplit > 1)) && batch == 1) {     // many splits per tile: partials + fold, no atomics
-                p.ws = (float*)wsp;
-                p.ws_bias = (float*)(wsp + (int64_t)p.nsplit * wtiles * 65536 * 4);
-            } else if (det && p.nsplit > 1) {            // no scratch for the partials: one workgroup per tile walks the whole reduction
-                p.m_per_split = (int)(cdiv64(p.Mred, BK) * BK);
-                p.nsplit = 1;
-            }
-            // the 8-phase main loop (DMA queue never drained) unless impl 6 asks for the per-stage-drain kernel (tests) or a stride is
-            // not a multiple of 16 bytes
-            if (impl == 0 && (p.sA * 2) % 16 == 0 && (p.sB * 2) % 16 == 0) {
-                dvq_note_kernel("gemm_tn_8phase_kernel");
-                dvq_ensure_dynamic_lds((const void*)gemm_tn_8phase_kernel, 8 * 64 * 256);
-                gemm_tn_8phase_kernel<<<dim3((unsigned)(p.itiles * p.jtiles * p.nsplit), 1, (unsigned)batch), dim3(512), 8 * 64 * 256, s>>>(p);
-                DVQ_CHECK_LAUNCH("gemm_tn_8phase");
-            } else {
-                dvq_note_kernel("gemm_tn_wide_pipe_kernel");
-                dvq_ensure_dynamic_lds((const void*)gemm_tn_wide_pipe_kernel, 2 * WTSTG);
-                gemm_tn_wide_pipe_kernel<<<dim3((unsigned)(p.itiles * p.jtiles * p.nsplit), 1, (unsigned)batch), dim3(512), 2 * WTSTG, s>>>(p);
-                DVQ_CHECK_LAUNCH("gemm_tn_wide_pipe");
-            }
-            if (p.ws != nullptr) {
-                gemm_tn_wide_reduce_kernel<<<dim3((unsigned)(wtiles * 256)), dim3(256), 0, s>>>(p);
-                DVQ_CHECK_LAUNCH("gemm_tn_wide_reduce");
-            }
-            return DVQ_OK;
-        }
-        if (sizeof(T) == 2 && p.conv && !p.thin && impl == 0 && batch == 1 && p.I % 8 == 0 && p.J % 8 == 0 &&
-            p.pad_t <= 8 && p.pad_l <= 8 && p.Mred % (p.DH * p.DW) == 0 &&
-            (int64_t)(8 * p.stride + p.taps / p.KW + 10) * p.SW * p.ldb * 2 < (1ll << 30) && (int64_t)8 * p.DW * p.lda * 2 < (1ll << 30)) {
-            // 8 x 8 output-pixel patches as reduction stages (conv_tn_patch_kernel): split over patch ranges
-            const int64_t PH = cdiv64(p.DH, 8), PW = cdiv64(p.DW, 8);
-            const int64_t npatch = (p.Mred / ((int64_t)p.DH * p.DW)) * PH * PW;
-            const int64_t ptiles = (int64_t)p.itiles * p.jtiles * p.taps;
-            int64_t psplits = 512 / ptiles;          // workgroups the patch kernel aims at (sweep: 128 / 256 / 512 / 1024, profiles/)
-            if (psplits > npatch / 16) psplits = npatch / 16;       // >= 16 stages per workgroup: the 64-KiB atomic flush amortised
-            if (psplits < 1) psplits = 1;
-            int64_t pps = cdiv64(npatch, psplits);
-            p.m_per_split = (int)pps;
-            p.nsplit = (int)cdiv64(npatch, pps);
-            int64_t dspan = 0;
-            const bool dfold = det && p.nsplit > 1 && tn_det_setup(p, batch, s, &dspan);      // partials + fold in split order
-            if (det && p.nsplit > 1 && !dfold) {                                             // no scratch / strided C: unsplit
-                p.m_per_split = (int)npatch;
-                p.nsplit = 1;
-            }
-            dvq_note_kernel("conv_tn_patch_kernel");
-            dvq_ensure_dynamic_lds((const void*)conv_tn_patch_kernel, 2 * TSTAGEB);
-            conv_tn_patch_kernel<<<dim3((unsigned)(ptiles * p.nsplit)), dim3(256), 2 * TSTAGEB, s>>>(p);
-            DVQ_CHECK_LAUNCH("conv_tn_patch");
-            if (dfold) {
-                tn_det_fold(p, dspan, s);
-                DVQ_CHECK_LAUNCH("tn_det_fold");
-            }
-            return DVQ_OK;
-        }
-        int64_t gspan = 0;
-        bool gfold = false;
-        if (det && p.nsplit > 1) {
-            gfold = sizeof(T) == 2 && impl != 3 && tn_det_setup(p, batch, s, &gspan);          // (the transpose-read kernel stores partials)
-            if (!gfold) {                                                                    // other kernels / no scratch: unsplit
-                p.m_per_split = (int)(cdiv64(p.Mred, BK) * BK);
-                p.nsplit = 1;
-                grid = dim3((unsigned)(p.itiles * p.jtiles * tapblk), 1, (unsigned)batch);
-            }
-        }
-        dvq_note_kernel(sizeof(T) == 2 && impl != 3 ? "igemm_tn_tr_kernel" : "igemm_tn_kernel");
-        if (sizeof(T) == 2 && impl != 3) {      // LDS-DMA + transpose-read kernel
-            if (p.conv) {
-                dvq_ensure_dynamic_lds((const void*)igemm_tn_tr_kernel<true>, 2 * TSTAGEB);
-                igemm_tn_tr_kernel<true><<<grid, dim3(256), 2 * TSTAGEB, s>>>(p);
-            } else {
-                dvq_ensure_dynamic_lds((const void*)igemm_tn_tr_kernel<false>, 2 * TSTAGEB);
-                igemm_tn_tr_kernel<false><<<grid, dim3(256), 2 * TSTAGEB, s>>>(p);
-            }
-        } else if (sizeof(T) == 4 && p.split3) {          // fp32x3
-            constexpr bool F32 = sizeof(T) == 4;
-            if (p.conv) {
-                dvq_ensure_dynamic_lds((const void*)igemm_tn_kernel<T, true, F32>, 2 * GSTAGEB);
-                igemm_tn_kernel<T, true, F32><<<grid, dim3(256), 2 * GSTAGEB, s>>>(p);
-            } else {
-                dvq_ensure_dynamic_lds((const void*)igemm_tn_kernel<T, false, F32>, 2 * GSTAGEB);
-                igemm_tn_kernel<T, false, F32><<<grid, dim3(256), 2 * GSTAGEB, s>>>(p);
-            }
-        } else if (p.conv) {
-            dvq_ensure_dynamic_lds((const void*)igemm_tn_kernel<T, true>, 2 * GSTAGEB);
-            igemm_tn_kernel<T, true><<<grid, dim3(256), 2 * GSTAGEB, s>>>(p);
-        } else {
-            dvq_ensure_dynamic_lds((const void*)igemm_tn_kernel<T, false>, 2 * GSTAGEB);
-            igemm_tn_kernel<T, false><<<grid, dim3(256), 2 * GSTAGEB, s>>>(p);
-        }
-        DVQ_CHECK_LAUNCH("igemm_tn");
-        if (gfold) {
-            tn_det_fold(p, gspan, s);
-            DVQ_CHECK_LAUNCH("tn_det_fold");
-        }
-    } else {
-        int64_t nout = (int64_t)p.I * p.taps * p.J + (p.colsumA ? p.I : 0);
-        unsigned blocks = (unsigned)(cdiv64(nout, 4) < 8192 ? cdiv64(nout, 4) : 8192);
-        dvq_note_kernel("naive_tn_kernel");
-        naive_tn_kernel<T><<<dim3(blocks, 1, (unsigned)batch), dim3(256), 0, s>>>(p);
-        DVQ_CHECK_LAUNCH("naive_tn");
+    const bool mfma_ok = p.lda % VN == 0 && p.ldb % VN == 0 && p.sA % VN == 0 && p.sB % VN == 0;
+    DVQ_REQUIRE(mfma_ok || impl < DVQ_IMPL_MFMA || (impl_preferred(impl) && impl != DVQ_IMPL_8PHASE), DVQ_ESHAPE,
+                "igemm_tn: MFMA path needs lda, ldb multiples of %d", VN);
+    const bool use_mfma = impl >= DVQ_IMPL_MFMA || (impl == DVQ_IMPL_AUTO && mfma_ok && (int64_t)p.Mred >= 256);
+    if (!use_mfma) return launch_tn_naive<T>(p, batch, s);
+    // the transpose-read kernel takes every bf16 product except under DVQ_IMPL_REGSTAGE
+    const bool tr = sizeof(T) == 2 && impl != DVQ_IMPL_REGSTAGE;
+    p.itiles = (int)cdiv64(p.I, TILE);
+    p.jtiles = (int)cdiv64(p.J, TILE);
+    p.thin = (p.conv && tr && p.J == 8 && p.taps <= 16 && p.taps > 1) ? 1 : 0;
+    // opt-in: no fp32 atomics from more than one workgroup per output element.  bf16 operands only (the training path): the fp32
+    // parity-mode kernel keeps its splits and atomics (unsplit it would put 9 workgroups on a 4-M-row reduction)
+    const bool det = dvq_deterministic() != 0 && sizeof(T) == 2;
+    if constexpr (sizeof(T) == 2) {
+        // DVQ_IMPL_WIDE_PIPE asks for the per-stage-drain kernel (tests) in place of the 8-phase one
+        if ((impl == DVQ_IMPL_AUTO || impl == DVQ_IMPL_WIDE_PIPE) && tn_wide_ok(p))
+            return launch_tn_wide(p, batch, det, impl == DVQ_IMPL_AUTO && (p.sA * 2) % 16 == 0 && (p.sB * 2) % 16 == 0, s);
+        if (impl == DVQ_IMPL_AUTO && batch == 1 && tn_patch_ok(p)) return launch_tn_patch(p, batch, det, s);
     }
-    return DVQ_OK;
+    return launch_tn_tiles<T>(p, batch, tr, det, s);
 }
 
 int conv_check(const dvq_conv_desc* d, const char* who) {
@@ -3195,36 +3289,78 @@ static int split_concat3(const float* x, void* out, int64_t rows, int64_t c, int
 
 static bool halo_eligible(const dvq_conv_desc* d) {
     return d->dtype == DVQ_BF16 && d->KH == 3 && d->KW == 3 && d->stride == 1 && d->pad_t == 1 && d->pad_l == 1 &&
-           d->OH == d->H && d->OW == d->W && (d->impl == 0 || d->impl == 4);
+           d->OH == d->H && d->OW == d->W && (d->impl == DVQ_IMPL_AUTO || d->impl == DVQ_IMPL_HALO);
+}
+
+// NtParams of a convolution pass.  MODE_FWD: A = x streams d->Cin channels, C = y is the output map; MODE_TCONV (input gradient): A = dy
+// streams d->Cout channels, C is the gradient at the LOGICAL input resolution (a folded upsample is summed down by the caller).
+static NtParams conv_nt_params(const dvq_conv_desc* d, int mode, const void* A, const void* B, void* C) {
+    const bool fwd = mode == MODE_FWD;
+    const int64_t cs = fwd ? d->Cin : d->Cout, co = fwd ? d->Cout : d->Cin;      // channels streamed / produced
+    NtParams p{};
+    p.A = A; p.B = B; p.C = C;
+    p.mode = mode;
+    p.M = (int)(fwd ? d->N * d->OH * d->OW : d->N * d->H * d->W); p.Ncols = (int)co; p.Ktot = (int)(d->KH * d->KW * cs);
+    p.lda = cs; p.ldb = p.Ktot; p.ldc = co;
+    if (fwd) {
+        p.SH = (int)(d->H >> d->upsample); p.SW = (int)(d->W >> d->upsample);
+        p.LH = (int)d->H; p.LW = (int)d->W; p.DH = (int)d->OH; p.DW = (int)d->OW;
+        p.up = d->upsample;
+    } else {
+        p.SH = (int)d->OH; p.SW = (int)d->OW; p.LH = (int)d->OH; p.LW = (int)d->OW;
+        p.DH = (int)d->H; p.DW = (int)d->W;
+    }
+    p.KW = d->KW; p.stride = d->stride; p.pad_t = d->pad_t; p.pad_l = d->pad_l;
+    p.alpha = 1.f; p.act_slope = 1.f;
+    return p;
+}
+
+// TnParams of a convolution's weight gradient; rows / columns beyond the real channel counts are padding
+static TnParams conv_tn_params(const dvq_conv_desc* d, const void* x, const void* dy, int64_t cin_real, int64_t cout_real, float* grad,
+                               float* dbias, int ohwi) {
+    TnParams p{};
+    p.A = dy; p.B = x; p.C = grad; p.colsumA = dbias;
+    p.conv = 1;
+    p.Mred = (int)(d->N * d->OH * d->OW); p.I = (int)cout_real; p.J = (int)d->Cin;
+    p.lda = d->Cout; p.ldb = d->Cin; p.ldc = (int64_t)d->KH * d->KW * d->Cin;
+    p.taps = d->KH * d->KW;
+    p.SH = (int)(d->H >> d->upsample); p.SW = (int)(d->W >> d->upsample);
+    p.LH = (int)d->H; p.LW = (int)d->W; p.DH = (int)d->OH; p.DW = (int)d->OW;
+    p.KW = d->KW; p.stride = d->stride; p.pad_t = d->pad_t; p.pad_l = d->pad_l; p.up = d->upsample;
+    p.c_oihw = ohwi ? 0 : 1; p.Jc = (int)cin_real;
+    if (ohwi) p.ldc = (int64_t)d->KH * d->KW * cin_real;
+    return p;
+}
+
+static NtParams gemm_nt_params(const void* A, const void* B, void* C, int64_t M, int64_t N, int64_t K, int64_t lda, int64_t ldb, int64_t ldc,
+                               int64_t sA, int64_t sB, int64_t sC, float alpha, const float* bias, int bias_mode) {
+    NtParams p{};
+    p.A = A; p.B = B; p.C = C; p.R = nullptr; p.bias = bias;
+    p.mode = MODE_GEMM;
+    p.M = (int)M; p.Ncols = (int)N; p.Ktot = (int)K;
+    p.lda = lda; p.ldb = ldb; p.ldc = ldc;
+    p.stride = 1; p.KW = 1;
+    p.alpha = alpha; p.bias_mode = bias_mode;
+    p.act_slope = 1.f;
+    p.sA = sA; p.sB = sB; p.sC = sC;
+    return p;
+}
+
+static TnParams gemm_tn_params(const void* A, const void* B, float* C, float* colsum, int64_t Mred, int64_t I, int64_t J, int64_t lda,
+                               int64_t ldb, int64_t ldc, int64_t sA, int64_t sB, int64_t sC) {
+    TnParams p{};
+    p.A = A; p.B = B; p.C = C; p.colsumA = colsum;
+    p.conv = 0;
+    p.Mred = (int)Mred; p.I = (int)I; p.J = (int)J;
+    p.lda = lda; p.ldb = ldb; p.ldc = ldc;
+    p.taps = 1; p.KW = 1; p.stride = 1;
+    p.Jc = p.J;
+    p.sA = sA; p.sB = sB; p.sC = sC;
+    return p;
 }
 
 // =================================================================================================
 extern "C" {
-
-int dvq_conv2d_fwd_ex(const dvq_conv_desc* d, const void* x, const void* w, const float* bias, const void* residual,
-                      void* y, const float* gn_scale_shift, double* out_stats, int out_groups, dvq_stream_t stream);
-int dvq_conv2d_wgrad_oihw_ex(const dvq_conv_desc* d, const void* x, const void* dy, int64_t cin_real, int64_t cout_real,
-                             float* grad_oihw, float* dbias, int ohwi, const float* gn_scale_shift, dvq_stream_t stream);
-
-int dvq_conv2d_fwd(const dvq_conv_desc* d, const void* x, const void* w, const float* bias, const void* residual,
-                   void* y, dvq_stream_t stream) {
-    return dvq_conv2d_fwd_ex(d, x, w, bias, residual, y, nullptr, nullptr, 0, stream);
-}
-
-static int conv2d_fwd_impl(const dvq_conv_desc* d, const void* x, const void* w, const float* bias, const void* residual,
-                           void* y, const float* gn_scale_shift, double* out_stats, int out_groups, int act,
-                           dvq_stream_t stream);
-
-int dvq_conv2d_fwd_ex(const dvq_conv_desc* d, const void* x, const void* w, const float* bias, const void* residual,
-                      void* y, const float* gn_scale_shift, double* out_stats, int out_groups, dvq_stream_t stream) {
-    return conv2d_fwd_impl(d, x, w, bias, residual, y, gn_scale_shift, out_stats, out_groups, DVQ_ACT_NONE, stream);
-}
-
-int dvq_conv2d_fwd_act(const dvq_conv_desc* d, const void* x, const void* w, const float* bias, void* y, int act,
-                       dvq_stream_t stream) {
-    DVQ_REQUIRE(act == DVQ_ACT_NONE || act == DVQ_ACT_RELU || act == DVQ_ACT_LRELU, DVQ_EINVAL, "dvq_conv2d_fwd_act: bad act");
-    return conv2d_fwd_impl(d, x, w, bias, nullptr, y, nullptr, nullptr, 0, act, stream);
-}
 
 int dvq_conv3x3_fused_ok(const dvq_conv_desc* d) {
     // shapes on which the halo kernels (and therefore the fused GroupNorm prologue / statistics epilogue) run
@@ -3232,12 +3368,14 @@ int dvq_conv3x3_fused_ok(const dvq_conv_desc* d) {
            d->N * d->H * d->W * (d->Cin > d->Cout ? d->Cin : d->Cout) < (1ll << 31);
 }
 
-static int conv2d_fwd_impl(const dvq_conv_desc* d, const void* x, const void* w, const float* bias, const void* residual,
-                           void* y, const float* gn_scale_shift, double* out_stats, int out_groups, int act,
-                           dvq_stream_t stream) {
+int dvq_conv2d_fwd(const dvq_conv_desc* d, const void* x, const void* w, const float* bias, const void* residual, void* y,
+                   const float* gn_scale_shift, double* out_stats, int out_groups, int act, dvq_stream_t stream) {
     if (int e = conv_check(d, "dvq_conv2d_fwd")) return e;
+    DVQ_REQUIRE(act == DVQ_ACT_NONE || act == DVQ_ACT_RELU || act == DVQ_ACT_LRELU, DVQ_EINVAL, "dvq_conv2d_fwd: bad act");
+    DVQ_REQUIRE(act == DVQ_ACT_NONE || (residual == nullptr && gn_scale_shift == nullptr && out_stats == nullptr), DVQ_EINVAL,
+                "dvq_conv2d_fwd: activation together with residual, gn_scale_shift or out_stats");
     DVQ_REQUIRE(x && w && y, DVQ_EINVAL, "dvq_conv2d_fwd: null pointer");
-    if (halo_eligible(d) && d->impl == 0 && d->Cin == 8 && !d->upsample && residual == nullptr && gn_scale_shift == nullptr &&
+    if (halo_eligible(d) && d->impl == DVQ_IMPL_AUTO && d->Cin == 8 && !d->upsample && residual == nullptr && gn_scale_shift == nullptr &&
         out_stats == nullptr) {          // image heads: 8 (padded) input channels
         const int rc = dvq_conv3x3_thin_k_try(x, w, bias, y, d->N, d->H, d->W, d->Cout, 0, act_slope_of(act), (hipStream_t)stream);
         if (rc != 0) return rc < 0 ? rc : DVQ_OK;
@@ -3249,17 +3387,10 @@ static int conv2d_fwd_impl(const dvq_conv_desc* d, const void* x, const void* w,
         if (rc != 0) return rc < 0 ? rc : DVQ_OK;
     }
     DVQ_REQUIRE(gn_scale_shift == nullptr && out_stats == nullptr, DVQ_ESHAPE,
-                "dvq_conv2d_fwd_ex: fused GroupNorm needs a shape accepted by dvq_conv3x3_fused_ok");
-    DVQ_REQUIRE(d->impl != 4, DVQ_ESHAPE, "dvq_conv2d_fwd: shape not eligible for the halo kernel");
-    NtParams p{};
-    p.A = x; p.B = w; p.C = y; p.R = residual; p.bias = bias;
-    p.mode = MODE_FWD;
-    p.M = (int)(d->N * d->OH * d->OW); p.Ncols = (int)d->Cout; p.Ktot = (int)(d->KH * d->KW * d->Cin);
-    p.lda = d->Cin; p.ldb = p.Ktot; p.ldc = d->Cout;
-    p.SH = (int)(d->H >> d->upsample); p.SW = (int)(d->W >> d->upsample);
-    p.LH = (int)d->H; p.LW = (int)d->W; p.DH = (int)d->OH; p.DW = (int)d->OW;
-    p.KW = d->KW; p.stride = d->stride; p.pad_t = d->pad_t; p.pad_l = d->pad_l; p.up = d->upsample;
-    p.alpha = 1.f; p.bias_mode = bias ? 1 : 0;
+                "dvq_conv2d_fwd: fused GroupNorm needs a shape accepted by dvq_conv3x3_fused_ok");
+    DVQ_REQUIRE(d->impl != DVQ_IMPL_HALO, DVQ_ESHAPE, "dvq_conv2d_fwd: shape not eligible for the halo kernel");
+    NtParams p = conv_nt_params(d, MODE_FWD, x, w, y);
+    p.R = residual; p.bias = bias; p.bias_mode = bias ? 1 : 0;
     p.act_slope = act_slope_of(act);
     if (d->dtype == DVQ_F32) return launch_nt<float>(p, 1, d->impl, (hipStream_t)stream);
     return launch_nt<bf16_t>(p, 1, d->impl, (hipStream_t)stream);
@@ -3267,23 +3398,19 @@ static int conv2d_fwd_impl(const dvq_conv_desc* d, const void* x, const void* w,
 
 int dvq_sumpool2x2(const void* in, int dtype, int64_t N, int64_t h, int64_t w, int64_t C, void* out, dvq_stream_t stream);
 
-int dvq_conv2d_dgrad(const dvq_conv_desc* d, const void* dy, const void* wt, void* dx, void* ws, dvq_stream_t stream) {
-    return dvq_conv2d_dgrad_mask(d, dy, wt, dx, ws, nullptr, DVQ_ACT_NONE, stream);
-}
-
-int dvq_conv2d_dgrad_mask(const dvq_conv_desc* d, const void* dy, const void* wt, void* dx, void* ws, const void* mask,
-                          int mask_act, dvq_stream_t stream) {
+int dvq_conv2d_dgrad(const dvq_conv_desc* d, const void* dy, const void* wt, void* dx, void* ws, const void* mask, int mask_act,
+                     dvq_stream_t stream) {
     if (int e = conv_check(d, "dvq_conv2d_dgrad")) return e;
     DVQ_REQUIRE(mask == nullptr || ((mask_act == DVQ_ACT_RELU || mask_act == DVQ_ACT_LRELU) && !d->upsample), DVQ_EINVAL,
-                "dvq_conv2d_dgrad_mask: mask needs act in {relu, lrelu} and no folded upsample");
+                "dvq_conv2d_dgrad: mask needs act in {relu, lrelu} and no folded upsample");
     DVQ_REQUIRE(dy && wt && dx && (!d->upsample || ws), DVQ_EINVAL, "dvq_conv2d_dgrad: null pointer");
-    if (d->dtype == DVQ_BF16 && d->impl == 0 && d->KH == 4 && d->KW == 4 && d->stride == 2 && d->pad_t == 1 && d->pad_l == 1 &&
+    if (d->dtype == DVQ_BF16 && d->impl == DVQ_IMPL_AUTO && d->KH == 4 && d->KW == 4 && d->stride == 2 && d->pad_t == 1 && d->pad_l == 1 &&
         d->Cin == 8 && !d->upsample && mask == nullptr && d->H == 2 * d->OH && d->W == 2 * d->OW) {
         // input gradient of the PatchGAN's first conv (3 image channels): thin transposed conv
         const int rc = dvq_tconv4x4s2_thin_try(dy, wt, dx, d->N, d->OH, d->OW, d->Cout, 4, (hipStream_t)stream);
         if (rc != 0) return rc < 0 ? rc : DVQ_OK;
     }
-    if (halo_eligible(d) && d->impl == 0 && d->Cout == 8 && !d->upsample && mask == nullptr) {
+    if (halo_eligible(d) && d->impl == DVQ_IMPL_AUTO && d->Cout == 8 && !d->upsample && mask == nullptr) {
         // dgrad of the 3-channel output conv: 8 gradient channels in, Cin out, taps reversed
         const int rc = dvq_conv3x3_thin_k_try(dy, wt, nullptr, dx, d->N, d->H, d->W, d->Cin, 1, 1.f, (hipStream_t)stream);
         if (rc != 0) return rc < 0 ? rc : DVQ_OK;
@@ -3296,17 +3423,9 @@ int dvq_conv2d_dgrad_mask(const dvq_conv_desc* d, const void* dy, const void* wt
         if (rc < 0) return rc;
         if (rc == 1) return d->upsample ? dvq_sumpool2x2(ws, d->dtype, d->N, d->H / 2, d->W / 2, d->Cin, dx, stream) : DVQ_OK;
     }
-    DVQ_REQUIRE(d->impl != 4, DVQ_ESHAPE, "dvq_conv2d_dgrad: shape not eligible for the halo kernel");
-    NtParams p{};
-    p.A = dy; p.B = wt; p.C = d->upsample ? ws : dx; p.R = nullptr; p.bias = nullptr;
-    p.mode = MODE_TCONV;
-    p.M = (int)(d->N * d->H * d->W); p.Ncols = (int)d->Cin; p.Ktot = (int)(d->KH * d->KW * d->Cout);
-    p.lda = d->Cout; p.ldb = p.Ktot; p.ldc = d->Cin;
-    p.SH = (int)d->OH; p.SW = (int)d->OW; p.LH = (int)d->OH; p.LW = (int)d->OW;
-    p.DH = (int)d->H; p.DW = (int)d->W;
-    p.KW = d->KW; p.stride = d->stride; p.pad_t = d->pad_t; p.pad_l = d->pad_l; p.up = 0;
-    p.alpha = 1.f; p.bias_mode = 0;
-    p.act_slope = 1.f; p.R = mask; p.res_mask = mask != nullptr; p.mask_slope = act_slope_of(mask_act);
+    DVQ_REQUIRE(d->impl != DVQ_IMPL_HALO, DVQ_ESHAPE, "dvq_conv2d_dgrad: shape not eligible for the halo kernel");
+    NtParams p = conv_nt_params(d, MODE_TCONV, dy, wt, d->upsample ? ws : dx);
+    p.R = mask; p.res_mask = mask != nullptr; p.mask_slope = act_slope_of(mask_act);
     int rc = d->dtype == DVQ_F32 ? launch_nt<float>(p, 1, d->impl, (hipStream_t)stream)
                                  : launch_nt<bf16_t>(p, 1, d->impl, (hipStream_t)stream);
     if (rc) return rc;
@@ -3314,58 +3433,19 @@ int dvq_conv2d_dgrad_mask(const dvq_conv_desc* d, const void* dy, const void* wt
     return DVQ_OK;
 }
 
-int dvq_conv2d_wgrad(const dvq_conv_desc* d, const void* x, const void* dy, float* dw, float* dbias,
-                     dvq_stream_t stream) {
+int dvq_conv2d_wgrad(const dvq_conv_desc* d, const void* x, const void* dy, int64_t cin_real, int64_t cout_real, float* grad,
+                     float* dbias, int ohwi, const float* gn_scale_shift, dvq_stream_t stream) {
     if (int e = conv_check(d, "dvq_conv2d_wgrad")) return e;
-    DVQ_REQUIRE(x && dy && dw, DVQ_EINVAL, "dvq_conv2d_wgrad: null pointer");
+    DVQ_REQUIRE(x && dy && grad && cin_real > 0 && cin_real <= d->Cin && cout_real > 0 && cout_real <= d->Cout,
+                DVQ_EINVAL, "dvq_conv2d_wgrad: bad arguments");
     if (halo_eligible(d)) {
-        const int rc = dvq_conv3x3_halo_wgrad_try(x, dy, dw, dbias, d->N, d->H, d->W, d->Cin, d->Cout, d->Cin, d->Cout, 0,
-                                                  d->upsample, nullptr, (hipStream_t)stream);
-        if (rc != 0) return rc < 0 ? rc : DVQ_OK;
-    }
-    DVQ_REQUIRE(d->impl != 4, DVQ_ESHAPE, "dvq_conv2d_wgrad: shape not eligible for the halo kernel");
-    TnParams p{};
-    p.A = dy; p.B = x; p.C = dw; p.colsumA = dbias;
-    p.conv = 1;
-    p.Mred = (int)(d->N * d->OH * d->OW); p.I = (int)d->Cout; p.J = (int)d->Cin;
-    p.lda = d->Cout; p.ldb = d->Cin; p.ldc = (int64_t)d->KH * d->KW * d->Cin;
-    p.taps = d->KH * d->KW;
-    p.SH = (int)(d->H >> d->upsample); p.SW = (int)(d->W >> d->upsample);
-    p.LH = (int)d->H; p.LW = (int)d->W; p.DH = (int)d->OH; p.DW = (int)d->OW;
-    p.KW = d->KW; p.stride = d->stride; p.pad_t = d->pad_t; p.pad_l = d->pad_l; p.up = d->upsample;
-    p.Jc = p.J;
-    if (d->dtype == DVQ_F32) return launch_tn<float>(p, 1, d->impl, (hipStream_t)stream);
-    return launch_tn<bf16_t>(p, 1, d->impl, (hipStream_t)stream);
-}
-
-int dvq_conv2d_wgrad_oihw(const dvq_conv_desc* d, const void* x, const void* dy, int64_t cin_real, int64_t cout_real,
-                          float* grad_oihw, float* dbias, int ohwi, dvq_stream_t stream) {
-    return dvq_conv2d_wgrad_oihw_ex(d, x, dy, cin_real, cout_real, grad_oihw, dbias, ohwi, nullptr, stream);
-}
-
-int dvq_conv2d_wgrad_oihw_ex(const dvq_conv_desc* d, const void* x, const void* dy, int64_t cin_real, int64_t cout_real,
-                             float* grad_oihw, float* dbias, int ohwi, const float* gn_scale_shift, dvq_stream_t stream) {
-    if (int e = conv_check(d, "dvq_conv2d_wgrad_oihw")) return e;
-    DVQ_REQUIRE(x && dy && grad_oihw && cin_real > 0 && cin_real <= d->Cin && cout_real > 0 && cout_real <= d->Cout,
-                DVQ_EINVAL, "dvq_conv2d_wgrad_oihw: bad arguments");
-    if (halo_eligible(d)) {
-        const int rc = dvq_conv3x3_halo_wgrad_try(x, dy, grad_oihw, dbias, d->N, d->H, d->W, d->Cin, d->Cout, cin_real,
+        const int rc = dvq_conv3x3_halo_wgrad_try(x, dy, grad, dbias, d->N, d->H, d->W, d->Cin, d->Cout, cin_real,
                                                   cout_real, ohwi ? 0 : 1, d->upsample, gn_scale_shift, (hipStream_t)stream);
         if (rc != 0) return rc < 0 ? rc : DVQ_OK;
     }
-    DVQ_REQUIRE(gn_scale_shift == nullptr, DVQ_ESHAPE, "dvq_conv2d_wgrad_oihw_ex: fused GroupNorm needs a shape accepted by dvq_conv3x3_fused_ok");
-    DVQ_REQUIRE(d->impl != 4, DVQ_ESHAPE, "dvq_conv2d_wgrad_oihw: shape not eligible for the halo kernel");
-    TnParams p{};
-    p.A = dy; p.B = x; p.C = grad_oihw; p.colsumA = dbias;
-    p.conv = 1;
-    p.Mred = (int)(d->N * d->OH * d->OW); p.I = (int)cout_real; p.J = (int)d->Cin;   // rows/cols beyond the real counts are padding
-    p.lda = d->Cout; p.ldb = d->Cin; p.ldc = (int64_t)d->KH * d->KW * d->Cin;
-    p.taps = d->KH * d->KW;
-    p.SH = (int)(d->H >> d->upsample); p.SW = (int)(d->W >> d->upsample);
-    p.LH = (int)d->H; p.LW = (int)d->W; p.DH = (int)d->OH; p.DW = (int)d->OW;
-    p.KW = d->KW; p.stride = d->stride; p.pad_t = d->pad_t; p.pad_l = d->pad_l; p.up = d->upsample;
-    p.c_oihw = ohwi ? 0 : 1; p.Jc = (int)cin_real;
-    if (ohwi) p.ldc = (int64_t)d->KH * d->KW * cin_real;
+    DVQ_REQUIRE(gn_scale_shift == nullptr, DVQ_ESHAPE, "dvq_conv2d_wgrad: fused GroupNorm needs a shape accepted by dvq_conv3x3_fused_ok");
+    DVQ_REQUIRE(d->impl != DVQ_IMPL_HALO, DVQ_ESHAPE, "dvq_conv2d_wgrad: shape not eligible for the halo kernel");
+    const TnParams p = conv_tn_params(d, x, dy, cin_real, cout_real, grad, dbias, ohwi);
     if (d->dtype == DVQ_F32) return launch_tn<float>(p, 1, d->impl, (hipStream_t)stream);
     return launch_tn<bf16_t>(p, 1, d->impl, (hipStream_t)stream);
 }
@@ -3461,9 +3541,9 @@ int dvq_conv2d_wgrad_oihw_x3(const dvq_conv_desc* d, const void* x, const void* 
         if (rc == 1) return DVQ_OK;
     }
     // small terms first; the bias gradient (column sums of dy) is the sum over BOTH dy planes, taken on the two launches that read x_hi
-    if (int e = dvq_conv2d_wgrad_oihw_ex(&b, xl, yh, cin_real, cout_real, grad_oihw, nullptr, ohwi, nullptr, stream)) return e;
-    if (int e = dvq_conv2d_wgrad_oihw_ex(&b, xh, yl, cin_real, cout_real, grad_oihw, dbias, ohwi, nullptr, stream)) return e;
-    return dvq_conv2d_wgrad_oihw_ex(&b, xh, yh, cin_real, cout_real, grad_oihw, dbias, ohwi, nullptr, stream);
+    if (int e = dvq_conv2d_wgrad(&b, xl, yh, cin_real, cout_real, grad_oihw, nullptr, ohwi, nullptr, stream)) return e;
+    if (int e = dvq_conv2d_wgrad(&b, xh, yl, cin_real, cout_real, grad_oihw, dbias, ohwi, nullptr, stream)) return e;
+    return dvq_conv2d_wgrad(&b, xh, yh, cin_real, cout_real, grad_oihw, dbias, ohwi, nullptr, stream);
 }
 
 // -------------------------------------------------------------------------------------------------
@@ -3479,7 +3559,7 @@ namespace {
 
 // cs: channels of the streamed operand (x: Cin / dy: Cout), co: channels produced
 bool x3_halo_shape_ok(const dvq_conv_desc* d, int64_t cs, int64_t co) {
-    return d->dtype == DVQ_F32 && d->impl == 0 && d->KH == 3 && d->KW == 3 && d->stride == 1 && d->pad_t == 1 && d->pad_l == 1 &&
+    return d->dtype == DVQ_F32 && d->impl == DVQ_IMPL_AUTO && d->KH == 3 && d->KW == 3 && d->stride == 1 && d->pad_t == 1 && d->pad_l == 1 &&
            d->OH == d->H && d->OW == d->W && d->H % 8 == 0 && d->W % 32 == 0 && cs % 64 == 0 && co >= 4 && co % 4 == 0 &&
            d->N * d->H * d->W * (3 * cs > co ? 3 * cs : co) < (1ll << 31) && co * 27 * cs < (1ll << 31) && d->H * d->W * co * 4 < (1ll << 31);
 }
@@ -3551,17 +3631,9 @@ int dvq_gemm_nt(const void* A, const void* B, void* C, int dtype, int64_t M, int
     DVQ_REQUIRE(M > 0 && N > 0 && K > 0 && batch > 0 && batch <= 65535 && M < (1ll << 31) && N < (1ll << 31), DVQ_ESHAPE,
                 "dvq_gemm_nt: bad shape");
     DVQ_REQUIRE(bias_mode == 0 || bias != nullptr, DVQ_EINVAL, "dvq_gemm_nt: bias_mode without bias");
-    NtParams p{};
-    p.A = A; p.B = B; p.C = C; p.R = nullptr; p.bias = bias;
-    p.mode = MODE_GEMM;
-    p.M = (int)M; p.Ncols = (int)N; p.Ktot = (int)K;
-    p.lda = lda; p.ldb = ldb; p.ldc = ldc;
-    p.stride = 1; p.KW = 1;
-    p.alpha = alpha; p.bias_mode = bias_mode;
-    p.act_slope = 1.f;
-    p.sA = sA; p.sB = sB; p.sC = sC;
-    if (dtype == DVQ_BF16 && impl == 0 && batch == 1 && bias_mode != 2 && M <= 32 && N >= 64 && K >= 64 && K % 8 == 0 && lda % 8 == 0 &&
-        ldb % 8 == 0) {
+    const NtParams p = gemm_nt_params(A, B, C, M, N, K, lda, ldb, ldc, sA, sB, sC, alpha, bias, bias_mode);
+    if (dtype == DVQ_BF16 && impl == DVQ_IMPL_AUTO && batch == 1 && bias_mode != 2 && M <= 32 && N >= 64 && K >= 64 && K % 8 == 0 &&
+        lda % 8 == 0 && ldb % 8 == 0) {
         // single-token Linear layers of the sampler: weight-streaming kernel
         const unsigned blocks = (unsigned)cdiv64(N, 32);
         // waves split K so that each has at most ~16 k-steps = one batch of loads
@@ -3577,63 +3649,18 @@ int dvq_gemm_nt(const void* A, const void* B, void* C, int dtype, int64_t M, int
     return DVQ_EINVAL;
 }
 
-// C = alpha * A B^T (+ bias) + R: the input-gradient GEMM of a Linear layer whose result is ADDED to an existing gradient of the same
-// shape (dx of the key projection onto dx of the query projection, ...) -- the sum leaves the fp32 accumulator, rounded once, instead of
-// through a separate add kernel.  R: same dtype / leading dimension / batch stride as C; may alias C.
-int dvq_gemm_nt_res(const void* A, const void* B, void* C, const void* R, int dtype, int64_t M, int64_t N, int64_t K, int64_t lda,
-                    int64_t ldb, int64_t ldc, int64_t batch, int64_t sA, int64_t sB, int64_t sC, float alpha, const float* bias,
-                    int bias_mode, dvq_stream_t stream) {
-    dvq_note_kernel("");
-    DVQ_REQUIRE(A && B && C && R, DVQ_EINVAL, "dvq_gemm_nt_res: null pointer");
-    DVQ_REQUIRE(M > 0 && N > 0 && K > 0 && batch > 0 && batch <= 65535 && M < (1ll << 31) && N < (1ll << 31), DVQ_ESHAPE,
-                "dvq_gemm_nt_res: bad shape");
-    DVQ_REQUIRE(bias_mode == 0 || bias != nullptr, DVQ_EINVAL, "dvq_gemm_nt_res: bias_mode without bias");
-    NtParams p{};
-    p.A = A; p.B = B; p.C = C; p.R = R; p.bias = bias;
-    p.mode = MODE_GEMM;
-    p.M = (int)M; p.Ncols = (int)N; p.Ktot = (int)K;
-    p.lda = lda; p.ldb = ldb; p.ldc = ldc;
-    p.stride = 1; p.KW = 1;
-    p.alpha = alpha; p.bias_mode = bias_mode;
-    p.act_slope = 1.f;
-    p.sA = sA; p.sB = sB; p.sC = sC;
-    if (dtype == DVQ_F32) return launch_nt<float>(p, batch, 0, (hipStream_t)stream);
-    if (dtype == DVQ_BF16) return launch_nt<bf16_t>(p, batch, 0, (hipStream_t)stream);
-    dvq_set_error("dvq_gemm_nt_res: bad dtype");
-    return DVQ_EINVAL;
-}
-
-static int gemm_tn_impl(const void* A, const void* B, float* C, float* colsum, int dtype, int64_t Mred, int64_t I, int64_t J, int64_t lda,
-                        int64_t ldb, int64_t ldc, int64_t batch, int64_t sA, int64_t sB, int64_t sC, int impl, dvq_stream_t stream) {
+int dvq_gemm_tn(const void* A, const void* B, float* C, float* colsum, int dtype, int64_t Mred, int64_t I, int64_t J, int64_t lda,
+                int64_t ldb, int64_t ldc, int64_t batch, int64_t sA, int64_t sB, int64_t sC, int impl, dvq_stream_t stream) {
     dvq_note_kernel("");
     DVQ_REQUIRE(A && B && C, DVQ_EINVAL, "dvq_gemm_tn: null pointer");
     DVQ_REQUIRE(Mred > 0 && I > 0 && J > 0 && batch > 0 && batch <= 65535 && Mred < (1ll << 31), DVQ_ESHAPE,
                 "dvq_gemm_tn: bad shape");
-    DVQ_REQUIRE(colsum == nullptr || batch == 1, DVQ_EINVAL, "dvq_gemm_tn_colsum: batch must be 1");
-    TnParams p{};
-    p.A = A; p.B = B; p.C = C; p.colsumA = colsum;
-    p.conv = 0;
-    p.Mred = (int)Mred; p.I = (int)I; p.J = (int)J;
-    p.lda = lda; p.ldb = ldb; p.ldc = ldc;
-    p.taps = 1; p.KW = 1; p.stride = 1;
-    p.Jc = p.J;
-    p.sA = sA; p.sB = sB; p.sC = sC;
+    DVQ_REQUIRE(colsum == nullptr || batch == 1, DVQ_EINVAL, "dvq_gemm_tn: colsum needs batch 1");
+    const TnParams p = gemm_tn_params(A, B, C, colsum, Mred, I, J, lda, ldb, ldc, sA, sB, sC);
     if (dtype == DVQ_F32) return launch_tn<float>(p, batch, impl, (hipStream_t)stream);
     if (dtype == DVQ_BF16) return launch_tn<bf16_t>(p, batch, impl, (hipStream_t)stream);
     dvq_set_error("dvq_gemm_tn: bad dtype");
     return DVQ_EINVAL;
-}
-
-int dvq_gemm_tn(const void* A, const void* B, float* C, int dtype, int64_t Mred, int64_t I, int64_t J, int64_t lda,
-                int64_t ldb, int64_t ldc, int64_t batch, int64_t sA, int64_t sB, int64_t sC, int impl,
-                dvq_stream_t stream) {
-    return gemm_tn_impl(A, B, C, nullptr, dtype, Mred, I, J, lda, ldb, ldc, batch, sA, sB, sC, impl, stream);
-}
-
-int dvq_gemm_tn_colsum(const void* A, const void* B, float* C, float* colsum, int dtype, int64_t Mred, int64_t I, int64_t J, int64_t lda,
-                       int64_t ldb, int64_t ldc, int impl, dvq_stream_t stream) {
-    DVQ_REQUIRE(colsum != nullptr, DVQ_EINVAL, "dvq_gemm_tn_colsum: null pointer");
-    return gemm_tn_impl(A, B, C, colsum, dtype, Mred, I, J, lda, ldb, ldc, 1, 0, 0, 0, impl, stream);
 }
 
 }  // extern "C"

@@ -922,7 +922,7 @@ int dvq_set_fp32_split(int on) {
 
 const char* dvq_last_error(void) { return g_err; }
 const char* dvq_last_kernel(void) { return dvq_kernel_note; }
-int dvq_version(void) { return 116; }
+int dvq_version(void) { return 117; }
 
 int dvq_set_workspace(void* ptr, int64_t bytes) {
     DVQ_REQUIRE((ptr == nullptr) == (bytes == 0) && bytes >= 0, DVQ_EINVAL, "dvq_set_workspace: bad arguments");

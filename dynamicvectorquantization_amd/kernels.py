@@ -487,18 +487,8 @@ def conv2d_fwd(d: ConvDesc, x, w, bias, residual=None, gn_ss=None, out_stats=Non
              ("+st" if out_stats is not None else "") + ("+act" if act != ACT_NONE else ""))
     if out_stats is not None:
         ensure_workspace(x.device)        # per-tile statistics partials of the halo kernel
-    if act != ACT_NONE:
-        assert residual is None and gn_ss is None and out_stats is None
-        _timed_conv(fl, nb, "dvq_conv2d_fwd_act", lambda:
-            lib().dvq_conv2d_fwd_act(C.byref(d), _p(x), _p(w), _p(bias), _p(y), act, _s()))
-        return y
-    if gn_ss is not None or out_stats is not None:
-        _timed_conv(fl, nb, "dvq_conv2d_fwd_ex", lambda:
-            lib().dvq_conv2d_fwd_ex(C.byref(d), _p(x), _p(w), _p(bias), _p(residual), _p(y), _p(gn_ss), _p(out_stats),
-                                    out_groups, _s()))
-        return y
     _timed_conv(fl, nb, "dvq_conv2d_fwd", lambda:
-        lib().dvq_conv2d_fwd(C.byref(d), _p(x), _p(w), _p(bias), _p(residual), _p(y), _s()))
+        lib().dvq_conv2d_fwd(C.byref(d), _p(x), _p(w), _p(bias), _p(residual), _p(y), _p(gn_ss), _p(out_stats), out_groups, act, _s()))
     return y
 
 
@@ -517,18 +507,9 @@ def conv2d_dgrad(d: ConvDesc, dy, wt, mask=None, mask_act=ACT_NONE):
             "dvq_conv2d_dgrad_x3"))
         return dx
     _tag(d, "dgrad")
-    _timed_conv(fl, nb, "dvq_conv2d_dgrad_mask", lambda:
-        lib().dvq_conv2d_dgrad_mask(C.byref(d), _p(dy), _p(wt), _p(dx), _p(ws), _p(mask), mask_act, _s()))
+    _timed_conv(fl, nb, "dvq_conv2d_dgrad", lambda:
+        lib().dvq_conv2d_dgrad(C.byref(d), _p(dy), _p(wt), _p(dx), _p(ws), _p(mask), mask_act, _s()))
     return dx
-
-
-def conv2d_wgrad(d: ConvDesc, x, dy, db=None):
-    """returns dw (fp32 packed [Cout,KH,KW,Cin]); db (fp32 [Cout]) is accumulated into when given"""
-    dw = torch.zeros(d.Cout, d.KH, d.KW, d.Cin, dtype=torch.float32, device=x.device)
-    fl, nb = _conv_cost(d, x.element_size())
-    _timed("conv_wgrad", fl, nb, lambda: check(
-        lib().dvq_conv2d_wgrad(C.byref(d), _p(x), _p(dy), _p(dw), _p(db), _s()), "dvq_conv2d_wgrad"))
-    return dw
 
 
 _workspace = {}
@@ -616,14 +597,9 @@ def conv2d_wgrad_oihw(d: ConvDesc, x, dy, cin_real, cout_real, grad_oihw, db=Non
                                            int(is_ohwi(grad_oihw)), _p(scratch), need, _s()), "dvq_conv2d_wgrad_oihw_x3"))
         return
     _tag(d, "wgrad")
-    if gn_ss is not None:
-        _timed_conv(fl, nb, "dvq_conv2d_wgrad_oihw_ex", lambda:
-            lib().dvq_conv2d_wgrad_oihw_ex(C.byref(d), _p(x), _p(dy), cin_real, cout_real, _praw(grad_oihw), _p(db),
-                                           int(is_ohwi(grad_oihw)), _p(gn_ss), _s()))
-        return
-    _timed_conv(fl, nb, "dvq_conv2d_wgrad_oihw", lambda:
-        lib().dvq_conv2d_wgrad_oihw(C.byref(d), _p(x), _p(dy), cin_real, cout_real, _praw(grad_oihw), _p(db),
-                                    int(is_ohwi(grad_oihw)), _s()))
+    _timed_conv(fl, nb, "dvq_conv2d_wgrad", lambda:
+        lib().dvq_conv2d_wgrad(C.byref(d), _p(x), _p(dy), cin_real, cout_real, _praw(grad_oihw), _p(db),
+                               int(is_ohwi(grad_oihw)), _p(gn_ss), _s()))
 
 
 def set_deterministic(on: bool):
@@ -697,16 +673,11 @@ def probe_mfma_rate(random_operands=True):
 
 
 def gemm_nt(a, b, m, n, k, lda, ldb, ldc, batch=1, sa=0, sb=0, sc=0, alpha=1.0, bias=None, bias_mode=0, out=None,
-            impl=0, residual=None):
-    """C[b][m][n] = alpha * sum_k A[b][m][k] B[b][n][k] (+bias) (+residual, same layout as C).  a, b, out are flat device tensors."""
+            impl=0):
+    """C[b][m][n] = alpha * sum_k A[b][m][k] B[b][n][k] (+bias).  a, b, out are flat device tensors.  impl: _lib.IMPL_*"""
     if out is None:
         out = torch.empty(batch * m * ldc if sc == 0 else batch * sc, dtype=a.dtype, device=a.device)
     es = a.element_size()
-    if residual is not None:
-        _timed("gemm_nt", 2 * batch * m * n * k, es * batch * (m * k + n * k + 2 * m * n), lambda: check(
-            lib().dvq_gemm_nt_res(_p(a), _p(b), _p(out), _p(residual), dt(a), m, n, k, lda, ldb, ldc, batch, sa, sb, sc, alpha, _p(bias),
-                                  bias_mode, _s()), "dvq_gemm_nt_res"))
-        return out
     _timed("gemm_nt", 2 * batch * m * n * k, es * batch * (m * k + n * k + m * n), lambda: check(
         lib().dvq_gemm_nt(_p(a), _p(b), _p(out), dt(a), m, n, k, lda, ldb, ldc, batch, sa, sb, sc, alpha, _p(bias),
                           bias_mode, impl, _s()), "dvq_gemm_nt"))
@@ -720,13 +691,8 @@ def gemm_tn(a, b, mred, i, j, lda, ldb, ldc, batch=1, sa=0, sb=0, sc=0, out=None
     es = a.element_size()
     if a.is_cuda and es == 2 and mred >= 1024 and i >= 256 and j >= 256:
         ensure_workspace(a.device)        # split partials of the 256 x 256 kernel (fold kernel instead of fp32 atomics)
-    if colsum is not None:
-        assert batch == 1
-        _timed("gemm_tn", 2 * mred * i * j, es * mred * (i + j) + 4 * i * j, lambda: check(
-            lib().dvq_gemm_tn_colsum(_p(a), _p(b), _p(out), _p(colsum), dt(a), mred, i, j, lda, ldb, ldc, impl, _s()), "dvq_gemm_tn_colsum"))
-        return out
     _timed("gemm_tn", 2 * batch * mred * i * j, es * batch * mred * (i + j) + 4 * batch * i * j, lambda: check(
-        lib().dvq_gemm_tn(_p(a), _p(b), _p(out), dt(a), mred, i, j, lda, ldb, ldc, batch, sa, sb, sc, impl, _s()),
+        lib().dvq_gemm_tn(_p(a), _p(b), _p(out), _p(colsum), dt(a), mred, i, j, lda, ldb, ldc, batch, sa, sb, sc, impl, _s()),
         "dvq_gemm_tn"))
     return out
 

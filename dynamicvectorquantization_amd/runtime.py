@@ -6,13 +6,17 @@ import os
 
 import torch
 
+from . import _lib
+
 # activations / packed weights are computed in this dtype ("fp32" = parity mode, "bf16" = perf mode)
 _compute_dtype = torch.float32
 # bumped whenever parameters change in place (optimizer step, load_state_dict): invalidates packed weights
 _weights_epoch = 0
-# 0 auto, 1 naive kernels, 2 generic MFMA kernels (LDS-DMA igemm), 3 register-staged igemm (A/B),
-# 4 require the LDS-resident-halo 3x3 kernel, 9 require the pipelined implicit-GEMM conv kernel (tests cross-check 1 / 2 / 4 / 9 on the GPU)
-_impl = 0
+# kernel choice of every conv / Linear layer (_lib.IMPL_*): AUTO, NAIVE kernels, generic MFMA kernels (LDS-DMA igemm), REGSTAGE igemm (A/B),
+# HALO requires the LDS-resident-halo 3x3 kernel, CONV_PIPE the pipelined implicit-GEMM conv kernel (tests cross-check NAIVE / MFMA /
+# HALO / CONV_PIPE on the GPU)
+IMPL_CHOICES = (_lib.IMPL_AUTO, _lib.IMPL_NAIVE, _lib.IMPL_MFMA, _lib.IMPL_REGSTAGE, _lib.IMPL_HALO, _lib.IMPL_CONV_PIPE)
+_impl = _lib.IMPL_AUTO
 
 
 # Every environment variable the Python package honours as a switch: name -> (default, what the non-default selects).  All of them
@@ -171,7 +175,7 @@ def impl() -> int:
 
 def set_impl(v: int):
     global _impl
-    assert v in (0, 1, 2, 3, 4, 9)
+    assert v in IMPL_CHOICES
     _impl = v
 
 

@@ -46,7 +46,9 @@ const char* dvq_last_error(void);
  * written in csrc ("conv3x3_halo_kernel", "conv_nt_pipe_kernel", ...; no template arguments, no fold / reduce / transpose helpers), noted
  * at the dispatch branch that launches it.  "" when nothing was noted (those entry points clear it first).  For timing labels. */
 const char* dvq_last_kernel(void);
-int dvq_version(void);     /* 116: dvq_grain_overlay, dvq_grain_lines, dvq_image_grid_u8 (+ dvq_image_grid_shape, dvq_imagelog_workspace_bytes):
+int dvq_version(void);     /* 117: DVQ_IMPL_* names for the impl codes; one entry per convolution / GEMM pass (dvq_conv2d_fwd, _dgrad, _wgrad, dvq_gemm_tn
+                            * take the arguments of their former _ex / _act / _mask / _oihw / _colsum variants; dvq_gemm_nt_res is gone);
+                            * 116: dvq_grain_overlay, dvq_grain_lines, dvq_image_grid_u8 (+ dvq_image_grid_shape, dvq_imagelog_workspace_bytes):
                             * training-time image logging;
                             * 115: dvq_vq_sample_argmax (+ dvq_vq_trained_prepare), dvq_vq_gumbel_noise, dvq_vq_codebook_grad, dvq_vq_mask_ratio,
                             * dvq_vq_rownorm / _ortho_sumsq / _rownorm_bwd (gradient-trained codebook: Gumbel search, codebook gradient, orthogonality term);
@@ -100,7 +102,7 @@ int dvq_vq_prepare(const float* codebook, int64_t K, int64_t D, void* prep, dvq_
  * stream-ordered calls without a zero-fill launch.  After the call int32 slots [4], [5], [6] hold the number of rows settled in
  * fp64 over all K codes (generic kernel only), over their candidate list / flagged residue classes, and -- of the latter -- with
  * more candidate classes than an entry lists.  impl: 0 = auto, 1 = force generic VALU kernel, 2 = force MFMA kernel
- * (DVQ_ESHAPE if unsupported). */
+ * (DVQ_ESHAPE if unsupported) -- this entry's own codes, not the DVQ_IMPL_* of the convolutions and GEMMs. */
 size_t dvq_vq_argmin_workspace_bytes(int64_t N);
 /* Analysis entry point (VQEmbedding.compute_distances, quantize2_mask.py:29-48): out[n][k] = (|x_n|^2 + |e_k|^2) - 2 x_n.e_k
  * (fp32 FMA arithmetic, the reference's addmm formula), out fp32 [N][K] caller-owned; at most 2^20 rows per call. */
@@ -177,6 +179,22 @@ int dvq_gn_bwd_dx(const void* x, const void* dy, int dtype, int64_t N, int64_t H
  * Upsample / Downsample / AttnBlock 1x1 / quant_conv (modules/diffusionmodules/model.py:38-192,
  * models/stage1_dynamic/dqvae_dual_entropy.py:93-94).
  * ---------------------------------------------------------------------------------------------- */
+/* Kernel choice of dvq_conv_desc.impl, dvq_gemm_nt and dvq_gemm_tn (dvq_vq_argmin's `impl` keeps its own 0 / 1 / 2 meaning, see there).
+ * A REQUIRED code returns DVQ_ESHAPE on a shape its kernel does not run; a PREFERRED code falls through to the automatic choice. */
+enum {
+    DVQ_IMPL_AUTO = 0,             /* automatic choice */
+    DVQ_IMPL_NAIVE = 1,            /* naive_nt_kernel / naive_tn_kernel; runs every shape */
+    DVQ_IMPL_MFMA = 2,             /* required. NT: 128 x 128 LDS-DMA igemm_nt_glds; TN: igemm_tn_tr for bf16 operands, igemm_tn for fp32 */
+    DVQ_IMPL_REGSTAGE = 3,         /* required. register-staged igemm_nt_kernel / igemm_tn_kernel */
+    DVQ_IMPL_HALO = 4,             /* required. conv entries only: the LDS-resident-halo 3 x 3 kernels (conv_halo.hip) */
+    DVQ_IMPL_WIDE = 5,             /* preferred. NT: gemm_nt_wide_kernel; TN: as DVQ_IMPL_MFMA */
+    DVQ_IMPL_WIDE_PIPE = 6,        /* preferred. NT: 256-row gemm_nt_wide_pipe; TN: gemm_tn_wide_pipe instead of the 8-phase kernel */
+    DVQ_IMPL_WIDE_PIPE_4WAVE = 7,  /* preferred. NT: 4-wave gemm_nt_wide_pipe; TN: as DVQ_IMPL_MFMA */
+    DVQ_IMPL_WIDE_PIPE_192 = 8,    /* preferred. NT: 192-row gemm_nt_wide_pipe; TN: as DVQ_IMPL_MFMA */
+    DVQ_IMPL_CONV_PIPE = 9,        /* required. NT convolutions (bf16): conv_nt_pipe_kernel; TN: as DVQ_IMPL_MFMA */
+    DVQ_IMPL_8PHASE = 10           /* preferred. NT: gemm_nt_8phase_kernel; TN: as DVQ_IMPL_MFMA */
+};
+
 typedef struct dvq_conv_desc {
     int64_t N;        /* batch */
     int64_t H, W;     /* LOGICAL input height/width (after the optional nearest x2 upsample) */
@@ -188,36 +206,39 @@ typedef struct dvq_conv_desc {
     int32_t pad_t, pad_l; /* zero padding top/left; bottom/right padding is implied by OH/OW */
     int32_t upsample; /* 1: the stored input is [N,H/2,W/2,Cin] and is read through nearest x2 (model.py:50) */
     int32_t dtype;    /* DVQ_F32 / DVQ_BF16: activations and packed weights */
-    int32_t impl;     /* 0 auto, 1 naive direct kernel, 2 MFMA implicit GEMM (DVQ_ESHAPE if unsupported) */
+    int32_t impl;     /* DVQ_IMPL_*: AUTO, NAIVE, MFMA, REGSTAGE, HALO, CONV_PIPE (DVQ_ESHAPE if the shape is not eligible) */
 } dvq_conv_desc;
 
-/* y[n,oh,ow,co] = bias[co] + sum x[n,oh*s-pt+kh, ow*s-pl+kw, ci] * w[co,kh,kw,ci] (+ residual).
+/* Activations fused into conv epilogues / behind a normalisation (dvq_gn_* take the same codes in `silu`):
+ * 0 none, 1 swish (GroupNorm only), 2 LeakyReLU(0.2) (PatchGAN, modules/discriminator/model.py:35-62),
+ * 3 ReLU (VGG16 of LPIPS, modules/losses/lpips.py:75-93; conv epilogues only). */
+enum { DVQ_ACT_NONE = 0, DVQ_ACT_SWISH = 1, DVQ_ACT_LRELU = 2, DVQ_ACT_RELU = 3 };
+
+/* y[n,oh,ow,co] = act(bias[co] + sum x[n,oh*s-pt+kh, ow*s-pl+kw, ci] * w[co,kh,kw,ci] (+ residual)).
  * w: packed [Cout][KH][KW][Cin] of `dtype` (Cin here is the padded count); bias fp32 [Cout] or NULL;
- * residual NHWC like y or NULL. */
-int dvq_conv2d_fwd(const dvq_conv_desc* d, const void* x, const void* w, const float* bias, const void* residual,
-                   void* y, dvq_stream_t stream);
-/* Fused variants on shapes accepted by dvq_conv3x3_fused_ok (bf16, 3x3, stride 1, pad 1, H % 8 == 0, W % 32 == 0,
- * Cin % 64 == 0): gn_scale_shift (fp32 [N][Cin][2], from dvq_gn_scale_shift) applies GroupNorm + swish to the INPUT
- * inside the kernel (ResnetBlock's norm -> swish -> conv, model.py:119-129, without materialising the activation);
+ * residual NHWC like y or NULL.
+ * act: DVQ_ACT_NONE / _RELU / _LRELU (nn.Conv2d followed by nn.ReLU / nn.LeakyReLU(0.2)); any other than NONE excludes residual,
+ * gn_scale_shift and out_stats (DVQ_EINVAL).
+ * Fused GroupNorm on shapes accepted by dvq_conv3x3_fused_ok (bf16, 3x3, stride 1, pad 1, H % 8 == 0, W % 32 == 0,
+ * Cin % 64 == 0; DVQ_ESHAPE elsewhere): gn_scale_shift (fp32 [N][Cin][2], from dvq_gn_scale_shift) applies GroupNorm + swish to the
+ * INPUT inside the kernel (ResnetBlock's norm -> swish -> conv, model.py:119-129, without materialising the activation);
  * out_stats (fp64 [N][out_groups][2], accumulated) receives sum / sum of squares of the OUTPUT per group, i.e. the
  * statistics pass of the next GroupNorm.  Either may be NULL. */
 int dvq_conv3x3_fused_ok(const dvq_conv_desc* d);
-int dvq_conv2d_fwd_ex(const dvq_conv_desc* d, const void* x, const void* w, const float* bias, const void* residual,
-                      void* y, const float* gn_scale_shift, double* out_stats, int out_groups, dvq_stream_t stream);
-int dvq_conv2d_wgrad_oihw_ex(const dvq_conv_desc* d, const void* x, const void* dy, int64_t cin_real, int64_t cout_real,
-                             float* grad_oihw, float* dbias, int ohwi, const float* gn_scale_shift, dvq_stream_t stream);
+int dvq_conv2d_fwd(const dvq_conv_desc* d, const void* x, const void* w, const float* bias, const void* residual, void* y,
+                   const float* gn_scale_shift, double* out_stats, int out_groups, int act, dvq_stream_t stream);
 /* fp32x3 weight gradient (dvq_set_fp32_split) at launch level: x / dy fp32 (descriptor dtype DVQ_F32, channels padded to 4) are split
  * into bf16 planes hi = RNE(v), lo = RNE(v - hi) in `scratch` (>= dvq_conv2d_wgrad_x3_scratch_bytes(d), 16-B aligned; channels re-padded
  * to 8) and the gradient is accumulated by THREE launches of the bf16 weight-gradient kernels, x_lo.dy_hi + x_hi.dy_lo + x_hi.dy_hi --
  * the same three products and fp32 accumulation the in-kernel split forms, at the bf16 kernels' speed.  Arguments as
- * dvq_conv2d_wgrad_oihw; any convolution geometry the bf16 path takes.  dvq_split_bf16_planes: x fp32 [rows][cin] -> two bf16
+ * dvq_conv2d_wgrad; any convolution geometry the bf16 path takes.  dvq_split_bf16_planes: x fp32 [rows][cin] -> two bf16
  * [rows][cout] tensors (cin % 4 == 0, cout % 8 == 0, cout >= cin; channels >= cin are zero). */
 int dvq_split_bf16_planes(const float* x, void* hi, void* lo, int64_t rows, int64_t cin, int64_t cout, dvq_stream_t stream);
 int64_t dvq_conv2d_wgrad_x3_scratch_bytes(const dvq_conv_desc* d);
 int dvq_conv2d_wgrad_oihw_x3(const dvq_conv_desc* d, const void* x, const void* dy, int64_t cin_real, int64_t cout_real,
                              float* grad_oihw, float* dbias, int ohwi, void* scratch, int64_t scratch_bytes, dvq_stream_t stream);
 /* fp32x3 forward / input gradient of a 3 x 3, stride 1, pad 1 convolution on the halo kernel: operands fp32 (descriptor dtype DVQ_F32,
- * arguments as dvq_conv2d_fwd / dvq_conv2d_fwd_act and dvq_conv2d_dgrad_mask), split into bf16 planes laid side by side on the channel
+ * arguments as dvq_conv2d_fwd and dvq_conv2d_dgrad), split into bf16 planes laid side by side on the channel
  * axis ([x_hi | x_lo | x_hi] against [w_hi | w_hi | w_lo]) in `scratch`, ONE launch of the bf16 halo kernel, fp32 residual / gate /
  * activation and fp32 output -- the three products and the fp32 accumulation of dvq_set_fp32_split at the halo kernel's speed.
  * dvq_conv3x3_x3_ok(d, dgrad): shapes taken (H % 8 == 0, W % 32 == 0, streamed channels % 64 == 0, produced channels > 32);
@@ -235,32 +256,21 @@ int dvq_gn_scale_shift(const double* stats, const float* gamma, const float* bet
 /* dx (stored-input shape, i.e. [N,H/2,W/2,Cin] when upsample) from dy [N,OH,OW,Cout].
  * wt: weights in IHWO layout [d->Cin,KH,KW,Cout] of `dtype` (dvq_pack_weight writes the first Cin_real rows; when the
  * descriptor's Cin is channel-padded the caller provides zero rows up to d->Cin).  When upsample is set,
- * ws must hold N*H*W*Cin elements of `dtype` (gradient at the upsampled resolution). */
-int dvq_conv2d_dgrad(const dvq_conv_desc* d, const void* dy, const void* wt, void* dx, void* ws,
-                     dvq_stream_t stream);
-/* Activations fused into conv epilogues / behind a normalisation (dvq_gn_* take the same codes in `silu`):
- * 0 none, 1 swish (GroupNorm only), 2 LeakyReLU(0.2) (PatchGAN, modules/discriminator/model.py:35-62),
- * 3 ReLU (VGG16 of LPIPS, modules/losses/lpips.py:75-93; conv epilogues only). */
-enum { DVQ_ACT_NONE = 0, DVQ_ACT_SWISH = 1, DVQ_ACT_LRELU = 2, DVQ_ACT_RELU = 3 };
-/* y = act(conv(x, w) + bias): replaces nn.Conv2d followed by nn.ReLU / nn.LeakyReLU(0.2) */
-int dvq_conv2d_fwd_act(const dvq_conv_desc* d, const void* x, const void* w, const float* bias, void* y, int act,
-                       dvq_stream_t stream);
-/* dgrad through the conv AND the activation that produced the conv's input: mask = that activation's OUTPUT
- * (same shape as dx); dx = dgrad * (mask > 0 ? 1 : slope(mask_act)).  mask == NULL: plain dvq_conv2d_dgrad. */
-int dvq_conv2d_dgrad_mask(const dvq_conv_desc* d, const void* dy, const void* wt, void* dx, void* ws, const void* mask,
-                          int mask_act, dvq_stream_t stream);
-/* dw (fp32 OHWI, ACCUMULATED into -- zero it first) and dbias (fp32 [Cout], accumulated; may be NULL). */
-int dvq_conv2d_wgrad(const dvq_conv_desc* d, const void* x, const void* dy, float* dw, float* dbias,
+ * ws must hold N*H*W*Cin elements of `dtype` (gradient at the upsampled resolution).
+ * mask (may be NULL): dgrad through the conv AND the activation that produced the conv's input: mask = that activation's OUTPUT
+ * (same shape as dx); dx = dgrad * (mask > 0 ? 1 : slope(mask_act)), mask_act DVQ_ACT_RELU / _LRELU, no folded upsample. */
+int dvq_conv2d_dgrad(const dvq_conv_desc* d, const void* dy, const void* wt, void* dx, void* ws, const void* mask, int mask_act,
                      dvq_stream_t stream);
 
-/* Same as dvq_conv2d_wgrad but accumulates straight into the reference-layout gradient
- * [cout_real][cin_real][KH][KW] (no packed intermediate, no unpack pass); d->Cin / d->Cout are the padded channel
- * counts of x / dy.  dbias: fp32 [cout_real], accumulated, may be NULL. */
-int dvq_conv2d_wgrad_oihw(const dvq_conv_desc* d, const void* x, const void* dy, int64_t cin_real, int64_t cout_real,
-                          float* grad_oihw, float* dbias, int ohwi, dvq_stream_t stream);
-/* ohwi = 0: grad is [cout][cin][KH][KW] (torch-contiguous parameter); ohwi = 1: grad is stored [cout][KH][KW][cin]
+/* Weight gradient, ACCUMULATED straight into the fp32 gradient of the reference-layout parameter (zero it first; no packed
+ * intermediate, no unpack pass); d->Cin / d->Cout are the padded channel counts of x / dy, cin_real / cout_real those of the parameter.
+ * ohwi = 0: grad is [cout][cin][KH][KW] (torch-contiguous parameter); ohwi = 1: grad is stored [cout][KH][KW][cin]
  * (the trainer's flat storage keeps conv weights and their gradients channel-last: contiguous atomics, no unpack).
- * dvq_pack_weight(_s_multi) accept the same storage with bit 8 of `dtype` set. */
+ * dvq_pack_weight(_s_multi) accept the same storage with bit 8 of `dtype` set.
+ * dbias: fp32 [cout_real], accumulated, may be NULL.  gn_scale_shift (may be NULL; shapes accepted by dvq_conv3x3_fused_ok): the
+ * GroupNorm + swish the forward fused into its prologue, re-applied to x inside the kernel. */
+int dvq_conv2d_wgrad(const dvq_conv_desc* d, const void* x, const void* dy, int64_t cin_real, int64_t cout_real, float* grad,
+                     float* dbias, int ohwi, const float* gn_scale_shift, dvq_stream_t stream);
 
 /* Pack every conv weight of a model in ONE launch.  table_dev: device array of n_entries records
  * { const float* master; void* w; void* wt; int64 Cout, Cin, taps, Cin_p, Cout_p, begin, dtype } where `begin` is
@@ -294,22 +304,14 @@ int dvq_nhwc_pad_to_nchw(const void* in, int dtype, int64_t B, int64_t C, int64_
 /* Generic batched GEMM on the same kernels.
  * NT:  C[b][m][n] = alpha * sum_k A[b][m][k] * B[b][n][k] (+ bias) ; bias_mode 0 none, 1 per-n, 2 per-m.
  * TN:  C[b][i][j] (fp32, accumulated) += sum_m A[b][m][i] * B[b][m][j].
- * Strides in elements. */
+ * Strides in elements.  impl: DVQ_IMPL_*. */
 int dvq_gemm_nt(const void* A, const void* B, void* C, int dtype, int64_t M, int64_t N, int64_t K, int64_t lda,
                 int64_t ldb, int64_t ldc, int64_t batch, int64_t sA, int64_t sB, int64_t sC, float alpha,
                 const float* bias, int bias_mode, int impl, dvq_stream_t stream);
-/* the same product ADDED to R (same dtype / layout as C, may alias C): input gradients that accumulate onto an earlier one leave the fp32
- * accumulator rounded once instead of passing through an add kernel (dx of the k / v projections onto dx of q, stackgpt.py:44-47) */
-int dvq_gemm_nt_res(const void* A, const void* B, void* C, const void* R, int dtype, int64_t M, int64_t N, int64_t K, int64_t lda,
-                    int64_t ldb, int64_t ldc, int64_t batch, int64_t sA, int64_t sB, int64_t sC, float alpha, const float* bias,
-                    int bias_mode, dvq_stream_t stream);
-int dvq_gemm_tn(const void* A, const void* B, float* C, int dtype, int64_t Mred, int64_t I, int64_t J, int64_t lda,
-                int64_t ldb, int64_t ldc, int64_t batch, int64_t sA, int64_t sB, int64_t sC, int impl,
-                dvq_stream_t stream);
-/* the same product with colsum[i] += sum_m A[m][i] from the same pass over A (bias gradient of a Linear layer next to its weight
- * gradient: torch.nn.Linear's autograd, stackgpt.py:44-96) */
-int dvq_gemm_tn_colsum(const void* A, const void* B, float* C, float* colsum, int dtype, int64_t Mred, int64_t I, int64_t J, int64_t lda,
-                       int64_t ldb, int64_t ldc, int impl, dvq_stream_t stream);
+/* colsum (may be NULL; batch 1 only): colsum[i] += sum_m A[m][i] from the same pass over A (bias gradient of a Linear layer next to
+ * its weight gradient: torch.nn.Linear's autograd, stackgpt.py:44-96) */
+int dvq_gemm_tn(const void* A, const void* B, float* C, float* colsum, int dtype, int64_t Mred, int64_t I, int64_t J, int64_t lda,
+                int64_t ldb, int64_t ldc, int64_t batch, int64_t sA, int64_t sB, int64_t sC, int impl, dvq_stream_t stream);
 
 /* Register a caller-owned device scratch buffer (one per process; the library cuts it into eight slots, one per stream that
  * uses it, so the side-stream weight gradients and the main stream never share one).  With >= 76 MiB per slot the split-K

@@ -8,7 +8,9 @@ the smallest shape that meets the branch's conditions in csrc/igemm.hip / csrc/c
   * gemm_tn_8phase_kernel, gemm_tn_wide_pipe_kernel: no conv call reaches them (gemm_tn calls do by default, under the fixed label
     "gemm_tn");
   * igemm_tn_kernel: fp32 operands only, and fp32 weight gradients go to the bf16 planes ("conv_wgrad_x3_planes") or need impl 3;
-  * the fp32x3 forms of the halo kernels (dvq_conv2d_fwd_x3 / _dgrad_x3 / _wgrad_oihw_x3) keep their fixed labels."""
+  * the fp32x3 forms of the halo kernels (dvq_conv2d_fwd_x3 / _dgrad_x3 / _wgrad_oihw_x3) keep their fixed labels.
+The activation epilogue of the forward and the activation mask of the input gradient are arguments of the one entry per pass: one
+halo case each, and the forward's refusal of an activation together with a residual."""
 import pytest
 import torch
 
@@ -33,9 +35,19 @@ def _fwd(K, dev, d, dtype=BF16):
     return K.conv2d_fwd(d, x, w, torch.zeros(d.Cout, device=dev))
 
 
+def _fwd_lrelu(K, dev, d, dtype=BF16):
+    x, w = _rand(dev, dtype, d.N, d.H, d.W, d.Cin), _rand(dev, dtype, d.Cout, d.KH, d.KW, d.Cin)
+    return K.conv2d_fwd(d, x, w, torch.zeros(d.Cout, device=dev), act=K.ACT_LRELU)
+
+
 def _dgrad(K, dev, d, dtype=BF16):
     dy, wt = _rand(dev, dtype, d.N, d.OH, d.OW, d.Cout), _rand(dev, dtype, d.Cin, d.KH, d.KW, d.Cout)
     return K.conv2d_dgrad(d, dy, wt)
+
+
+def _dgrad_relu_mask(K, dev, d, dtype=BF16):
+    dy, wt = _rand(dev, dtype, d.N, d.OH, d.OW, d.Cout), _rand(dev, dtype, d.Cin, d.KH, d.KW, d.Cout)
+    return K.conv2d_dgrad(d, dy, wt, mask=_rand(dev, dtype, d.N, d.H, d.W, d.Cin), mask_act=K.ACT_RELU)
 
 
 def _wgrad(K, dev, d, dtype=BF16):
@@ -49,11 +61,14 @@ def _wgrad(K, dev, d, dtype=BF16):
 DISPATCH_CASES = [
     # halo_try_impl: H % 8, W % 32, Cin % 64, Cout % 8
     ("halo-fwd", _fwd, "conv3x3_halo_kernel", dict(n=1, h=8, w=32, cin=64, cout=64, k=3), BF16),
-    # conv2d_fwd_impl: Cin == 8 (image heads) -> dvq_conv3x3_thin_k_try: W % 32, Cout % 8
+    # the same entry with an activation epilogue / the input gradient gated through an activation's output: the same kernel
+    ("halo-fwd-lrelu", _fwd_lrelu, "conv3x3_halo_kernel", dict(n=1, h=8, w=32, cin=64, cout=64, k=3), BF16),
+    ("halo-dgrad-relu-mask", _dgrad_relu_mask, "conv3x3_halo_kernel", dict(n=1, h=8, w=32, cin=64, cout=64, k=3), BF16),
+    # dvq_conv2d_fwd: Cin == 8 (image heads) -> dvq_conv3x3_thin_k_try: W % 32, Cout % 8
     ("thin-k-fwd", _fwd, "conv3x3_thin_k_kernel", dict(n=1, h=8, w=32, cin=8, cout=64, k=3), BF16),
-    # dvq_conv2d_dgrad_mask: Cout == 8 (gradient of the 3-channel output conv), the same kernel with the taps reversed
+    # dvq_conv2d_dgrad: Cout == 8 (gradient of the 3-channel output conv), the same kernel with the taps reversed
     ("thin-k-dgrad", _dgrad, "conv3x3_thin_k_kernel", dict(n=1, h=8, w=32, cin=64, cout=8, k=3), BF16),
-    # dvq_conv2d_dgrad_mask: 4 x 4 / stride 2 / pad 1, Cin == 8, H == 2 OH (input gradient of the PatchGAN's first conv)
+    # dvq_conv2d_dgrad: 4 x 4 / stride 2 / pad 1, Cin == 8, H == 2 OH (input gradient of the PatchGAN's first conv)
     ("tconv4x4s2-thin", _dgrad, "tconv4x4s2_thin_kernel", dict(n=1, h=16, w=16, cin=8, cout=64, k=4, stride=2, pad=1), BF16),
     # launch_nt pipe_ok: 64-channel K slabs, stride 1 / 2; the encoder's downsampling conv (3 x 3 / stride 2, pad bottom / right only)
     ("nt-pipe-down", _fwd, "conv_nt_pipe_kernel", dict(n=1, h=16, w=16, cin=64, cout=64, k=3, stride=2, pad=0, oh=8, ow=8), BF16),
@@ -91,6 +106,20 @@ def test_dispatch_label(dev, case):
         fams = K.profile_stop()
     assert list(fams) == [family] and fams[family]["launches"] == 1, fams
     assert bool(torch.isfinite(out.float()).all())
+
+
+def test_fwd_refuses_activation_with_residual_before_dispatch(dev):
+    """act != ACT_NONE excludes a residual: DVQ_EINVAL from the argument check, no kernel family noted"""
+    from dynamicvectorquantization_amd import _lib
+    from dynamicvectorquantization_amd import kernels as K
+    d = _desc(K, n=1, h=8, w=32, cin=64, cout=64, k=3)
+    x, w = _rand(dev, BF16, d.N, d.H, d.W, d.Cin), _rand(dev, BF16, d.Cout, d.KH, d.KW, d.Cin)
+    r = _rand(dev, BF16, d.N, d.OH, d.OW, d.Cout)
+    _fwd(K, dev, d)                     # a call that notes a family first: the refusal below must clear it
+    assert K.lib().dvq_last_kernel() == b"conv3x3_halo_kernel"
+    with pytest.raises(_lib.DvqError, match="code -1"):
+        K.conv2d_fwd(d, x, w, torch.zeros(d.Cout, device=dev), residual=r, act=K.ACT_RELU)
+    assert K.lib().dvq_last_kernel() == b""
 
 
 @pytest.mark.parametrize("dtype", [BF16, F32], ids=["bf16", "fp32"])

@@ -8,7 +8,7 @@ import torch
 import torch.nn.functional as F
 
 from conftest import REPO, load_golden
-from dynamicvectorquantization_amd import synth
+from dynamicvectorquantization_amd import _lib, synth
 
 pytestmark = pytest.mark.gpu
 
@@ -1051,11 +1051,12 @@ def test_tconv4x4s2_thin_kernel(dev, case):
     assert np.abs(outs[0] - outs[1]).max() / np.abs(dref).max() < 1e-2
 
 
-@pytest.mark.parametrize("impl", [5, 6, 7, 8, 10], ids=["plain", "pipelined", "pipelined-4wave", "pipelined-192", "8phase"])
+@pytest.mark.parametrize("impl", [_lib.IMPL_WIDE, _lib.IMPL_WIDE_PIPE, _lib.IMPL_WIDE_PIPE_4WAVE, _lib.IMPL_WIDE_PIPE_192, _lib.IMPL_8PHASE],
+                         ids=["plain", "pipelined", "pipelined-4wave", "pipelined-192", "8phase"])
 @pytest.mark.parametrize("shape", [(3, 600, 520, 200, 1), (1, 2048, 1032, 512, 2), (2, 1296, 648, 128, 0), (1, 300, 264, 64, 1),
                                    (1, 1100, 776, 448, 1), (2, 520, 512, 4160, 2)])
 def test_gemm_nt_wide_kernel(dev, shape, impl):
-    """256 x 256 macro-tile GEMMs (bf16; impl 5 = plain main loop, impl 6 = the software-pipelined one the automatic dispatch uses
+    """256 x 256 macro-tile GEMMs (bf16; IMPL_WIDE = plain main loop, IMPL_WIDE_PIPE = the software-pipelined one the automatic dispatch uses
     for large plain products the library does not take): ragged M / N / K tails, a single K slab, bias per column / row, batches --
     against an fp32 torch product of the same bf16-rounded operands"""
     from dynamicvectorquantization_amd import kernels as K
@@ -1079,11 +1080,11 @@ def test_gemm_nt_wide_kernel(dev, shape, impl):
 
 def test_gemm_nt_8phase_long_reduction(dev):
     """the 8-phase 256 x 256 kernel (counted vmcnt, DMA queue never drained) where the automatic dispatch takes it -- K >= 4096 over at
-    least two rounds of tiles -- and forced (impl 10) on an odd number of K tiles with ragged row / column tails: the WHOLE output against
+    least two rounds of tiles -- and forced (IMPL_8PHASE) on an odd number of K tiles with ragged row / column tails: the WHOLE output against
     an fp32 product of the same bf16 operands, and bit-identical results over repeated launches"""
     from dynamicvectorquantization_amd import kernels as K
     torch.manual_seed(11)
-    for (m, n, k, impl) in ((8192, 4096, 4096, 0), (4100, 2056, 4160, 10), (8192, 8192, 8192, 0)):
+    for (m, n, k, impl) in ((8192, 4096, 4096, _lib.IMPL_AUTO), (4100, 2056, 4160, _lib.IMPL_8PHASE), (8192, 8192, 8192, _lib.IMPL_AUTO)):
         a2 = (torch.rand(m, k, device=dev) * 2 - 1).to(torch.bfloat16)
         b2 = (torch.rand(n, k, device=dev) * 2 - 1).to(torch.bfloat16)
         bias = torch.randn(n, device=dev)
@@ -1448,7 +1449,7 @@ def test_pipelined_kernels_reproduce_bitwise_full_size(dev):
         m, n, k = 20736, 1024, 4096
         a = torch.randn(m, k, device=dev).to(torch.bfloat16).reshape(-1)
         b = torch.randn(n, k, device=dev).to(torch.bfloat16).reshape(-1)
-        for impl in (6, 8, 10):
+        for impl in (_lib.IMPL_WIDE_PIPE, _lib.IMPL_WIDE_PIPE_192, _lib.IMPL_8PHASE):
             same(lambda: [K.gemm_nt(a, b, m, n, k, k, k, n, impl=impl)])
         a2 = torch.randn(m, 1024, device=dev).to(torch.bfloat16).reshape(-1)
         b2 = torch.randn(m, 4096, device=dev).to(torch.bfloat16).reshape(-1)

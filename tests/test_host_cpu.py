@@ -30,6 +30,25 @@ def test_library_exports_every_header_symbol():
     assert lib.dvq_vq_argmin_workspace_bytes(65536) >= 4 * 65536
 
 
+def test_impl_codes_match_the_header():
+    """the DVQ_IMPL_* enum of include/dvq_hip.h, _lib's mirror of it, and the codes runtime.set_impl accepts for whole layers"""
+    from dynamicvectorquantization_amd import _lib
+    from dynamicvectorquantization_amd import runtime as rt
+    header = open(os.path.join(REPO, "include", "dvq_hip.h")).read()
+    enum = {n: int(v) for n, v in re.findall(r"^\s*DVQ_(IMPL_[A-Z0-9_]+) = (\d+),?\s*/\*", header, re.M)}
+    assert sorted(enum.values()) == list(range(11)), enum
+    assert {n: getattr(_lib, n) for n in enum} == enum
+    assert {n for n in dir(_lib) if n.startswith("IMPL_")} == set(enum)
+    accepted = []
+    for v in range(-1, 12):
+        try:
+            with rt.impl_ctx(v):
+                accepted.append(v)
+        except AssertionError:
+            pass
+    assert accepted == [0, 1, 2, 3, 4, 9] and rt.impl() == 0
+
+
 def test_error_convention_without_gpu():
     from dynamicvectorquantization_amd import _lib
     lib = _lib.load()

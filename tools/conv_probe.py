@@ -34,7 +34,8 @@ def main():
     timeit("fwd", lambda: K.conv2d_fwd(d, x, w, bias, None))
     timeit("fwd_res", lambda: K.conv2d_fwd(d, x, w, bias, dy))
     timeit("dgrad", lambda: K.conv2d_dgrad(d, dy, wt))
-    timeit("wgrad", lambda: K.conv2d_wgrad(d, x, dy, None))
+    gw = torch.zeros(C, C, 3, 3, device=dev)
+    timeit("wgrad", lambda: K.conv2d_wgrad_oihw(d, x, dy, C, C, gw, None))
     print(json.dumps(res))
 
 if __name__ == "__main__":

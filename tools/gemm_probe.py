@@ -1,11 +1,11 @@
 #!/usr/bin/env python3
-"""plain bf16 GEMM timings on the StackGPT shapes (M = 32 x 648 tokens): our 128x128 LDS-DMA kernel (impl 2), the 256x256
-wide kernel (impl 5), auto (impl 0), and -- as a yardstick only, never a product path -- torch.matmul (hipBLASLt).
+"""plain bf16 GEMM timings on the StackGPT shapes (M = 32 x 648 tokens): the pipelined 256-wide kernels
+(IMPL_WIDE_PIPE, IMPL_WIDE_PIPE_4WAVE, IMPL_WIDE_PIPE_192), the automatic choice (IMPL_AUTO), and -- as a yardstick only, never a product path -- torch.matmul (hipBLASLt).
 Also the TN weight-gradient GEMM."""
 import os, sys
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import torch
-from dynamicvectorquantization_amd import kernels as K
+from dynamicvectorquantization_amd import _lib, kernels as K
 dev = torch.device("cuda:0")
 
 
@@ -27,15 +27,16 @@ for (m, n, k) in [(20736, 1024, 1024), (20736, 3072, 1024), (20736, 4096, 1024),
     a, b = a2.reshape(-1), b2.reshape(-1)
     out = torch.empty(m * n, device=dev, dtype=torch.bfloat16)
     row = []
-    for impl in (6, 7, 8, 0):
+    for name in ("WIDE_PIPE", "WIDE_PIPE_4WAVE", "WIDE_PIPE_192", "AUTO"):
+        impl = getattr(_lib, "IMPL_" + name)
         ms = timeit(lambda: K.gemm_nt(a, b, m, n, k, k, k, n, out=out, impl=impl))
-        row.append(f"impl{impl} {ms:7.3f} ms {2.0*m*n*k/ms/1e9:6.0f} TF/s")
+        row.append(f"{name} {ms:7.3f} ms {2.0*m*n*k/ms/1e9:6.0f} TF/s")
     ms = timeit(lambda: torch.matmul(a2, b2.t()))
     row.append(f"torch {ms:7.3f} ms {2.0*m*n*k/ms/1e9:6.0f} TF/s")
-    K.gemm_nt(a, b, m, n, k, k, k, n, out=out, impl=8)
+    K.gemm_nt(a, b, m, n, k, k, k, n, out=out, impl=_lib.IMPL_WIDE_PIPE_192)
     ref = torch.matmul(a2[:512].float(), b2.float().t())
     err = float((out.view(m, n)[:512].float() - ref).abs().max() / ref.abs().max())
-    row.append(f"impl8 err {err:.1e}")
+    row.append(f"WIDE_PIPE_192 err {err:.1e}")
     print(f"NT M={m} N={n} K={k}: " + "   ".join(row), flush=True)
 
 for (mred, i, j) in [(20736, 1024, 1024), (20736, 3072, 1024), (20736, 4096, 1024), (20736, 1024, 4096)]:
