@@ -7,10 +7,14 @@ travels with the repo snapshot to the GPU box.
 (DVQ_HALO_DBG, DVQ_WGRAD_DBG, DVQ_ATTN_DBG, DVQ_VQ_DBG -- wrong results by construction) and the slower persistent convolution
 (conv_halo2.hip, DVQ_HALO2=1).  `_lib.load()` takes it only when DVQ_USE_PROBES_LIB=1 (tools/debug/); the product library contains
 none of that code and does not read those variables.
+
+Sources compile in parallel, at most MAX_JOBS (default 16) at a time.  An object is rebuilt when its source, any header under csrc/ or
+include/dvq_hip.h is newer than it.
 """
 from __future__ import annotations
 
 import concurrent.futures as cf
+import glob
 import os
 import shutil
 import subprocess
@@ -22,7 +26,7 @@ OBJ = os.path.join(CSRC, "_obj")
 LIB = os.path.join(HERE, "libdvq_hip.so")
 LIB_PROBES = os.path.join(HERE, "libdvq_hip_probes.so")
 PROBE_SOURCES = ["conv_halo2.hip"]          # compiled and linked into the probe library only
-SOURCES = ["vq.hip", "vq_trained.hip", "entropy.hip", "groupnorm.hip", "igemm.hip", "conv_halo.hip", "misc.hip", "lossnet.hip", "router.hip", "permuter.hip", "transformer.hip", "attention.hip", "attention2.hip", "imgproc.hip", "decode.hip", "cmdlist.hip", "metrics.hip", "nll.hip", "tokens.hip", "imagelog.hip"]
+SOURCES = ["vq.hip", "vq_trained.hip", "entropy.hip", "groupnorm.hip", "igemm.hip", "igemm_nt.hip", "igemm_tn.hip", "conv_halo.hip", "misc.hip", "lossnet.hip", "router.hip", "permuter.hip", "transformer.hip", "attention.hip", "attention2.hip", "imgproc.hip", "decode.hip", "cmdlist.hip", "metrics.hip", "nll.hip", "tokens.hip", "imagelog.hip"]
 FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-munsafe-fp-atomics", "-Wno-unused-result"]
 # per-file additions.  vq.hip: no SLP vectorisation -- it pairs the scalar fp32 bookkeeping between the MFMAs of the argmin main loop
 # into v_pk_fma_f32 / v_pk_add_f32, which issue more slowly beside a busy matrix pipe than the two instructions they replace
@@ -36,6 +40,11 @@ def _hipcc() -> str:
     if not os.path.exists(exe):
         raise RuntimeError("hipcc not found: libdvq_hip.so cannot be built on this machine")
     return exe
+
+
+def headers() -> list:
+    """what every object depends on besides its own source: each header under csrc/ and the public one"""
+    return sorted(glob.glob(os.path.join(CSRC, "*.h"))) + [os.path.join(HERE, "..", "include", "dvq_hip.h")]
 
 
 def _stale(target: str, deps) -> bool:
@@ -52,14 +61,14 @@ def build(force: bool = False, verbose: bool = True, probes: bool = False) -> st
     flags = FLAGS + (["-DDVQ_PROBES"] if probes else []) + os.environ.get("DVQ_BUILD_EXTRA_FLAGS", "").split()
     os.makedirs(obj_dir, exist_ok=True)
     hipcc = _hipcc()
-    headers = [os.path.join(CSRC, "dvq_common.h"), os.path.join(HERE, "..", "include", "dvq_hip.h")]
+    hdrs = headers()
     jobs = []
     objs = []
     for src in SOURCES + (PROBE_SOURCES if probes else []):
         s = os.path.join(CSRC, src)
         o = os.path.join(obj_dir, src.replace(".hip", ".o"))
         objs.append(o)
-        if force or _stale(o, [s] + headers):
+        if force or _stale(o, [s] + hdrs):
             jobs.append([hipcc] + flags + EXTRA_FLAGS.get(src, []) + ["-c", s, "-o", o])
 
     def run(cmd):
@@ -69,7 +78,8 @@ def build(force: bool = False, verbose: bool = True, probes: bool = False) -> st
         return cmd[-1]
 
     if jobs:
-        with cf.ThreadPoolExecutor(max_workers=min(len(jobs), os.cpu_count() or 4)) as ex:
+        # MAX_JOBS: a shared machine reports every CPU of the host, not the share a command may use
+        with cf.ThreadPoolExecutor(max_workers=min(len(jobs), int(os.environ.get("MAX_JOBS", 16)), os.cpu_count() or 4)) as ex:
             for done in ex.map(run, jobs):
                 if verbose:
                     print("[dvq build] compiled", os.path.basename(done), flush=True)

@@ -1,6 +1,6 @@
 // 3x3 stride-1 pad-1 convolution with an LDS-resident input halo (bf16, gfx950).
 //
-// The generic implicit-GEMM kernel (igemm.hip) streams every operand tile from L2 once per tap: 64 flop per
+// The generic implicit-GEMM kernel (igemm_nt.hip) streams every operand tile from L2 once per tap: 64 flop per
 // byte of global->LDS traffic, and PMC shows its waves parked on that stream (profiles/r01_v2_conv_probe_pmc.csv).
 // Here a workgroup owns an 8x32 pixel tile x 128 output channels; per 64-channel input chunk the
 // (8+2)x(32+2) pixel halo is DMA'd to LDS ONCE and reused by all 9 taps (a tap is just a row offset of the
@@ -60,12 +60,6 @@ struct HaloParams {
 // DVQ_HALO_DBG=6: per workgroup {CU key, start, end of the main loop, end, ...} in 10-ns ticks (dvq_halo_trace_read)
 constexpr int HALO_TRACE_MAX = 32768;
 __device__ unsigned long long g_halo_trace[HALO_TRACE_MAX][6];
-
-__device__ __forceinline__ int xcd_remap(int id, int n) {
-    const int q = n >> 3, r = n & 7;
-    const int xcd = id & 7, j = id >> 3;
-    return (xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q) + j;
-}
 
 // n / d for n * d < 2^32 with magic = ceil(2^32 / d) (0 encodes d == 1): scalar-unit arithmetic (s_mul_hi_u32) instead of the float
 // division sequence the compiler emits for a runtime divisor -- VALU instructions are what a workgroup pays dearly for outside its

@@ -194,6 +194,16 @@ __device__ __forceinline__ T wave_max(T v) {
     return v;
 }
 
+// XCD-aware work-item order (MI355X: block b is dispatched to XCD b % 8, each XCD has a private 4-MiB L2):
+// remap the linear block id so that every XCD walks one CONTIGUOUS range of work items; neighbouring items
+// (adjacent output rows of a conv, the taps of one wgrad split) then share operand rows through the same L2
+// instead of each XCD fetching them again.  Bijective for any item count.
+__device__ __forceinline__ int xcd_remap(int id, int n) {
+    const int q = n >> 3, r = n & 7;
+    const int xcd = id & 7, j = id >> 3;
+    return (xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q) + j;
+}
+
 // ---------------------------------------------------------------------------------------------
 // dropout decisions: keep element `idx` iff dvq_hash32(lo32(idx) * rm + ra + hi32(idx) * 0x9E3779B1) >= p * 2^32, with the
 // odd multiplier rm and the offset ra derived from the 64-bit seed (different seeds are not shifted copies of each other).

@@ -5,7 +5,7 @@
 //     with its gradient w.r.t. the reconstruction's features;
 //   * y = a + s[0] * b with a device-resident scalar (generator loss weighting, vqperceptual_multidisc.py:97-107,139).
 // The 3x3 convolutions of VGG16 and the 4x4 convolutions of the PatchGAN run on the conv kernels (conv_halo.hip /
-// igemm.hip) with the ReLU / LeakyReLU fused into their epilogues; BatchNorm runs on the GroupNorm kernels with one
+// igemm_nt.hip) with the ReLU / LeakyReLU fused into their epilogues; BatchNorm runs on the GroupNorm kernels with one
 // group per channel over the whole batch (groupnorm.hip).
 #include "dvq_common.h"
 

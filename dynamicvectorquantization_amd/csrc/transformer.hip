@@ -5,7 +5,7 @@
 //   embedding gather(+add) / scatter-add    nn.Embedding(padding_idx)       stackgpt.py:136-146,177-199
 //   cross entropy with ignore_index         F.cross_entropy                 stackgpt.py:213-224
 //   dropout (counter-based hash RNG)        nn.Dropout                      stackgpt.py:31-32,82,146
-// The GEMMs (q/k/v/proj/MLP/heads, QK^T, PV and their backward) run on igemm.hip's kernels.
+// The GEMMs (q/k/v/proj/MLP/heads, QK^T, PV and their backward) run on the kernels of igemm_nt.hip / igemm_tn.hip.
 #include "dvq_common.h"
 #include <type_traits>
 

@@ -445,6 +445,17 @@ def test_last_kernel_is_empty_in_a_fresh_process():
     assert out.returncode == 0 and out.stdout.strip() == "b''", out.stdout + out.stderr
 
 
+def test_build_staleness_covers_every_header_and_sources_exist():
+    """an edited header that the build does not watch links stale objects without a word"""
+    from dynamicvectorquantization_amd import build
+    watched = {os.path.realpath(h) for h in build.headers()}
+    on_disk = {os.path.realpath(os.path.join(build.CSRC, f)) for f in os.listdir(build.CSRC) if f.endswith(".h")}
+    assert on_disk and on_disk <= watched, sorted(on_disk - watched)
+    assert os.path.realpath(os.path.join(REPO, "include", "dvq_hip.h")) in watched
+    for src in build.SOURCES + build.PROBE_SOURCES:
+        assert os.path.isfile(os.path.join(build.CSRC, src)), src
+
+
 # every environment switch the native code reads.  Adding one takes an edit here AND a row in the switch table of
 # docs/design/03-kernels.md: a switch nobody lists is a kernel nobody tests.
 CSRC_GETENV_SWITCHES = {
@@ -485,8 +496,10 @@ def test_python_environment_reads_go_through_the_registry():
     from dynamicvectorquantization_amd import losses
     from dynamicvectorquantization_amd import runtime as rt
     pkg = os.path.join(REPO, "dynamicvectorquantization_amd")
-    # the three reads whose argument is no string literal: the accessor's own, and LPIPS' two weight files (named by class attributes)
-    indirect = {("runtime.py", "name"): set(), ("losses.py", "self.ENV_VGG"): {losses.LPIPS.ENV_VGG}, ("losses.py", "self.ENV_LIN"): {losses.LPIPS.ENV_LIN}}
+    # the three reads whose argument is no string literal: the accessor's own, and LPIPS' two weight files (named by class attributes);
+    # and the one read of a name that is not the package's: the build's worker count follows the machine's MAX_JOBS
+    indirect = {("runtime.py", "name"): set(), ("losses.py", "self.ENV_VGG"): {losses.LPIPS.ENV_VGG}, ("losses.py", "self.ENV_LIN"): {losses.LPIPS.ENV_LIN},
+                ("build.py", '"MAX_JOBS"'): set()}
     direct, through_switch, seen_indirect = set(), set(), set()
     for f in sorted(os.listdir(pkg)):
         if not f.endswith(".py"):

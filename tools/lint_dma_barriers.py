@@ -29,11 +29,11 @@ ALLOW = [
     ("conv_halo.hip", "conv3x3_halo_kernel", 1,
      "the bias-publication barrier ahead of the main loop is LDS-only on purpose (inline s_waitcnt lgkmcnt(0) + s_barrier): the first halo / "
      "weight DMA stays in flight across it and is waited for by the chunk barrier (dvq_dma_barrier) that follows"),
-    ("igemm.hip", "gemm_nt_8phase_kernel", 10,
+    ("igemm_nt.hip", "gemm_nt_8phase_kernel", 10,
      "by design: the 8-phase main loop never drains the DMA queue.  A half-tile is published by the counted s_waitcnt vmcnt(6) of phase 3 "
      "(all but the three youngest half-tiles have landed) followed by TWO barriers before its first ds_read; the other barriers of a K tile "
      "separate read and MFMA sections only.  The queue is drained (vmcnt(0)) ahead of the epilogue's barrier."),
-    ("igemm.hip", "gemm_tn_8phase_kernel", 10,
+    ("igemm_tn.hip", "gemm_tn_8phase_kernel", 10,
      "by design, as gemm_nt_8phase_kernel: counted s_waitcnt vmcnt(6) once per K tile, two barriers between that wait and the first transpose "
      "read of the half-tiles it retires, vmcnt(0) ahead of the barrier that ends the loop"),
     ("conv_halo.hip", "conv3x3_halo_wgrad_kernel", 1,
@@ -54,7 +54,7 @@ def asm_of(src):
     out = os.path.join(B.OBJ, "lint", src.replace(".hip", ".s"))
     os.makedirs(os.path.dirname(out), exist_ok=True)
     s = os.path.join(B.CSRC, src)
-    if not os.path.exists(out) or os.path.getmtime(out) < max(os.path.getmtime(s), os.path.getmtime(os.path.join(B.CSRC, "dvq_common.h"))):
+    if B._stale(out, [s] + B.headers()):
         cmd = [B._hipcc()] + B.FLAGS + B.EXTRA_FLAGS.get(src, []) + ["--cuda-device-only", "-S", s, "-o", out]
         r = subprocess.run(cmd, capture_output=True, text=True)
         if r.returncode != 0:
