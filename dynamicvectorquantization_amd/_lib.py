@@ -48,6 +48,7 @@ SIGNATURES = {
     "dvq_check_device": (i32, []),
     "dvq_set_deterministic": (i32, [i32]),
     "dvq_deterministic": (i32, []),
+    "dvq_unordered_launches": (C.c_longlong, []),
     "dvq_set_fp32_split": (i32, [i32]),
     "dvq_fp32_split": (i32, []),
     "dvq_probe_mfma_rate": (i32, [i32, vp, vp, vp]),

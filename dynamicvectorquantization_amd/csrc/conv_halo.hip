@@ -857,6 +857,16 @@ static int halo_try_impl(const void* x, const void* w, const float* bias, const 
         int64_t ws_bytes = 0;
         void* ws = dvq_workspace_stream(stream, &ws_bytes);
         if (ws != nullptr && ws_bytes >= N * out_groups * ntiles * 2 * (int64_t)sizeof(float)) p.stat_part = (float*)ws;
+        if (p.stat_part == nullptr && ntiles > 1) {
+            // no scratch for the per-tile partials: every tile of an image adds into out_stats with fp64 atomics.  Deterministic mode
+            // refuses that form (the caller registers a workspace, or runs the conv without statistics and dvq_gn_stats on its output)
+            if (dvq_deterministic() != 0) {
+                dvq_set_error("conv3x3_halo: deterministic mode needs a registered workspace for the statistics epilogue (%lld bytes)",
+                              (long long)(N * out_groups * ntiles * 2 * (int64_t)sizeof(float)));
+                return DVQ_EWORKSPACE;
+            }
+            dvq_note_unordered();
+        }
     }
     const int64_t blocks = N * p.tiles_y * p.tiles_x * p.gn;
     if (blocks >= (1ll << 31)) return 0;
@@ -1377,6 +1387,7 @@ static int halo_wgrad_impl(const void* x, const void* dy, float* dw, float* db, 
         p.nsplit = 1;
         nblk = (int64_t)p.gi * p.gj;
     }
+    if (p.ws == nullptr && p.nsplit > 1) dvq_note_unordered();       // every split flushes its tile with fp32 atomics
     dvq_note_kernel("conv3x3_halo_wgrad_kernel");
     if (thin) {
         dvq_ensure_dynamic_lds((const void*)conv3x3_halo_wgrad_kernel<true>, 2 * WSTAGE);

@@ -39,6 +39,10 @@ void dvq_set_error(const char* fmt, ...);
 extern thread_local const char* dvq_kernel_note;
 static inline void dvq_note_kernel(const char* family) { dvq_kernel_note = family; }
 
+// a launch whose floating-point result depends on arrival order (float atomics with several writers per address): every launcher
+// calls this at the dispatch branch that selects such a kernel or epilogue (dvq_unordered_launches)
+void dvq_note_unordered(void);
+
 #define DVQ_REQUIRE(cond, code, ...)      \
     do {                                  \
         if (!(cond)) {                    \
@@ -78,6 +82,17 @@ void dvq_ensure_dynamic_lds(const void* kernel, int bytes);
 void* dvq_workspace(int64_t* bytes);
 // the calling stream's slot of that buffer (1/4 of it): concurrent streams never share scratch
 void* dvq_workspace_stream(hipStream_t stream, int64_t* bytes);
+// deterministic mode (dvq_deterministic): `bytes` of the calling stream's slot for per-split partials, or null -- the caller then
+// launches UNSPLIT or returns DVQ_EWORKSPACE, never the atomic form
+static inline void* dvq_det_scratch(hipStream_t stream, int64_t bytes) {
+    int64_t have = 0;
+    void* p = dvq_workspace_stream(stream, &have);
+    return p != nullptr && have >= bytes ? p : nullptr;
+}
+// out[i] += part[0][i] + part[1][i] + ... in split order, i < n, part[s] at part + s * stride: one owner per output element (a
+// thread, or a wave whose lanes stride the splits and meet in wave_sum's fixed tree where n is small and nsplit large)
+int dvq_det_fold_f32(float* out, const float* part, int nsplit, int64_t stride, int64_t n, hipStream_t stream);
+int dvq_det_fold_f64(double* out, const double* part, int nsplit, int64_t stride, int64_t n, hipStream_t stream);
 
 // ---------------------------------------------------------------------------------------------
 // bf16 <-> f32 (device)

@@ -46,11 +46,16 @@ __device__ __forceinline__ GnGeom gn_geom(int64_t C, int G) {
     return g;
 }
 
-template <typename T>
+// DET (deterministic mode): no float atomics.  Every thread parks the (sum, sum of squares) of each group its 8 channels touch in
+// an LDS slot of its own, thread g then adds group g's slots in (pixel row, column) order; the workgroup's sums go to
+// part[block][n][2 G] for dvq_det_fold_f64 (block order), or straight into stats when the launch has one workgroup per image.
+// rpb = pixels per workgroup (gn_rows_per_block(HW); HW in the unsplit deterministic launch).
+template <typename T, bool DET>
 __global__ __launch_bounds__(256) void gn_stats_kernel(const T* __restrict__ x, int64_t HW, int64_t C, int G,
-                                                       double* __restrict__ stats) {
+                                                       double* __restrict__ stats, int64_t rpb, double* __restrict__ part) {
     extern __shared__ __attribute__((aligned(16))) char smem[];
     double* gs = reinterpret_cast<double*>(smem);   // [G][2]
+    double* slot = gs + 2 * G;                      // DET: [256][8][2]
     const GnGeom ge = gn_geom(C, G);
     const int64_t n = blockIdx.y;
     for (int i = threadIdx.x; i < 2 * G; i += 256) gs[i] = 0.0;
@@ -60,9 +65,9 @@ __global__ __launch_bounds__(256) void gn_stats_kernel(const T* __restrict__ x, 
 #pragma unroll
     for (int j = 0; j < 8; ++j) s[j] = q[j] = 0.f;
     if (prow < ge.rows_per_pass) {
-        const int64_t p_end = min((int64_t)(blockIdx.x + 1) * gn_rows_per_block(HW), HW);
+        const int64_t p_end = min((int64_t)(blockIdx.x + 1) * rpb, HW);
         const T* base = x + n * HW * C + col * 8;
-        for (int64_t p = (int64_t)blockIdx.x * gn_rows_per_block(HW) + prow; p < p_end; p += ge.rows_per_pass) {
+        for (int64_t p = (int64_t)blockIdx.x * rpb + prow; p < p_end; p += ge.rows_per_pass) {
             float v[8];
             load8(base + p * C, v);
 #pragma unroll
@@ -80,14 +85,41 @@ __global__ __launch_bounds__(256) void gn_stats_kernel(const T* __restrict__ x, 
             dq += (double)q[j];
             const int g = (col * 8 + j) / ge.cpg;
             if (j == 7 || (col * 8 + j + 1) / ge.cpg != g) {
-                atomicAdd(&gs[2 * g], ds);
-                atomicAdd(&gs[2 * g + 1], dq);
+                if constexpr (DET) {
+                    const int piece = g - (col * 8) / ge.cpg;          // < 8
+                    slot[(threadIdx.x * 8 + piece) * 2] = ds;
+                    slot[(threadIdx.x * 8 + piece) * 2 + 1] = dq;
+                } else {
+                    atomicAdd(&gs[2 * g], ds);
+                    atomicAdd(&gs[2 * g + 1], dq);
+                }
                 ds = dq = 0.0;
             }
         }
     }
     __syncthreads();
-    for (int i = threadIdx.x; i < 2 * G; i += 256) atomicAdd(&stats[n * 2 * G + i], gs[i]);
+    if constexpr (DET) {
+        for (int g = threadIdx.x; g < G; g += 256) {
+            const int c_lo = (g * ge.cpg) / 8, c_hi = ((g + 1) * ge.cpg - 1) / 8;      // columns that hold channels of group g
+            double ds = 0.0, dq = 0.0;
+            for (int r = 0; r < ge.rows_per_pass; ++r)
+                for (int c = c_lo; c <= c_hi; ++c) {
+                    const int t = r * ge.ncol + c, piece = g - (c * 8) / ge.cpg;
+                    ds += slot[(t * 8 + piece) * 2];
+                    dq += slot[(t * 8 + piece) * 2 + 1];
+                }
+            double* dst = part != nullptr ? part + ((int64_t)blockIdx.x * gridDim.y + n) * 2 * G : stats + n * 2 * G;
+            if (part != nullptr) {
+                dst[2 * g] = ds;
+                dst[2 * g + 1] = dq;
+            } else {                                  // one workgroup per image: the only writer
+                dst[2 * g] += ds;
+                dst[2 * g + 1] += dq;
+            }
+        }
+    } else {
+        for (int i = threadIdx.x; i < 2 * G; i += 256) atomicAdd(&stats[n * 2 * G + i], gs[i]);
+    }
 }
 
 __device__ __forceinline__ void gn_mean_rstd(const double* stats, int64_t n, int G, int g, double cnt, float eps,
@@ -182,7 +214,7 @@ __global__ __launch_bounds__(256) void gn_bwd_reduce_kernel(const T* __restrict_
                                                             const float* __restrict__ gamma,
                                                             const float* __restrict__ beta, double* __restrict__ red,
                                                             float* __restrict__ dgamma, float* __restrict__ dbeta,
-                                                            float* __restrict__ part) {
+                                                            float* __restrict__ part, int det) {
     extern __shared__ __attribute__((aligned(16))) char smem[];
     float* sA = reinterpret_cast<float*>(smem);   // [C] sum dz
     float* sB = sA + C;                            // [C] sum dz*xhat
@@ -234,13 +266,31 @@ __global__ __launch_bounds__(256) void gn_bwd_reduce_kernel(const T* __restrict_
             ld8<NT>(dy + off + p * C, g8);
             accumulate(v, g8);
         }
+        if (det) {
+            // deterministic mode: one LDS row [2 C] per pixel row of the pass instead of LDS float atomics, added below in row order
+            float* row = sA + (1 + prow) * 2 * C;
 #pragma unroll
-        for (int j = 0; j < 8; ++j) {
-            atomicAdd(&sA[col * 8 + j], a[j]);
-            atomicAdd(&sB[col * 8 + j], b[j]);
+            for (int j = 0; j < 8; ++j) {
+                row[col * 8 + j] = a[j];
+                row[C + col * 8 + j] = b[j];
+            }
+        } else {
+#pragma unroll
+            for (int j = 0; j < 8; ++j) {
+                atomicAdd(&sA[col * 8 + j], a[j]);
+                atomicAdd(&sB[col * 8 + j], b[j]);
+            }
         }
     }
     __syncthreads();
+    if (det) {
+        for (int i = threadIdx.x; i < 2 * C; i += 256) {
+            float t = 0.f;
+            for (int r = 0; r < ge.rows_per_pass; ++r) t += sA[(1 + r) * 2 * C + i];
+            sA[i] = t;
+        }
+        __syncthreads();
+    }
     if (part != nullptr) {
         // per-block partials, folded by gn_bwd_finalize_kernel: with thousands of blocks adding into the same C + 2 G addresses the
         // serial chains of memory-side atomics, not the two tensor reads, set this kernel's time (3.7 TB/s against 5.1 for its
@@ -268,34 +318,46 @@ __global__ __launch_bounds__(256) void gn_bwd_reduce_kernel(const T* __restrict_
 // (32 channels x {sum dz, sum dz*xhat}); -> red[n][g] (+=, one writer), dgamma / dbeta (one atomic per image and channel)
 __global__ __launch_bounds__(256) void gn_bwd_finalize_kernel(const float* __restrict__ part, int nb, int64_t C, int G,
                                                               const float* __restrict__ gamma, double* __restrict__ red,
-                                                              float* __restrict__ dgamma, float* __restrict__ dbeta) {
+                                                              float* __restrict__ dgamma, float* __restrict__ dbeta, int n_all,
+                                                              float* __restrict__ img) {
     __shared__ double sm[4][64];
-    const int64_t n = blockIdx.y;
     const int rg = threadIdx.x >> 6, l = threadIdx.x & 63;
     const int ab = l >> 5, c = blockIdx.x * 32 + (l & 31);        // ab: 0 = sum dz (dbeta), 1 = sum dz*xhat (dgamma)
-    // fp64 across the blocks, like the atomics it replaces: BatchNorm's backward subtracts the mean of a nearly constant gradient
-    double acc = 0.0;
-    if (c < C) {
-        const float* src = part + (int64_t)n * nb * 2 * C + ab * C + c;
-        double a4[4] = {0.0, 0.0, 0.0, 0.0};
-        int b = rg;
-        for (; b + 12 < nb; b += 16) {
+    // deterministic mode: img != null -- image blockIdx.y STORES its (dbeta, dgamma) terms at img[n][2][C], dvq_det_fold_f32 adds the
+    // images in order; n_all > 0 (no scratch for img, grid.y = 1) -- the workgroup walks the n_all images in order and is the only
+    // writer of its dgamma / dbeta elements.  Default: image blockIdx.y, one atomic per image and channel
+    const int64_t n_lo = n_all > 0 ? 0 : blockIdx.y, n_hi = n_all > 0 ? n_all : blockIdx.y + 1;
+    float dsum = 0.f;
+    for (int64_t n = n_lo; n < n_hi; ++n) {
+        // fp64 across the blocks, like the atomics it replaces: BatchNorm's backward subtracts the mean of a nearly constant gradient
+        double acc = 0.0;
+        if (c < C) {
+            const float* src = part + (int64_t)n * nb * 2 * C + ab * C + c;
+            double a4[4] = {0.0, 0.0, 0.0, 0.0};
+            int b = rg;
+            for (; b + 12 < nb; b += 16) {
 #pragma unroll
-            for (int u = 0; u < 4; ++u) a4[u] += (double)src[(int64_t)(b + 4 * u) * 2 * C];
+                for (int u = 0; u < 4; ++u) a4[u] += (double)src[(int64_t)(b + 4 * u) * 2 * C];
+            }
+            for (; b < nb; b += 4) a4[0] += (double)src[(int64_t)b * 2 * C];
+            acc = (a4[0] + a4[1]) + (a4[2] + a4[3]);
         }
-        for (; b < nb; b += 4) a4[0] += (double)src[(int64_t)b * 2 * C];
-        acc = (a4[0] + a4[1]) + (a4[2] + a4[3]);
+        __syncthreads();
+        sm[rg][l] = acc;
+        __syncthreads();
+        if (rg != 0) continue;
+        const double v = (sm[0][l] + sm[1][l]) + (sm[2][l] + sm[3][l]);
+        if (n_all > 0) dsum += (float)v;
+        else if (img != nullptr) {
+            if (c < C) img[(n * 2 + ab) * C + c] = (float)v;
+        } else if (c < C) atomicAdd(ab ? &dgamma[c] : &dbeta[c], (float)v);
+        // group sums: gamma-weighted over the cpg (power of two <= 32, launcher) adjacent channels of a group
+        const int cpg = (int)(C / G);
+        double w = c < C ? (double)gamma[c] * v : 0.0;
+        for (int off = 1; off < cpg; off <<= 1) w += __shfl_xor(w, off, 64);
+        if (c < C && (c & (cpg - 1)) == 0) red[(n * G + c / cpg) * 2 + ab] += w;
     }
-    sm[rg][l] = acc;
-    __syncthreads();
-    if (rg != 0) return;
-    const double v = (sm[0][l] + sm[1][l]) + (sm[2][l] + sm[3][l]);
-    if (c < C) atomicAdd(ab ? &dgamma[c] : &dbeta[c], (float)v);
-    // group sums: gamma-weighted over the cpg (power of two <= 32, launcher) adjacent channels of a group
-    const int cpg = (int)(C / G);
-    double w = c < C ? (double)gamma[c] * v : 0.0;
-    for (int off = 1; off < cpg; off <<= 1) w += __shfl_xor(w, off, 64);
-    if (c < C && (c & (cpg - 1)) == 0) red[(n * G + c / cpg) * 2 + ab] += w;
+    if (n_all > 0 && rg == 0 && c < C) (ab ? dgamma : dbeta)[c] += dsum;
 }
 
 template <typename T, int ACT, bool NT>
@@ -415,8 +477,26 @@ int dvq_gn_stats(const void* x, int dtype, int64_t N, int64_t HW, int64_t C, int
     DVQ_REQUIRE(x && stats, DVQ_EINVAL, "dvq_gn_stats: null pointer");
     if (int e = gn_check("dvq_gn_stats", N, HW, C, G)) return e;
     dim3 grid((unsigned)cdiv64(HW, gn_rows_per_block(HW)), (unsigned)N);
-    DVQ_DISPATCH_DTYPE(dtype, T, gn_stats_kernel<T><<<grid, dim3(256), 2 * G * sizeof(double), (hipStream_t)stream>>>(
-                                     (const T*)x, HW, C, G, stats););
+    hipStream_t s = (hipStream_t)stream;
+    if (dvq_deterministic() != 0) {
+        // partials [block][N][2 G] + a fold in block order; without scratch one workgroup per image walks every pixel
+        int64_t rpb = gn_rows_per_block(HW);
+        const int64_t span = N * 2 * G;
+        double* part = grid.x > 1 ? (double*)dvq_det_scratch(s, (int64_t)grid.x * span * 8) : nullptr;
+        const int nb = (int)grid.x;
+        if (part == nullptr) {
+            rpb = HW;
+            grid.x = 1;
+        }
+        const size_t lds = (2 * G + 256 * 8 * 2) * sizeof(double);
+        DVQ_DISPATCH_DTYPE(dtype, T, gn_stats_kernel<T, true><<<grid, dim3(256), lds, s>>>((const T*)x, HW, C, G, stats, rpb, part););
+        DVQ_CHECK_LAUNCH("gn_stats");
+        if (part != nullptr) return dvq_det_fold_f64(stats, part, nb, span, span, s);
+        return DVQ_OK;
+    }
+    dvq_note_unordered();               // fp64 atomics from every pixel row of a workgroup (LDS) and from every workgroup of an image
+    DVQ_DISPATCH_DTYPE(dtype, T, gn_stats_kernel<T, false><<<grid, dim3(256), 2 * G * sizeof(double), s>>>(
+                                     (const T*)x, HW, C, G, stats, (int64_t)gn_rows_per_block(HW), nullptr););
     DVQ_CHECK_LAUNCH("gn_stats");
     return DVQ_OK;
 }
@@ -464,12 +544,39 @@ int dvq_gn_bwd_reduce(const void* x, const void* dy, int dtype, int64_t N, int64
     hipStream_t s = (hipStream_t)stream;
     size_t lds = 2 * C * sizeof(float);
     const int64_t cpg = C / G;
-    if (partials != nullptr && ((cpg & (cpg - 1)) != 0 || cpg > 32)) partials = nullptr;      // (the finalize kernel folds a group inside a wave)
-    DVQ_DISPATCH_DTYPE(dtype, T, GN_ACT_SWITCH(gn_bwd_reduce_kernel, lds, (const T*)x, (const T*)dy, HW, C, G, mean_rstd, gamma, beta, red, dgamma, dbeta, partials));
+    const bool fin_ok = (cpg & (cpg - 1)) == 0 && cpg <= 32;                                  // (the finalize kernel folds a group inside a wave)
+    if (partials != nullptr && !fin_ok) partials = nullptr;
+    const int det = dvq_deterministic() != 0 ? 1 : 0;
+    float* img = nullptr;
+    if (det) {
+        // per-workgroup partials (the caller's, else workspace) + the finalize kernel walking blocks and images in order; LDS rows per
+        // pixel row instead of LDS float atomics
+        DVQ_REQUIRE(fin_ok, DVQ_ESHAPE, "dvq_gn_bwd_reduce: deterministic mode needs a power-of-two C / G <= 32 (got %lld)", (long long)cpg);
+        const int64_t pbytes = ((int64_t)dvq_gn_bwd_partial_bytes(N, HW, C) + 255) & ~(int64_t)255, ibytes = N * 2 * C * 4;
+        if (partials == nullptr) {
+            char* w = (char*)dvq_det_scratch(s, pbytes + ibytes);
+            if (w == nullptr) w = (char*)dvq_det_scratch(s, pbytes);
+            else img = (float*)(w + pbytes);
+            partials = (float*)w;
+        } else if (N > 1) {
+            img = (float*)dvq_det_scratch(s, ibytes);           // per-image terms [N][2][C]; none: one workgroup per slice walks the images
+        }
+        DVQ_REQUIRE(partials != nullptr, DVQ_EWORKSPACE, "dvq_gn_bwd_reduce: deterministic mode needs a partials buffer or a registered workspace");
+        lds += (size_t)(256 / (C / 8)) * 2 * C * sizeof(float);       // <= 16 KiB of rows on top of the 2 C sums (C <= 2048: 32 KiB in all)
+    } else {
+        dvq_note_unordered();           // LDS float atomics across the pixel rows of a pass; global atomics on dgamma / dbeta (/ red)
+    }
+    DVQ_DISPATCH_DTYPE(dtype, T, GN_ACT_SWITCH(gn_bwd_reduce_kernel, lds, (const T*)x, (const T*)dy, HW, C, G, mean_rstd, gamma, beta, red, dgamma, dbeta, partials, det));
     DVQ_CHECK_LAUNCH("gn_bwd_reduce");
     if (partials != nullptr) {
-        gn_bwd_finalize_kernel<<<dim3((unsigned)cdiv64(C, 32), (unsigned)N), dim3(256), 0, s>>>(partials, (int)grid.x, C, G, gamma, red, dgamma, dbeta);
+        const bool serial = det && img == nullptr;
+        gn_bwd_finalize_kernel<<<dim3((unsigned)cdiv64(C, 32), serial ? 1u : (unsigned)N), dim3(256), 0, s>>>(partials, (int)grid.x, C, G, gamma, red, dgamma, dbeta,
+                                                                                                            serial ? (int)N : 0, img);
         DVQ_CHECK_LAUNCH("gn_bwd_finalize");
+        if (img != nullptr) {
+            if (int e = dvq_det_fold_f32(dbeta, img, (int)N, 2 * C, C, s)) return e;
+            return dvq_det_fold_f32(dgamma, img + C, (int)N, 2 * C, C, s);
+        }
     }
     return DVQ_OK;
 }

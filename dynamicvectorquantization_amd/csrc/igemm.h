@@ -57,6 +57,8 @@ struct TnParams {
     int64_t dws_stride;   //   offsets as C, which must be one contiguous span) and its bias partial at dws_bias + s * I; tn_det_fold_kernel
     float* dws_bias;      //   adds the slices to C / colsumA in split order.  null: fp32 atomics straight into C (default)
     int split3;           // fp32 operands: two bf16 planes + three bf16 MFMA passes (dvq_set_fp32_split)
+    int det;              // deterministic mode: igemm_tn_kernel adds the column sums of a workgroup's row blocks in LDS, in block order,
+                          //   instead of with one atomic per thread (several threads of ONE workgroup own the same column)
 };
 
 // preferred impl codes (include/dvq_hip.h) ask for a kernel and take the automatic choice on a shape that kernel does not run

@@ -192,8 +192,31 @@ __global__ __launch_bounds__(256, 2) void igemm_tn_kernel(TnParams p) {
 #pragma unroll
             for (int r = 0; r < 16; ++r) {
                 const int row = i0 + wm * 64 + mt * 32 + (r & 3) + 8 * (r >> 2) + 4 * half;
-                if (row < p.I) atomicAdd(Cg + tn_c_offset(p, row, tap, col), acc[mt][nt][r]);
+                if (row < p.I) {
+                    if (p.dws != nullptr) p.dws[(int64_t)split * p.dws_stride + tn_c_offset(p, row, tap, col)] = acc[mt][nt][r];
+                    else atomicAdd(Cg + tn_c_offset(p, row, tap, col), acc[mt][nt][r]);
+                }
             }
+    }
+    if (p.det) {
+        // deterministic mode: the BK / VN row blocks of the workgroup park their column sums in LDS (the stages have been consumed:
+        // the main loop ends on a barrier), thread `col` adds them in block order and is the column's only writer of this split
+        if (p.colsumA == nullptr || tap != 0 || jt != 0) return;
+        constexpr int NMB = (SPLIT_OPS ? 128 : 256) / NBLK_COL;
+        float* sb = reinterpret_cast<float*>(smem);              // [NMB][TILE]
+        if (doA) {
+#pragma unroll
+            for (int c = 0; c < VN; ++c) sb[mb * TILE + cb * VN + c] = bsum[c];
+        }
+        __syncthreads();
+        if (tid < TILE && i0 + tid < p.I) {
+            float t = 0.f;
+#pragma unroll
+            for (int m = 0; m < NMB; ++m) t += sb[m * TILE + tid];
+            if (p.dws_bias != nullptr) p.dws_bias[(int64_t)split * p.I + i0 + tid] = t;
+            else p.colsumA[i0 + tid] += t;                       // (unsplit launch)
+        }
+        return;
     }
     if (do_bias) {
 #pragma unroll
@@ -1201,6 +1224,7 @@ int launch_tn_wide(TnParams p, int64_t batch, bool det, bool eight_phase, hipStr
         p.m_per_split = (int)(cdiv64(p.Mred, BK) * BK);
         p.nsplit = 1;
     }
+    if (p.ws == nullptr && p.nsplit > 1) dvq_note_unordered();      // two splits (or a batched product without scratch): fp32 atomics into C
     if (eight_phase) {
         dvq_note_kernel("gemm_tn_8phase_kernel");
         dvq_ensure_dynamic_lds((const void*)gemm_tn_8phase_kernel, 8 * 64 * 256);
@@ -1243,6 +1267,7 @@ int launch_tn_patch(TnParams p, int64_t batch, bool det, hipStream_t s) {
         p.m_per_split = (int)npatch;
         p.nsplit = 1;
     }
+    if (p.nsplit > 1 && !dfold) dvq_note_unordered();
     dvq_note_kernel("conv_tn_patch_kernel");
     dvq_ensure_dynamic_lds((const void*)conv_tn_patch_kernel, 2 * TSTAGEB);
     conv_tn_patch_kernel<<<dim3((unsigned)(ptiles * p.nsplit)), dim3(256), 2 * TSTAGEB, s>>>(p);
@@ -1274,13 +1299,16 @@ int launch_tn_tiles(TnParams p, int64_t batch, bool tr, bool det, hipStream_t s)
     int64_t gspan = 0;
     bool gfold = false;
     if (det && p.nsplit > 1) {
-        gfold = tr && tn_det_setup(p, batch, s, &gspan);          // (the transpose-read kernel stores partials)
-        if (!gfold) {                                                                    // other kernels / no scratch: unsplit
+        gfold = tn_det_setup(p, batch, s, &gspan);                // partials + fold in split order
+        if (!gfold) {                                                                    // batched / strided C / no scratch: unsplit
             p.m_per_split = (int)(cdiv64(p.Mred, BK) * BK);
             p.nsplit = 1;
             grid = dim3((unsigned)(p.itiles * p.jtiles * tapblk), 1, (unsigned)batch);
         }
     }
+    // fp32 atomics from several splits per element -- and, on the register-staged kernel, from the row blocks of ONE workgroup per column sum
+    if (p.nsplit > 1 && !gfold) dvq_note_unordered();
+    else if (!tr && !det && p.colsumA != nullptr) dvq_note_unordered();
     dvq_note_kernel(tr ? "igemm_tn_tr_kernel" : "igemm_tn_kernel");
     if (tr) {
         if (p.conv) {
@@ -1343,9 +1371,10 @@ int launch_tn(TnParams p, int64_t batch, int impl, hipStream_t s) {
     p.itiles = (int)cdiv64(p.I, TILE);
     p.jtiles = (int)cdiv64(p.J, TILE);
     p.thin = (p.conv && tr && p.J == 8 && p.taps <= 16 && p.taps > 1) ? 1 : 0;
-    // opt-in: no fp32 atomics from more than one workgroup per output element.  bf16 operands only (the training path): the fp32
-    // parity-mode kernel keeps its splits and atomics (unsplit it would put 9 workgroups on a 4-M-row reduction)
-    const bool det = dvq_deterministic() != 0 && sizeof(T) == 2;
+    // opt-in: no fp32 atomics from more than one writer per output element, for both operand types: every split kernel stores
+    // partials for tn_det_fold_kernel, or runs unsplit where C is batched / strided or no scratch is registered
+    const bool det = dvq_deterministic() != 0;
+    p.det = det ? 1 : 0;
     if constexpr (sizeof(T) == 2) {
         // DVQ_IMPL_WIDE_PIPE asks for the per-stage-drain kernel (tests) in place of the 8-phase one
         if ((impl == DVQ_IMPL_AUTO || impl == DVQ_IMPL_WIDE_PIPE) && tn_wide_ok(p))

@@ -139,7 +139,8 @@ template <typename T, int L>
 __global__ __launch_bounds__(256) void lpips_head_kernel(const T* __restrict__ f0, const T* __restrict__ f1,
                                                          const float* __restrict__ lin, int64_t N, int64_t HW,
                                                          float* __restrict__ val, float gscale, T* __restrict__ df1,
-                                                         unsigned drop_thr, float drop_scale, unsigned rm, unsigned ra) {
+                                                         unsigned drop_thr, float drop_scale, unsigned rm, unsigned ra,
+                                                         float* __restrict__ part_out) {
     constexpr int C = L * 8;
     constexpr int PPB = 256 / L;          // pixels per block pass
     const int lane = threadIdx.x % L, slot = threadIdx.x / L;
@@ -211,7 +212,10 @@ __global__ __launch_bounds__(256) void lpips_head_kernel(const T* __restrict__ f
     __shared__ float part[4];
     if ((threadIdx.x & 63) == 0) part[threadIdx.x >> 6] = vsum;
     __syncthreads();
-    if (threadIdx.x == 0) atomicAdd(&val[n], (part[0] + part[1] + part[2] + part[3]) * inv_hw);
+    if (threadIdx.x != 0) return;
+    const float t = (part[0] + part[1] + part[2] + part[3]) * inv_hw;
+    if (part_out != nullptr) part_out[(int64_t)blockIdx.x * gridDim.y + n] = t;      // deterministic mode: [block][N], folded in block order
+    else atomicAdd(&val[n], t);
 }
 
 }  // namespace
@@ -272,14 +276,22 @@ int dvq_lpips_head_drop(const void* f0, const void* f1, const float* lin, int dt
     int64_t bx = cdiv64(HW, (int64_t)ppb * 8LL);
     if (bx > 256) bx = 256;
     if (bx < 1) bx = 1;
-    dim3 grid((unsigned)bx, (unsigned)N);
     hipStream_t s = (hipStream_t)stream;
+    float* part = nullptr;
+    if (bx > 1) {
+        if (dvq_deterministic() != 0) {                    // partials [block][N] + a fold in block order; no scratch: one workgroup per image
+            part = (float*)dvq_det_scratch(s, bx * N * 4);
+            if (part == nullptr) bx = 1;
+        } else dvq_note_unordered();                       // one fp32 atomic per workgroup into val[n]
+    }
+    dim3 grid((unsigned)bx, (unsigned)N);
 #define HEAD(L_)                                                                                                   \
     DVQ_DISPATCH_DTYPE(dtype, T, lpips_head_kernel<T, L_><<<grid, dim3(256), 0, s>>>((const T*)f0, (const T*)f1, lin, N, HW, val, \
-                                                                                    gscale, (T*)df1, drop_thr, drop_scale, rm, ra););
+                                                                                    gscale, (T*)df1, drop_thr, drop_scale, rm, ra, part););
     if (L == 8) { HEAD(8) } else if (L == 16) { HEAD(16) } else if (L == 32) { HEAD(32) } else { HEAD(64) }
 #undef HEAD
     DVQ_CHECK_LAUNCH("lpips_head");
+    if (part != nullptr) return dvq_det_fold_f32(val, part, (int)bx, N, N, s);
     return DVQ_OK;
 }
 

@@ -18,6 +18,7 @@ void dvq_set_error(const char* fmt, ...) {
     va_end(ap);
 }
 
+#include <atomic>
 #include <mutex>
 #include <vector>
 void dvq_ensure_dynamic_lds(const void* kernel, int bytes) {
@@ -245,12 +246,13 @@ __global__ __launch_bounds__(256) void add_bias_bcast_kernel(const T* __restrict
 // combined with fp32 atomics (one per column and batch chunk)
 template <typename T>
 __global__ __launch_bounds__(256) void sum_batch_kernel(const T* __restrict__ x, int64_t batch, int64_t inner,
-                                                        float* __restrict__ out, int64_t rows_per_chunk) {
+                                                        float* __restrict__ out, int64_t rows_per_chunk, float* __restrict__ part) {
     const int64_t b0 = (int64_t)blockIdx.y * rows_per_chunk, b1 = min(batch, b0 + rows_per_chunk);
     for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < inner; i += (int64_t)gridDim.x * 256) {
         float acc = 0.f;
         for (int64_t b = b0; b < b1; ++b) acc += ElemIO<T>::load(x + b * inner + i);
         if (gridDim.y == 1) out[i] += acc;
+        else if (part != nullptr) part[(int64_t)blockIdx.y * inner + i] = acc;       // deterministic mode: dvq_det_fold_f32 adds the chunks in order
         else atomicAdd(&out[i], acc);
     }
 }
@@ -259,7 +261,8 @@ __global__ __launch_bounds__(256) void sum_batch_kernel(const T* __restrict__ x,
 // LDS and issues one atomic per column and batch chunk
 template <typename T>
 __global__ __launch_bounds__(256) void sum_batch_vec_kernel(const T* __restrict__ x, int64_t batch, int64_t inner8,
-                                                            float* __restrict__ out, int64_t rows_per_chunk, int cvb_log2) {
+                                                            float* __restrict__ out, int64_t rows_per_chunk, int cvb_log2,
+                                                            float* __restrict__ part) {
     __shared__ float red[256 * 8];
     const int cvb = 1 << cvb_log2, rlanes = 256 >> cvb_log2;
     const int cv = threadIdx.x & (cvb - 1), rl = threadIdx.x >> cvb_log2;
@@ -284,6 +287,7 @@ __global__ __launch_bounds__(256) void sum_batch_vec_kernel(const T* __restrict_
         const int64_t col = (int64_t)blockIdx.x * ncol + threadIdx.x;
         if (col < inner8 * 8) {
             if (gridDim.y == 1) out[col] += t;
+            else if (part != nullptr) part[(int64_t)blockIdx.y * inner8 * 8 + col] = t;
             else atomicAdd(&out[col], t);
         }
     }
@@ -523,7 +527,7 @@ __global__ __launch_bounds__(256) void nhwc_pad_to_nchw_kernel(const T* __restri
 
 __global__ __launch_bounds__(256) void l1_loss_kernel(const float* __restrict__ x, const float* __restrict__ xr,
                                                       int64_t n, double* loss_sum, const float* __restrict__ scale_dev,
-                                                      float* __restrict__ g) {
+                                                      float* __restrict__ g, double* __restrict__ part_out) {
     __shared__ double part[4];
     const float sc = (g && scale_dev) ? scale_dev[0] : 0.f;
     float acc = 0.f;
@@ -543,7 +547,11 @@ __global__ __launch_bounds__(256) void l1_loss_kernel(const float* __restrict__ 
     dacc = wave_sum(dacc);
     if ((threadIdx.x & 63) == 0) part[threadIdx.x >> 6] = dacc;
     __syncthreads();
-    if (threadIdx.x == 0 && loss_sum) atomicAdd(loss_sum, part[0] + part[1] + part[2] + part[3]);
+    if (threadIdx.x != 0 || !loss_sum) return;
+    const double t = part[0] + part[1] + part[2] + part[3];
+    if (part_out != nullptr) part_out[blockIdx.x] = t;            // deterministic mode: one partial per workgroup, folded in index order
+    else if (gridDim.x == 1) loss_sum[0] += t;
+    else atomicAdd(loss_sum, t);
 }
 
 __global__ __launch_bounds__(256) void adam_kernel(float* __restrict__ p, const float* __restrict__ g,
@@ -828,7 +836,50 @@ __global__ __launch_bounds__(256) void mfma_rate_kernel(const uint4* __restrict_
     }
 }
 
+// deterministic folds (dvq_det_fold_f32 / _f64).  WAVE = false: thread e owns out[e] and walks the splits in index order; 64-thread
+// workgroups, so that an output of a few hundred elements still lands on several CUs.  WAVE = true (few outputs, many splits): a
+// wave owns out[e], lane l adds splits l, l + 64, ... in order and the 64 lane sums meet in wave_sum's fixed butterfly.
+template <typename F, bool WAVE>
+__global__ __launch_bounds__(64) void det_fold_kernel(F* __restrict__ out, const F* __restrict__ part, int nsplit, int64_t stride, int64_t n) {
+    if constexpr (WAVE) {
+        const int64_t e = blockIdx.x;
+        F acc = (F)0;
+        for (int sidx = threadIdx.x; sidx < nsplit; sidx += 64) acc += part[(int64_t)sidx * stride + e];
+        acc = wave_sum(acc);
+        if (threadIdx.x == 0) out[e] += acc;
+    } else {
+        const int64_t e = (int64_t)blockIdx.x * 64 + threadIdx.x;
+        if (e >= n) return;
+        F acc = (F)0;
+        int sidx = 0;
+        for (; sidx + 8 <= nsplit; sidx += 8) {          // eight loads in flight, added in split order all the same
+            F v[8];
+#pragma unroll
+            for (int u = 0; u < 8; ++u) v[u] = part[(int64_t)(sidx + u) * stride + e];
+#pragma unroll
+            for (int u = 0; u < 8; ++u) acc += v[u];
+        }
+        for (; sidx < nsplit; ++sidx) acc += part[(int64_t)sidx * stride + e];
+        out[e] += acc;
+    }
+}
+
+template <typename F>
+int det_fold(F* out, const F* part, int nsplit, int64_t stride, int64_t n, hipStream_t s) {
+    DVQ_REQUIRE(out && part && nsplit > 0 && n > 0 && stride >= n, DVQ_EINVAL, "det_fold: bad arguments");
+    if (n <= 64 && nsplit >= 128) det_fold_kernel<F, true><<<dim3((unsigned)n), dim3(64), 0, s>>>(out, part, nsplit, stride, n);
+    else det_fold_kernel<F, false><<<dim3((unsigned)cdiv64(n, 64)), dim3(64), 0, s>>>(out, part, nsplit, stride, n);
+    DVQ_CHECK_LAUNCH("det_fold");
+    return DVQ_OK;
+}
+
 }  // namespace
+
+int dvq_det_fold_f32(float* out, const float* part, int nsplit, int64_t stride, int64_t n, hipStream_t s) { return det_fold<float>(out, part, nsplit, stride, n, s); }
+int dvq_det_fold_f64(double* out, const double* part, int nsplit, int64_t stride, int64_t n, hipStream_t s) { return det_fold<double>(out, part, nsplit, stride, n, s); }
+
+static std::atomic<long long> g_unordered{0};
+void dvq_note_unordered(void) { g_unordered.fetch_add(1, std::memory_order_relaxed); }
 
 // =================================================================================================
 static void* g_ws_ptr = nullptr;
@@ -845,7 +896,8 @@ void* dvq_workspace(int64_t* bytes) {
 //     that stream until dvq_workspace_release(stream) (runtime.StepGraph drops it with the recording) or dvq_set_workspace;
 //   * an unpinned slot may be handed to a new stream only when its owner is idle (hipStreamQuery == hipSuccess: nothing that
 //     could still write partials there), least recently used first;
-//   * otherwise the caller gets nullptr, which every user treats as "no workspace" (split kernels fall back to fp32 atomics).
+//   * otherwise the caller gets nullptr, which every user treats as "no workspace": split kernels fall back to fp32 atomics (and
+//     count the launch, dvq_unordered_launches) -- in deterministic mode to an UNSPLIT launch or DVQ_EWORKSPACE, never to atomics.
 // The tables are guarded by a mutex (the autograd engine may call from its own thread).
 static constexpr int DVQ_WS_SLOTS = 8;
 static hipStream_t g_ws_stream[DVQ_WS_SLOTS] = {};
@@ -922,7 +974,8 @@ int dvq_set_fp32_split(int on) {
 
 const char* dvq_last_error(void) { return g_err; }
 const char* dvq_last_kernel(void) { return dvq_kernel_note; }
-int dvq_version(void) { return 117; }
+int dvq_version(void) { return 118; }
+long long dvq_unordered_launches(void) { return g_unordered.load(std::memory_order_relaxed); }
 
 int dvq_set_workspace(void* ptr, int64_t bytes) {
     DVQ_REQUIRE((ptr == nullptr) == (bytes == 0) && bytes >= 0, DVQ_EINVAL, "dvq_set_workspace: bad arguments");
@@ -1040,6 +1093,7 @@ int dvq_add_bias_bcast(const void* x, const float* bias, int dtype, int64_t batc
 
 int dvq_sum_batch(const void* x, int dtype, int64_t batch, int64_t inner, float* out, dvq_stream_t stream) {
     DVQ_REQUIRE(x && out && batch > 0 && inner > 0, DVQ_EINVAL, "dvq_sum_batch: bad arguments");
+    const bool det = dvq_deterministic() != 0;
     if (inner % 8 == 0 && batch >= 64) {
         const int64_t inner8 = inner / 8;
         int lg = 2;
@@ -1047,12 +1101,18 @@ int dvq_sum_batch(const void* x, int dtype, int64_t batch, int64_t inner, float*
         const int64_t gx = cdiv64(inner8, 1 << lg);
         int64_t chunks = gx >= 512 ? 1 : cdiv64(512, gx);
         if (chunks > cdiv64(batch, 64)) chunks = cdiv64(batch, 64);
-        const int64_t rpc = cdiv64(batch, chunks);
+        int64_t rpc = cdiv64(batch, chunks);
         chunks = cdiv64(batch, rpc);
         if (gx <= 65535 && chunks <= 65535) {
+            float* part = nullptr;
+            if (chunks > 1 && det) {                       // partials [chunk][inner] + fold, or one chunk: never atomics
+                part = (float*)dvq_det_scratch((hipStream_t)stream, chunks * inner * 4);
+                if (part == nullptr) { chunks = 1; rpc = batch; }
+            } else if (chunks > 1) dvq_note_unordered();
             DVQ_DISPATCH_DTYPE(dtype, T, sum_batch_vec_kernel<T><<<dim3((unsigned)gx, (unsigned)chunks), dim3(256), 0, (hipStream_t)stream>>>(
-                                             (const T*)x, batch, inner8, out, rpc, lg););
+                                             (const T*)x, batch, inner8, out, rpc, lg, part););
             DVQ_CHECK_LAUNCH("sum_batch");
+            if (part != nullptr) return dvq_det_fold_f32(out, part, (int)chunks, inner, inner, (hipStream_t)stream);
             return DVQ_OK;
         }
     }
@@ -1061,11 +1121,17 @@ int dvq_sum_batch(const void* x, int dtype, int64_t batch, int64_t inner, float*
     int64_t chunks = col_blocks >= 1024 ? 1 : cdiv64(1024, col_blocks);
     if (chunks > cdiv64(batch, 16)) chunks = cdiv64(batch, 16);
     if (chunks < 1) chunks = 1;
-    const int64_t rpc = cdiv64(batch, chunks);
+    int64_t rpc = cdiv64(batch, chunks);
     chunks = cdiv64(batch, rpc);
+    float* part = nullptr;
+    if (chunks > 1 && det) {
+        part = (float*)dvq_det_scratch((hipStream_t)stream, chunks * inner * 4);
+        if (part == nullptr) { chunks = 1; rpc = batch; }
+    } else if (chunks > 1) dvq_note_unordered();
     DVQ_DISPATCH_DTYPE(dtype, T, sum_batch_kernel<T><<<dim3((unsigned)(col_blocks < 65535 ? col_blocks : 65535), (unsigned)chunks), dim3(256), 0,
-                                                      (hipStream_t)stream>>>((const T*)x, batch, inner, out, rpc););
+                                                      (hipStream_t)stream>>>((const T*)x, batch, inner, out, rpc, part););
     DVQ_CHECK_LAUNCH("sum_batch");
+    if (part != nullptr) return dvq_det_fold_f32(out, part, (int)chunks, inner, inner, (hipStream_t)stream);
     return DVQ_OK;
 }
 
@@ -1158,8 +1224,17 @@ int dvq_nhwc_pad_to_nchw(const void* in, int dtype, int64_t B, int64_t C, int64_
 int dvq_l1_loss(const float* x, const float* xrec, int64_t n, double* loss_sum, const float* scale_dev, float* g,
                 dvq_stream_t stream) {
     DVQ_REQUIRE(x && xrec && n > 0, DVQ_EINVAL, "dvq_l1_loss: bad arguments");
-    l1_loss_kernel<<<dim3(nblocks(n, 1024)), dim3(256), 0, (hipStream_t)stream>>>(x, xrec, n, loss_sum, scale_dev, g);
+    unsigned nb = nblocks(n, 1024);
+    double* part = nullptr;
+    if (loss_sum != nullptr && nb > 1) {
+        if (dvq_deterministic() != 0) {
+            part = (double*)dvq_det_scratch((hipStream_t)stream, (int64_t)nb * 8);
+            if (part == nullptr) nb = 1;             // no scratch: one workgroup walks the whole tensor
+        } else dvq_note_unordered();
+    }
+    l1_loss_kernel<<<dim3(nb), dim3(256), 0, (hipStream_t)stream>>>(x, xrec, n, loss_sum, scale_dev, g, part);
     DVQ_CHECK_LAUNCH("l1_loss");
+    if (part != nullptr) return dvq_det_fold_f64(loss_sum, part, (int)nb, 1, 1, (hipStream_t)stream);
     return DVQ_OK;
 }
 

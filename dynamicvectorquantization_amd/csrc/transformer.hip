@@ -324,15 +324,25 @@ __global__ __launch_bounds__(256) void embed_scatter_kernel(const int64_t* __res
 // in LDS and accumulates their gradient rows in registers (thread = 8 channels): one atomic per channel and workgroup
 // instead of one per channel and TOKEN (position / segment tables have a few hundred rows hit by 20k tokens: the
 // per-token atomics serialised on them, 0.8 ms per call).
-template <typename T>
+// DET (deterministic mode): the first wave lists the hits of a window in TOKEN order (ballot + prefix count, no LDS counter whose
+// order is arrival order); a workgroup stores its sums at part[split][v][C] for dvq_det_fold_f32 (zeros for a row without hits and for
+// the padding row: the fold reads every slot), or adds them to the row itself when the launch has one split (its only writer).
+template <typename T, bool DET>
 __global__ __launch_bounds__(256) void embed_scatter_rows_kernel(const int64_t* __restrict__ idx, const T* __restrict__ dout, int64_t B,
                                                                  int64_t len, int64_t Ttot, int64_t t0, int C8, int64_t padding_idx,
                                                                  int64_t idx_bstride, float* __restrict__ dtable,
-                                                                 int64_t tok_per_split) {
+                                                                 int64_t tok_per_split, float* __restrict__ part) {
     __shared__ int list[1024];
     __shared__ int cnt;
     const int64_t v = blockIdx.x;
-    if (v == padding_idx) return;
+    if (v == padding_idx) {
+        if (DET && part != nullptr && (int)threadIdx.x < C8) {
+            float* dst = part + (((int64_t)blockIdx.y * gridDim.x + v) * C8 + threadIdx.x) * 8;
+#pragma unroll
+            for (int k = 0; k < 8; ++k) dst[k] = 0.f;
+        }
+        return;
+    }
     const int64_t ntok = B * len;
     const int64_t n0 = (int64_t)blockIdx.y * tok_per_split, n1 = min(ntok, n0 + tok_per_split);
     const int c8 = threadIdx.x;
@@ -340,11 +350,29 @@ __global__ __launch_bounds__(256) void embed_scatter_rows_kernel(const int64_t* 
     float acc[8] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
     bool any = false;
     for (int64_t w0 = n0; w0 < n1; w0 += 1024) {
-        if (threadIdx.x == 0) cnt = 0;
-        __syncthreads();
-        for (int i = threadIdx.x; i < 1024 && w0 + i < n1; i += 256) {
-            const int64_t n = w0 + i, b = n / len, j = n - b * len;
-            if (idx[b * idx_bstride + j] == v) list[atomicAdd(&cnt, 1)] = i;
+        if constexpr (DET) {
+            if (threadIdx.x < 64) {
+                int base = 0;
+                for (int q = 0; q < 16; ++q) {
+                    const int i = q * 64 + (int)threadIdx.x;
+                    bool hit = false;
+                    if (w0 + i < n1) {
+                        const int64_t n = w0 + i, b = n / len, j = n - b * len;
+                        hit = idx[b * idx_bstride + j] == v;
+                    }
+                    const unsigned long long m = __ballot(hit);
+                    if (hit) list[base + __popcll(m & ((1ull << threadIdx.x) - 1ull))] = i;
+                    base += __popcll(m);
+                }
+                if (threadIdx.x == 0) cnt = base;
+            }
+        } else {
+            if (threadIdx.x == 0) cnt = 0;
+            __syncthreads();
+            for (int i = threadIdx.x; i < 1024 && w0 + i < n1; i += 256) {
+                const int64_t n = w0 + i, b = n / len, j = n - b * len;
+                if (idx[b * idx_bstride + j] == v) list[atomicAdd(&cnt, 1)] = i;
+            }
         }
         __syncthreads();
         const int m = cnt;
@@ -360,6 +388,19 @@ __global__ __launch_bounds__(256) void embed_scatter_rows_kernel(const int64_t* 
         }
         __syncthreads();
     }
+    if constexpr (DET) {
+        if (!own) return;
+        if (part != nullptr) {
+            float* dst = part + (((int64_t)blockIdx.y * gridDim.x + v) * C8 + c8) * 8;
+#pragma unroll
+            for (int k = 0; k < 8; ++k) dst[k] = acc[k];
+        } else if (any) {
+            float* dst = dtable + (v * C8 + c8) * 8;
+#pragma unroll
+            for (int k = 0; k < 8; ++k) dst[k] += acc[k];
+        }
+        return;
+    }
     if (own && any) {
         float* dst = dtable + (v * C8 + c8) * 8;
 #pragma unroll
@@ -372,7 +413,9 @@ __global__ __launch_bounds__(256) void embed_scatter_rows_kernel(const int64_t* 
 // dlogits (optional) = (softmax - onehot) * gscale[0]  (0 for ignored rows and for the padding columns >= V)
 // one pair of atomics per WORKGROUP: 2 x 20736 same-address fp32 atomics (one per row) were what a call cost -- 0.35 ms at
 // [20736, 1027] whatever the loads did (rocprofv3 of the stage-2 step, round 4)
-__device__ __forceinline__ void ce_fold(float lsum, float lcnt, float* loss_sum, float* cnt) {
+// part != null (deterministic mode): the workgroup STORES its pair at part[blockIdx.x], part[gridDim.x + blockIdx.x]; dvq_det_fold_f32
+// adds them in workgroup order
+__device__ __forceinline__ void ce_fold(float lsum, float lcnt, float* loss_sum, float* cnt, float* part_out) {
     __shared__ float part[8];
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
     if (lane == 0) {
@@ -382,7 +425,10 @@ __device__ __forceinline__ void ce_fold(float lsum, float lcnt, float* loss_sum,
     __syncthreads();
     if (threadIdx.x == 0) {
         const float c = part[4] + part[5] + part[6] + part[7];
-        if (c > 0.f) {
+        if (part_out != nullptr) {
+            part_out[blockIdx.x] = part[0] + part[1] + part[2] + part[3];
+            part_out[gridDim.x + blockIdx.x] = c;
+        } else if (c > 0.f) {
             atomicAdd(loss_sum, part[0] + part[1] + part[2] + part[3]);
             atomicAdd(cnt, c);
         }
@@ -393,7 +439,8 @@ template <typename T>
 __global__ __launch_bounds__(256) void cross_entropy_kernel(const T* __restrict__ logits, int64_t rows, int V, int ldl,
                                                             const int64_t* __restrict__ target, int64_t ignore_index,
                                                             float* __restrict__ loss_sum, float* __restrict__ cnt,
-                                                            const float* __restrict__ gscale, T* __restrict__ dlogits) {
+                                                            const float* __restrict__ gscale, T* __restrict__ dlogits,
+                                                            float* __restrict__ part_out) {
     const int lane = threadIdx.x & 63;
     float lsum = 0.f, lcnt = 0.f;
     for (int64_t r = (int64_t)blockIdx.x * 4 + (threadIdx.x >> 6); r < rows; r += (int64_t)gridDim.x * 4) {
@@ -421,7 +468,7 @@ __global__ __launch_bounds__(256) void cross_entropy_kernel(const T* __restrict_
             }
         }
     }
-    ce_fold(lsum, lcnt, loss_sum, cnt);
+    ce_fold(lsum, lcnt, loss_sum, cnt, part_out);
 }
 
 // The same with the row held in registers (ldl % 8 == 0, ldl <= 64 * 8 * NV): ONE pass of 16-byte loads per row instead of three
@@ -430,7 +477,8 @@ template <typename T, int NV>
 __global__ __launch_bounds__(256) void cross_entropy_vec_kernel(const T* __restrict__ logits, int64_t rows, int V, int ldl,
                                                                 const int64_t* __restrict__ target, int64_t ignore_index,
                                                                 float* __restrict__ loss_sum, float* __restrict__ cnt,
-                                                                const float* __restrict__ gscale, T* __restrict__ dlogits) {
+                                                                const float* __restrict__ gscale, T* __restrict__ dlogits,
+                                                                float* __restrict__ part_out) {
     const int lane = threadIdx.x & 63;
     const int L8 = ldl >> 3;
     float lsum = 0.f, lcnt = 0.f;
@@ -480,7 +528,7 @@ __global__ __launch_bounds__(256) void cross_entropy_vec_kernel(const T* __restr
             }
         }
     }
-    ce_fold(lsum, lcnt, loss_sum, cnt);
+    ce_fold(lsum, lcnt, loss_sum, cnt, part_out);
 }
 
 // ---- dropout: y = x * keep / (1 - p), keep decided by dvq_hash32 of (seed, element index) (dvq_common.h).  The same call
@@ -573,13 +621,20 @@ int dvq_layernorm_bwd_res_drop(const void* x, const void* dy, const void* dres, 
     if (rpw < 1) rpw = 1;
     const int64_t waves = cdiv64(rows, rpw);
     const int c8 = (int)(C / 8);
-    const dim3 grid((unsigned)cdiv64(waves, 4));
+    dim3 grid((unsigned)cdiv64(waves, 4));
     const size_t lds = (size_t)(4 * 2 * C * sizeof(float));           // one [2 C] row per wave
     float* part = nullptr;
+    const bool det = dvq_deterministic() != 0;
     {
         int64_t ws_bytes = 0;
         void* ws = dvq_workspace_stream((hipStream_t)stream, &ws_bytes);
-        if (ws != nullptr && ws_bytes >= (int64_t)grid.x * 2 * C * (int64_t)sizeof(float) && grid.x > 8) part = (float*)ws;
+        if (ws != nullptr && ws_bytes >= (int64_t)grid.x * 2 * C * (int64_t)sizeof(float) && (grid.x > 8 || (det && grid.x > 1))) part = (float*)ws;
+    }
+    if (det && part == nullptr && grid.x > 1) {          // deterministic mode without scratch: one workgroup, the only writer of dgamma / dbeta
+        rpw = (int)cdiv64(rows, 4);
+        grid.x = 1;
+    } else if (!det && (part != nullptr ? grid.x > 64 : grid.x > 1)) {
+        dvq_note_unordered();                            // fp32 atomics per column from every workgroup, or from every 64-row block of the fold
     }
 #define DVQ_LN_BWD(NVV) \
     DVQ_DISPATCH_DTYPE(dtype, T, if (lds > 48 * 1024) dvq_ensure_dynamic_lds((const void*)ln_bwd_kernel<T, NVV>, (int)lds); \
@@ -588,6 +643,11 @@ int dvq_layernorm_bwd_res_drop(const void* x, const void* dy, const void* dres, 
                                      (T*)dx_drop, p_drop, rm, ra);)
     if (c8 <= 64) { DVQ_LN_BWD(1); } else if (c8 <= 128) { DVQ_LN_BWD(2); } else if (c8 <= 256) { DVQ_LN_BWD(4); } else { DVQ_LN_BWD(8); }
 #undef DVQ_LN_BWD
+    if (part != nullptr && det) {                        // a thread per column walks the workgroups' rows in order
+        DVQ_CHECK_LAUNCH("layernorm_bwd");
+        if (int e = dvq_det_fold_f32(dgamma, part, (int)grid.x, 2 * C, C, (hipStream_t)stream)) return e;
+        return dvq_det_fold_f32(dbeta, part + C, (int)grid.x, 2 * C, C, (hipStream_t)stream);
+    }
     if (part != nullptr)
         ln_bwd_fold_kernel<<<dim3((unsigned)cdiv64(2 * C, 64), (unsigned)cdiv64(grid.x, 64)), dim3(256), 0, (hipStream_t)stream>>>(
             part, (int)grid.x, (int)C, dgamma, dbeta);
@@ -634,17 +694,35 @@ int dvq_embed_scatter_add(const int64_t* idx, int64_t idx_bstride, const void* d
                           int64_t t0, int64_t C, int64_t padding_idx, int64_t V, float* dtable, dvq_stream_t stream) {
     DVQ_REQUIRE(idx && dout && dtable && B > 0 && len > 0 && t0 >= 0 && t0 + len <= Ttot && C > 0 && C % 8 == 0, DVQ_EINVAL,
                 "dvq_embed_scatter_add: bad arguments");
+    const bool det = dvq_deterministic() != 0;
+    DVQ_REQUIRE(!det || (V > 0 && V <= 65535 && C <= 2048), DVQ_ESHAPE,
+                "dvq_embed_scatter_add: deterministic mode needs the table's row count (0 < V <= 65535) and C <= 2048");
     if (V > 0 && V <= 65535 && C <= 2048) {
         const int64_t ntok = B * len;
         int64_t splits = V >= 512 ? 1 : cdiv64(512, V);
         if (splits > cdiv64(ntok, 128)) splits = cdiv64(ntok, 128);
-        const int64_t tps = cdiv64(ntok, splits);
+        int64_t tps = cdiv64(ntok, splits);
         splits = cdiv64(ntok, tps);
-        DVQ_DISPATCH_DTYPE(dtype, T, embed_scatter_rows_kernel<T><<<dim3((unsigned)V, (unsigned)splits), dim3(256), 0, (hipStream_t)stream>>>(
-                                         idx, (const T*)dout, B, len, Ttot, t0, (int)(C / 8), padding_idx, idx_bstride, dtable, tps););
+        if (det) {
+            // token lists in token order; the splits' sums through part[split][V][C] + a fold in split order, or one split
+            float* part = splits > 1 ? (float*)dvq_det_scratch((hipStream_t)stream, splits * V * C * 4) : nullptr;
+            if (part == nullptr) {
+                splits = 1;
+                tps = ntok;
+            }
+            DVQ_DISPATCH_DTYPE(dtype, T, embed_scatter_rows_kernel<T, true><<<dim3((unsigned)V, (unsigned)splits), dim3(256), 0, (hipStream_t)stream>>>(
+                                             idx, (const T*)dout, B, len, Ttot, t0, (int)(C / 8), padding_idx, idx_bstride, dtable, tps, part););
+            DVQ_CHECK_LAUNCH("embed_scatter_add");
+            if (part != nullptr) return dvq_det_fold_f32(dtable, part, (int)splits, V * C, V * C, (hipStream_t)stream);
+            return DVQ_OK;
+        }
+        dvq_note_unordered();          // the token list of a window fills in arrival order; with splits > 1 also fp32 atomics per row
+        DVQ_DISPATCH_DTYPE(dtype, T, embed_scatter_rows_kernel<T, false><<<dim3((unsigned)V, (unsigned)splits), dim3(256), 0, (hipStream_t)stream>>>(
+                                         idx, (const T*)dout, B, len, Ttot, t0, (int)(C / 8), padding_idx, idx_bstride, dtable, tps, nullptr););
         DVQ_CHECK_LAUNCH("embed_scatter_add");
         return DVQ_OK;
     }
+    dvq_note_unordered();              // one fp32 atomic per channel and token
     DVQ_DISPATCH_DTYPE(dtype, T, embed_scatter_kernel<T><<<dim3(nblk(B * len * (C / 8), 256)), dim3(256), 0, (hipStream_t)stream>>>(
                                      idx, (const T*)dout, B, len, Ttot, t0, (int)(C / 8), padding_idx, idx_bstride, dtable););
     DVQ_CHECK_LAUNCH("embed_scatter_add");
@@ -655,22 +733,34 @@ int dvq_cross_entropy(const void* logits, int dtype, int64_t rows, int64_t V, in
                       float* loss_sum, float* count, const float* gscale_dev, void* dlogits, dvq_stream_t stream) {
     DVQ_REQUIRE(logits && target && loss_sum && count && rows > 0 && V > 0 && ldl >= V && (dlogits == nullptr || gscale_dev != nullptr),
                 DVQ_EINVAL, "dvq_cross_entropy: bad arguments");
+    unsigned nb = nblk(rows, 4, 1024);
+    float* part = nullptr;
+    if (nb > 1) {
+        if (dvq_deterministic() != 0) {                    // a (loss, count) pair per workgroup + a fold in workgroup order; no scratch: one workgroup
+            part = (float*)dvq_det_scratch((hipStream_t)stream, (int64_t)nb * 2 * 4);
+            if (part == nullptr) nb = 1;
+        } else dvq_note_unordered();                       // one fp32 atomic pair per workgroup
+    }
     if (ldl % 8 == 0 && ldl <= 64 * 8 * 4) {
         if (ldl <= 64 * 8 * 2) {
-            DVQ_DISPATCH_DTYPE(dtype, T, cross_entropy_vec_kernel<T, 2><<<dim3(nblk(rows, 4, 1024)), dim3(256), 0, (hipStream_t)stream>>>(
+            DVQ_DISPATCH_DTYPE(dtype, T, cross_entropy_vec_kernel<T, 2><<<dim3(nb), dim3(256), 0, (hipStream_t)stream>>>(
                                              (const T*)logits, rows, (int)V, (int)ldl, target, ignore_index, loss_sum, count, gscale_dev,
-                                             (T*)dlogits););
+                                             (T*)dlogits, part););
         } else {
-            DVQ_DISPATCH_DTYPE(dtype, T, cross_entropy_vec_kernel<T, 4><<<dim3(nblk(rows, 4, 1024)), dim3(256), 0, (hipStream_t)stream>>>(
+            DVQ_DISPATCH_DTYPE(dtype, T, cross_entropy_vec_kernel<T, 4><<<dim3(nb), dim3(256), 0, (hipStream_t)stream>>>(
                                              (const T*)logits, rows, (int)V, (int)ldl, target, ignore_index, loss_sum, count, gscale_dev,
-                                             (T*)dlogits););
+                                             (T*)dlogits, part););
         }
     } else {
-        DVQ_DISPATCH_DTYPE(dtype, T, cross_entropy_kernel<T><<<dim3(nblk(rows, 4, 1024)), dim3(256), 0, (hipStream_t)stream>>>(
+        DVQ_DISPATCH_DTYPE(dtype, T, cross_entropy_kernel<T><<<dim3(nb), dim3(256), 0, (hipStream_t)stream>>>(
                                          (const T*)logits, rows, (int)V, (int)ldl, target, ignore_index, loss_sum, count, gscale_dev,
-                                         (T*)dlogits););
+                                         (T*)dlogits, part););
     }
     DVQ_CHECK_LAUNCH("cross_entropy");
+    if (part != nullptr) {
+        if (int e = dvq_det_fold_f32(loss_sum, part, (int)nb, 1, 1, (hipStream_t)stream)) return e;
+        return dvq_det_fold_f32(count, part + nb, (int)nb, 1, 1, (hipStream_t)stream);
+    }
     return DVQ_OK;
 }
 

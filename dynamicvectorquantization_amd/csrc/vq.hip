@@ -805,7 +805,7 @@ template <typename T>
 __global__ __launch_bounds__(256) void vq_gather_loss_kernel(const T* __restrict__ x, const float* __restrict__ cb,
                                                              const int64_t* __restrict__ idx,
                                                              const float* __restrict__ mask, int64_t N, int64_t D,
-                                                             T* __restrict__ xq, double* loss_sum) {
+                                                             T* __restrict__ xq, double* loss_sum, double* __restrict__ part_out) {
     __shared__ double part[4];
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
     double acc = 0.0;
@@ -824,7 +824,10 @@ __global__ __launch_bounds__(256) void vq_gather_loss_kernel(const T* __restrict
     }
     if (lane == 0) part[wave] = acc;
     __syncthreads();
-    if (threadIdx.x == 0) atomicAdd(loss_sum, part[0] + part[1] + part[2] + part[3]);
+    if (threadIdx.x != 0) return;
+    const double t = part[0] + part[1] + part[2] + part[3];
+    if (part_out != nullptr) part_out[blockIdx.x] = t;           // deterministic mode: dvq_det_fold_f64 adds the workgroups in order
+    else atomicAdd(loss_sum, t);
 }
 
 template <typename T>
@@ -870,14 +873,26 @@ constexpr int EMA_SLICE = 1024;   // rows per (code, slice) work item
 // slice) wave walked several hundred rows one round trip after the other and set the kernel's duration (413 us per launch in the
 // headline step).  The matching rows now form a compact list (slice order: same rows, same summation order as before) that is walked
 // four rows per trip with all 4 NJ loads in flight.  NJ = ceil(D / 64) rounded up to a power of two (launcher).
-template <typename T, int NJ>
+// ALL = true (deterministic mode, grid.y = 1): ONE wave per code walks every slice in order and finishes with a plain store -- the
+// sum of a code's rows no longer depends on the order in which its slices' atomics arrive.
+template <typename T, int NJ, bool ALL>
 __global__ __launch_bounds__(64) void vq_ema_stats_kernel(const T* __restrict__ x, const int64_t* __restrict__ idx,
                                                           int64_t N, int64_t K, int64_t D,
                                                           float* __restrict__ stats) {
     const int64_t k = blockIdx.x;
-    const int64_t nbeg = (int64_t)blockIdx.y * EMA_SLICE, nend = min(N, nbeg + EMA_SLICE);
     const int lane = threadIdx.x;
     constexpr int NCH = EMA_SLICE / 64;
+    __shared__ unsigned short rows_l[EMA_SLICE];
+    float acc[NJ];
+#pragma unroll
+    for (int j = 0; j < NJ; ++j) acc[j] = 0.f;
+    int dj[NJ];                                  // this lane's columns, clamped into the row (masked when past D)
+#pragma unroll
+    for (int j = 0; j < NJ; ++j) dj[j] = (int)min((int64_t)(lane + 64 * j), D - 1);
+    int total = 0;
+    const int64_t sl_lo = ALL ? 0 : (int64_t)blockIdx.y, sl_hi = ALL ? (N + EMA_SLICE - 1) / EMA_SLICE : (int64_t)blockIdx.y + 1;
+    for (int64_t sl = sl_lo; sl < sl_hi; ++sl) {
+    const int64_t nbeg = sl * EMA_SLICE, nend = min(N, nbeg + EMA_SLICE);
     int64_t iv[NCH];
 #pragma unroll
     for (int q = 0; q < NCH; ++q) iv[q] = idx[min(nbeg + q * 64 + lane, N - 1)];       // 16 independent loads, one wait
@@ -888,8 +903,9 @@ __global__ __launch_bounds__(64) void vq_ema_stats_kernel(const T* __restrict__ 
         hit[q] = __ballot(nbeg + q * 64 + lane < nend && iv[q] == k);
         count += __popcll(hit[q]);
     }
-    if (count == 0) return;
-    __shared__ unsigned short rows_l[EMA_SLICE];
+    if (count == 0) continue;
+    total += count;
+    __syncthreads();                             // (ALL: the previous slice's list has been read)
     {
         int base = 0;
 #pragma unroll
@@ -900,12 +916,6 @@ __global__ __launch_bounds__(64) void vq_ema_stats_kernel(const T* __restrict__ 
         }
     }
     __syncthreads();
-    float acc[NJ];
-#pragma unroll
-    for (int j = 0; j < NJ; ++j) acc[j] = 0.f;
-    int dj[NJ];                                  // this lane's columns, clamped into the row (masked when past D)
-#pragma unroll
-    for (int j = 0; j < NJ; ++j) dj[j] = (int)min((int64_t)(lane + 64 * j), D - 1);
     for (int i = 0; i < count; i += 4) {
         float v[4][NJ];
 #pragma unroll
@@ -919,12 +929,20 @@ __global__ __launch_bounds__(64) void vq_ema_stats_kernel(const T* __restrict__ 
 #pragma unroll
             for (int j = 0; j < NJ; ++j) acc[j] += (i + u < count && lane + 64 * j < D) ? v[u][j] : 0.f;
     }
+    }
+    if (total == 0) return;
 #pragma unroll
     for (int j = 0; j < NJ; ++j) {
         const int64_t d = lane + 64 * j;
-        if (d < D) atomicAdd(stats + k * (D + 1) + d, acc[j]);
+        if (d < D) {
+            if constexpr (ALL) stats[k * (D + 1) + d] = acc[j];           // (zeroed by the launcher; this wave is the row's only writer)
+            else atomicAdd(stats + k * (D + 1) + d, acc[j]);
+        }
     }
-    if (lane == 0) atomicAdd(stats + k * (D + 1) + D, (float)count);
+    if (lane == 0) {
+        if constexpr (ALL) stats[k * (D + 1) + D] = (float)total;
+        else atomicAdd(stats + k * (D + 1) + D, (float)total);
+    }
 }
 
 __global__ __launch_bounds__(256) void vq_ema_update_kernel(const float* __restrict__ stats,
@@ -1125,9 +1143,17 @@ int dvq_vq_gather_loss(const void* x, int dtype, const float* codebook, const in
     DVQ_REQUIRE(x && codebook && idx && x_q && loss_sum, DVQ_EINVAL, "dvq_vq_gather_loss: null pointer");
     hipStream_t s = (hipStream_t)stream;
     unsigned grid = (unsigned)(cdiv64(N, 4) < 4096 ? cdiv64(N, 4) : 4096);
+    double* part = nullptr;
+    if (grid > 1) {
+        if (dvq_deterministic() != 0) {                    // a partial per workgroup + a fold in order; no scratch: one workgroup
+            part = (double*)dvq_det_scratch(s, (int64_t)grid * 8);
+            if (part == nullptr) grid = 1;
+        } else dvq_note_unordered();                       // one fp64 atomic per workgroup
+    }
     DVQ_DISPATCH_DTYPE(dtype, T, vq_gather_loss_kernel<T><<<dim3(grid), dim3(256), 0, s>>>(
-                                     (const T*)x, codebook, idx, mask, N, D, (T*)x_q, loss_sum););
+                                     (const T*)x, codebook, idx, mask, N, D, (T*)x_q, loss_sum, part););
     DVQ_CHECK_LAUNCH("vq_gather_loss");
+    if (part != nullptr) return dvq_det_fold_f64(loss_sum, part, (int)grid, 1, 1, s);
     return DVQ_OK;
 }
 
@@ -1166,7 +1192,11 @@ int dvq_vq_ema_stats(const void* x, int dtype, const int64_t* idx, int64_t N, in
     }
     dim3 grid((unsigned)K, (unsigned)cdiv64(N, EMA_SLICE));
     DVQ_REQUIRE(grid.y <= 65535, DVQ_ESHAPE, "dvq_vq_ema_stats: N too large");
-#define DVQ_EMA_STATS(NJV) DVQ_DISPATCH_DTYPE(dtype, T, vq_ema_stats_kernel<T, NJV><<<grid, dim3(64), 0, s>>>((const T*)x, idx, N, K, D, stats);)
+    const bool all = dvq_deterministic() != 0 && grid.y > 1;
+    if (all) grid.y = 1;
+    else if (grid.y > 1) dvq_note_unordered();          // one fp32 atomic per dimension from every slice that holds rows of the code
+#define DVQ_EMA_STATS(NJV) DVQ_DISPATCH_DTYPE(dtype, T, if (all) vq_ema_stats_kernel<T, NJV, true><<<grid, dim3(64), 0, s>>>((const T*)x, idx, N, K, D, stats); \
+                                                     else vq_ema_stats_kernel<T, NJV, false><<<grid, dim3(64), 0, s>>>((const T*)x, idx, N, K, D, stats);)
     if (D <= 64) { DVQ_EMA_STATS(1); } else if (D <= 128) { DVQ_EMA_STATS(2); } else if (D <= 256) { DVQ_EMA_STATS(4); }
     else if (D <= 512) { DVQ_EMA_STATS(8); } else { DVQ_EMA_STATS(16); }
 #undef DVQ_EMA_STATS

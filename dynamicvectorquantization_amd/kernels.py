@@ -60,7 +60,16 @@ def is_ohwi(t) -> bool:
     raise _lib.DvqError(f"unsupported weight strides {t.stride()} for shape {tuple(t.shape)}")
 
 
+_det = [None]         # the library's deterministic flag as last seen here (None: not asked yet; DVQ_DETERMINISTIC=1 sets it at load)
+
+
 def _s():
+    if _det[0] is not False:
+        # deterministic mode: the ordered forms keep their per-split partials in the registered workspace
+        if _det[0] is None:
+            _det[0] = bool(lib().dvq_deterministic())
+        if _det[0]:
+            ensure_workspace(torch.device("cuda", torch.cuda.current_device()))
     return C.c_void_p(torch.cuda.current_stream().cuda_stream)
 
 
@@ -603,12 +612,21 @@ def conv2d_wgrad_oihw(d: ConvDesc, x, dy, cin_real, cout_real, grad_oihw, db=Non
 
 
 def set_deterministic(on: bool):
-    """opt-in: weight-gradient split reductions run unsplit or through partials + a fold kernel (bit-reproducible gradients)"""
+    """opt-in: every floating-point reduction of a training step runs in a fixed order -- per-split partials + a fold, or one owner per
+    output element -- never through float atomics with several writers (bit-reproducible steps; docs/design/21-reproducible-training.md)"""
     check(lib().dvq_set_deterministic(int(bool(on))), "dvq_set_deterministic")
+    _det[0] = bool(on)
 
 
 def deterministic() -> bool:
-    return bool(lib().dvq_deterministic())
+    _det[0] = bool(lib().dvq_deterministic())
+    return _det[0]
+
+
+def unordered_launches() -> int:
+    """process-wide count of launches whose floating-point result depends on arrival order (float atomics with several writers per
+    address); it does not move across calls made in deterministic mode"""
+    return int(lib().dvq_unordered_launches())
 
 
 def pack_weights_multi(table_dev, n_entries, total_work):

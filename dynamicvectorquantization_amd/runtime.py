@@ -224,6 +224,17 @@ def next_dropout_seed() -> int:
     return (torch.initial_seed() * 1000003 + _seed_counter[0]) & 0x7FFFFFFFFFFFFFFF
 
 
+def reseed_draws(model=None):
+    """restart the host-side draws of a run (Trainer(deterministic=True)): the dropout-seed counter goes back to zero and the
+    device-resident {seed, counter} of every codebook's restart-row sampler is rebuilt from torch's seed at its next use -- two runs
+    from the same torch.manual_seed in one process then draw the same sequence"""
+    _seed_counter[0] = 0
+    if model is not None:
+        for mod in model.modules():
+            if getattr(mod, "_rng_state", None) is not None:
+                mod._rng_state = None
+
+
 def step_replay_mode() -> str:
     """how a recorded segment is replayed: "list" = csrc/cmdlist.hip re-issues the captured launches on the current + side stream
     (the device sees an eager step's queues).  A segment the list cannot re-issue falls back to hipGraphLaunch on its own."""

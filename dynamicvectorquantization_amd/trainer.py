@@ -449,8 +449,16 @@ class Trainer:
     static input buffers.  `DVQ_STEP_GRAPH=0` (or use_graph=False) keeps every step eager."""
 
     def __init__(self, model, max_steps, log_every=0, use_graph=None, graph_after=3, gradient_clip_val=0.0, skip_nonfinite=False,
-                 ema_decay=0.0, ema_warmup=True):
+                 ema_decay=0.0, ema_warmup=True, deterministic=False):
         self.model, self.max_steps, self.log_every = model, max_steps, log_every
+        # Lightning's Trainer(deterministic=True) (docs/design/21-reproducible-training.md): every floating-point reduction of the step in
+        # a fixed order (kernels.set_deterministic, before the first launch) and every host-side draw of the step -- the dropout seeds
+        # of stage 2, the restart rows of the codebooks -- a function of torch's seed and the number of draws made by THIS trainer, not
+        # of what ran in the process before it.  Off (the default): nothing changes
+        self.deterministic = bool(deterministic)
+        if self.deterministic:
+            K.set_deterministic(True)
+            rt.reseed_draws(model)
         self.opts, self.scheds = model.configure_optimizers()
         self.buckets = [GradBuckets(o.flatten()) for o in self.opts]
         # Lightning's Trainer(gradient_clip_val=...): global-norm clipping once per optimizer; skip_nonfinite: a step whose gradient
@@ -555,6 +563,8 @@ class Trainer:
         world = dist.get_world_size() if dist.is_available() and dist.is_initialized() else 1
         guard = (self.gradient_clip_val, self.skip_nonfinite)           # launch arguments of the recorded norm kernels
         sig = (tuple(items), bool(m.training), rt.compute_dtype(), rt.impl(), rt.fuse_gn_prologue(), world, extra, guard)
+        if K.deterministic():                      # the ordered kernels are other launches: a recording made in one mode is not replayed in the other
+            sig = sig + (("deterministic",),)
         # whether the EMA launch is part of the step; the decay is device data and not part of the signature
         return sig + (("ema",) if self.ema_enabled else ())
 

@@ -46,7 +46,8 @@ const char* dvq_last_error(void);
  * written in csrc ("conv3x3_halo_kernel", "conv_nt_pipe_kernel", ...; no template arguments, no fold / reduce / transpose helpers), noted
  * at the dispatch branch that launches it.  "" when nothing was noted (those entry points clear it first).  For timing labels. */
 const char* dvq_last_kernel(void);
-int dvq_version(void);     /* 117: DVQ_IMPL_* names for the impl codes; one entry per convolution / GEMM pass (dvq_conv2d_fwd, _dgrad, _wgrad, dvq_gemm_tn
+int dvq_version(void);     /* 118: dvq_unordered_launches; dvq_set_deterministic orders every floating-point reduction of a training step;
+                            * 117: DVQ_IMPL_* names for the impl codes; one entry per convolution / GEMM pass (dvq_conv2d_fwd, _dgrad, _wgrad, dvq_gemm_tn
                             * take the arguments of their former _ex / _act / _mask / _oihw / _colsum variants; dvq_gemm_nt_res is gone);
                             * 116: dvq_grain_overlay, dvq_grain_lines, dvq_image_grid_u8 (+ dvq_image_grid_shape, dvq_imagelog_workspace_bytes):
                             * training-time image logging;
@@ -67,13 +68,22 @@ int dvq_version(void);     /* 117: DVQ_IMPL_* names for the impl codes; one entr
                             * no vendor-library entry points; + dvq_decode_stack, dvq_gemm_tn_colsum) */
 /* 0 if the current HIP device is gfx950, DVQ_EARCH otherwise */
 int dvq_check_device(void);
-/* Deterministic summation (opt-in; default: environment DVQ_DETERMINISTIC=1, else off).  On: every split-reduction family of weight
- * gradients -- the patch-stage and transpose-read convolution weight gradients, the plain TN products -- runs UNSPLIT or through
- * workspace partials + a fold kernel, never through fp32 atomics from several workgroups: the gradients of a step are then
- * bit-reproducible run to run (the halo weight gradient, the GroupNorm / LayerNorm backward reductions already fold partials in a
- * fixed order).  Costs occupancy on the small-map shapes.  Scalar loss sums and the VQ-EMA statistics still use atomics. */
+/* Deterministic summation (opt-in; default: environment DVQ_DETERMINISTIC=1, else off).  On: no kernel of a training step lets a
+ * floating-point result depend on arrival order, neither across workgroups in global memory nor across waves in LDS.  Every
+ * reduction takes one of two forms: per-split partials in the registered workspace (dvq_set_workspace) + a fold in split order with one
+ * owner per output element, or one owner that walks its inputs in index order.  Covered: the weight gradients of every TN / halo
+ * family for bf16, fp32 and fp32x3 operands with their column sums (bias gradients), dvq_sum_batch, the GroupNorm / BatchNorm
+ * statistics and backward sums, the statistics epilogue of the halo convolution, the LayerNorm backward, the embedding gradient, the
+ * cross-entropy / L1 / commitment / LPIPS loss sums, the VQ-EMA statistics and the trained-codebook gradient.  Without a workspace
+ * (or with one too small) a call launches UNSPLIT or returns DVQ_EWORKSPACE / DVQ_ESHAPE -- never the atomic form.  Integer atomics
+ * (histograms, counters, maxima on float bits) are exact and stay.  Scope: one process, one GPU, one binary; slower
+ * (docs/design/21-reproducible-training.md has the table).  Off: nothing changes. */
 int dvq_set_deterministic(int on);
 int dvq_deterministic(void);
+/* Process-wide count of launches that took a path whose floating-point result depends on arrival order (float atomics with several
+ * writers per address), bumped at the dispatch branch that selects such a kernel or epilogue.  It does not move across a call made in
+ * deterministic mode; that it DOES move with the mode off shows a shape really has several writers per address. */
+long long dvq_unordered_launches(void);
 /* fp32 operands on the bf16 matrix pipe (opt-in; default: environment DVQ_FP32_SPLIT=1, else off): the fp32 instantiations of the
  * convolution / GEMM kernels split every operand element into two bf16 planes (x = hi + lo) in registers and run hi.hi + hi.lo + lo.hi as
  * three v_mfma_f32_32x32x16_bf16 passes with fp32 accumulation instead of v_mfma_f32_32x32x2_f32: ~2^-17 relative error per product

@@ -15,6 +15,9 @@ path, without pytorch_lightning / OmegaConf:
   a step whose gradient holds an Inf / NaN leaves parameters and Adam moments untouched (docs/design/19-gradient-clipping.md).
 * `--ema_decay D` (0: off): an exponential moving average of the weights of optimizer 0, used for validation and stored under the
   checkpoint's "ema" key; `--ema_no_warmup` drops the (1 + n) / (10 + n) warm-up of the decay (docs/design/20-weight-ema.md).
+* `--deterministic` (Lightning's Trainer flag; off by default): every floating-point sum of the step in a fixed order and every host-side
+  draw from the run's seed -- two runs with the same seed on one GPU walk the same trajectory bit for bit
+  (docs/design/21-reproducible-training.md).  Stored in the run's saved config (`lightning.trainer.deterministic`), so `-r` keeps it.
 Unsupported Trainer flags are accepted and ignored with a warning, like unknown Lightning flags would be.
 """
 from __future__ import annotations
@@ -73,6 +76,9 @@ def get_parser():
                         "value given on this command line applies")
     p.add_argument("--ema_no_warmup", action="store_true",
                    help="use --ema_decay from the first update on, without the min(decay, (1 + n) / (10 + n)) warm-up")
+    p.add_argument("--deterministic", action="store_true",
+                   help="bit-reproducible training (Lightning's Trainer flag): ordered sums in every kernel of the step, host-side draws "
+                        "seeded by --seed; slower.  One process on one GPU: with several ranks the collective's reduction order also counts")
     return p
 
 
@@ -132,6 +138,10 @@ def run(rank, world, opt, unknown):
     if not opt.base:
         raise SystemExit("-b/--base <config.yaml> is required (or -r <logdir> holding configs/)")
     config = cfg.merge(*[cfg.load_yaml(b) for b in opt.base], cfg.from_dotlist(dot))
+    # --deterministic lives in the saved config like the reference's lightning.trainer section: a resumed run keeps the mode it began in
+    if opt.deterministic:
+        config = cfg.merge(config, cfg.from_dotlist(["lightning.trainer.deterministic=true"]))
+    deterministic = bool(config.get("lightning", {}).get("trainer", {}).get("deterministic", False))
     if logdir is None:
         now = datetime.datetime.now().strftime("%Y-%m-%dT%H-%M-%S")
         logdir = os.path.join(opt.logdir, now + ("_" + opt.name if opt.name else "") + opt.postfix)
@@ -209,7 +219,8 @@ def run(rank, world, opt, unknown):
 
     total = model.training_steps if opt.max_steps < 0 else min(opt.max_steps, model.training_steps)
     trainer = Trainer(model, max_steps=total, log_every=10 if rank == 0 else 0, gradient_clip_val=opt.gradient_clip_val,
-                      skip_nonfinite=opt.skip_nonfinite_grads, ema_decay=opt.ema_decay, ema_warmup=not opt.ema_no_warmup)
+                      skip_nonfinite=opt.skip_nonfinite_grads, ema_decay=opt.ema_decay, ema_warmup=not opt.ema_no_warmup,
+                      deterministic=deterministic)
     pool = [torch.from_numpy(synth.half_flat_images(bs, size, seed=opt.seed + 977 * rank + i)).to(dev) for i in range(4)]
 
     image_key = getattr(model, "image_key", None) or getattr(model, "first_stage_key", "image")
