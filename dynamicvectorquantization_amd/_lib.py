@@ -40,6 +40,16 @@ class PackEntry(C.Structure):
                 ("Cout_p", i64), ("begin", i64), ("dtype", i64)]
 
 
+class ScalarRecord(C.Structure):
+    """dvq_scalar_record of include/dvq_hip.h (dvq_scalar_push): 64 (address | fp64 bits, type code) pairs, passed by value"""
+    _fields_ = [("addr", C.c_uint64 * 64), ("code", C.c_uint8 * 64)]
+
+
+# DVQ_SCALAR_* of include/dvq_hip.h: element types of dvq_scalar_push and dvq_codebook_health
+SCALAR_F32, SCALAR_BF16, SCALAR_F64, SCALAR_I32, SCALAR_I64, SCALAR_IMM, SCALAR_SKIP = range(7)
+SCALAR_PUSH_MAX, SCALAR_COLUMNS_MAX = 64, 256
+
+
 # name -> (restype, argtypes); mirrors include/dvq_hip.h one to one
 SIGNATURES = {
     "dvq_last_error": (C.c_char_p, []),
@@ -195,6 +205,9 @@ SIGNATURES = {
     "dvq_grain_lines": (i32, [vp, vp, i32, i64, i64, i64, i64, i64, vp]),
     "dvq_image_grid_shape": (i32, [i64, i64, i64, i64, i64, C.POINTER(i64), C.POINTER(i64)]),
     "dvq_image_grid_u8": (i32, [vp, i64, i64, i64, i64, i64, i64, i32, vp, sz, vp, sz, vp]),
+    "dvq_scalar_push_state_bytes": (sz, [i64]),
+    "dvq_scalar_push": (i32, [C.POINTER(ScalarRecord), i32, i32, i32, vp, vp]),
+    "dvq_codebook_health": (i32, [vp, i32, i64, i64, vp, vp, vp, vp]),
 }
 
 

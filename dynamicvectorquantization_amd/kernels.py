@@ -1246,6 +1246,66 @@ def set_f32x8(dst, values):
     check(lib().dvq_set_f32x8(_p(dst), *vals, _s()), "dvq_set_f32x8")
 
 
+_SCALAR_CODE = {torch.float32: _lib.SCALAR_F32, torch.bfloat16: _lib.SCALAR_BF16, torch.float64: _lib.SCALAR_F64,
+                torch.int32: _lib.SCALAR_I32, torch.int64: _lib.SCALAR_I64}
+
+
+def scalar_push_state(columns, device):
+    """zeroed state block of scalar_push for `columns` columns (include/dvq_hip.h: sum fp64 | cnt int64 | bad int64 | last fp32)"""
+    nbytes = int(lib().dvq_scalar_push_state_bytes(int(columns)))
+    if nbytes == 0:
+        raise _lib.DvqError(f"scalar_push: {columns} columns, 1 .. {_lib.SCALAR_COLUMNS_MAX} supported")
+    return torch.zeros(nbytes // 4, dtype=torch.float32, device=device)
+
+
+def scalar_push_views(state, columns):
+    """(sum fp64, cnt int64, bad int64, last fp32) views of a state block, or of a host copy of one"""
+    c = int(columns)
+    return (state[:2 * c].view(torch.float64), state[2 * c:4 * c].view(torch.int64), state[4 * c:6 * c].view(torch.int64),
+            state[6 * c:7 * c])
+
+
+def scalar_push(values, state, columns, col0=0):
+    """gather `values` -- one-element device tensors (fp32 / bf16 / fp64 / int32 / int64), Python numbers, or None for a column
+    that has no value this time -- into columns col0 .. of `state`: last value, fp64 running sum and count of the finite ones, count of the others.  The addresses travel in the launch
+    arguments, 64 per launch: no device pointer table, no copy; a recorded step replays with the addresses it was recorded with, so
+    the tensors must stay alive (the step graph's pool keeps a captured step's)."""
+    n = len(values)
+    if col0 < 0 or col0 + n > int(columns):           # the library refuses the launch that crosses the end; refuse the whole call before any
+        raise _lib.DvqError(f"scalar_push: columns {col0} .. {col0 + n - 1} outside a state block of {columns}")
+    for lo in range(0, n, _lib.SCALAR_PUSH_MAX):
+        part = values[lo:lo + _lib.SCALAR_PUSH_MAX]
+        rec = _lib.ScalarRecord()
+        if all(v is None for v in part):
+            continue
+        for i, v in enumerate(part):
+            if v is None:
+                rec.code[i] = _lib.SCALAR_SKIP
+            elif torch.is_tensor(v):
+                if v.numel() != 1 or v.dtype not in _SCALAR_CODE:
+                    raise TypeError(f"scalar_push takes one-element fp32 / bf16 / fp64 / int32 / int64 tensors, got {tuple(v.shape)} {v.dtype}")
+                if not v.is_cuda:
+                    raise _lib.DvqError("libdvq_hip kernels need device tensors (no CPU fallback)")
+                rec.addr[i], rec.code[i] = v.data_ptr(), _SCALAR_CODE[v.dtype]
+            else:
+                rec.addr[i], rec.code[i] = C.c_uint64.from_buffer_copy(C.c_double(float(v))).value, _lib.SCALAR_IMM
+        check(lib().dvq_scalar_push(C.byref(rec), len(part), col0 + lo, int(columns), _p(state), _s()), "dvq_scalar_push")
+    return state
+
+
+def codebook_health(counts, k, stride, out3, total=None, out3_f64=None):
+    """out3 (fp32 [3]) <- perplexity, active codes, tokens of the per-code counts counts[j * stride], j < k (fp32 or int64; the EMA
+    quantiser's are column D of its [K, D + 1] statistics); total (fp64 [k]) += counts.  One workgroup, fp64, fixed order."""
+    code = _SCALAR_CODE.get(counts.dtype)
+    assert code in (_lib.SCALAR_F32, _lib.SCALAR_I64), f"counts are fp32 or int64, got {counts.dtype}"
+    assert out3.dtype == torch.float32 and out3.numel() >= 3 and (total is None or (total.dtype == torch.float64 and total.numel() >= k))
+    assert out3_f64 is None or (out3_f64.dtype == torch.float64 and out3_f64.numel() >= 3)
+    assert counts.is_cuda and counts.numel() > 0
+    # the counts may be a strided column of a larger buffer: the caller vouches that element j * stride past data_ptr() exists
+    check(lib().dvq_codebook_health(_praw(counts), code, int(k), int(stride), _p(out3), _p(out3_f64), _p(total), _s()), "dvq_codebook_health")
+    return out3
+
+
 def sample_rows(k, n, state):
     """k distinct pseudo-random indices in [0, n) (device-resident RNG state uint64-as-int64 [2]: replayable in a hipGraph)"""
     out = torch.empty(k, dtype=torch.int64, device=state.device)

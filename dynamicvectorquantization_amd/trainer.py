@@ -449,8 +449,11 @@ class Trainer:
     static input buffers.  `DVQ_STEP_GRAPH=0` (or use_graph=False) keeps every step eager."""
 
     def __init__(self, model, max_steps, log_every=0, use_graph=None, graph_after=3, gradient_clip_val=0.0, skip_nonfinite=False,
-                 ema_decay=0.0, ema_warmup=True, deterministic=False):
+                 ema_decay=0.0, ema_warmup=True, deterministic=False, metrics_logger=None):
         self.model, self.max_steps, self.log_every = model, max_steps, log_every
+        # scalar logs (metrics.MetricsLogger, docs/design/22-metrics-logging.md): the model's logged scalars gathered on the device at the
+        # end of every step, rows written every log_every_n_steps steps and at epoch ends.  None (the default): no launch, no file
+        self.metrics_logger = metrics_logger
         # Lightning's Trainer(deterministic=True) (docs/design/21-reproducible-training.md): every floating-point reduction of the step in
         # a fixed order (kernels.set_deterministic, before the first launch) and every host-side draw of the step -- the dropout seeds
         # of stage 2, the restart rows of the codebooks -- a function of torch's seed and the number of draws made by THIS trainer, not
@@ -461,6 +464,8 @@ class Trainer:
             rt.reseed_draws(model)
         self.opts, self.scheds = model.configure_optimizers()
         self.buckets = [GradBuckets(o.flatten()) for o in self.opts]
+        if metrics_logger is not None:         # its device state is allocated here, never inside a step
+            metrics_logger.attach(model, self.buckets[0].fp.flat_g.device)
         # Lightning's Trainer(gradient_clip_val=...): global-norm clipping once per optimizer; skip_nonfinite: a step whose gradient
         # holds an Inf / NaN changes neither parameters nor Adam moments (HipAdam.set_grad_guard).  Both off (the default): no extra launch, dvq_adamw_dev as ever
         self.gradient_clip_val, self.skip_nonfinite = float(gradient_clip_val), bool(skip_nonfinite)
@@ -492,7 +497,13 @@ class Trainer:
     def train_step(self, batch, batch_idx):
         if self._in_ema_scope:
             raise RuntimeError("train_step inside ema_scope(): the parameters hold the averaged weights, a step would train those")
-        out = self._train_step(batch, batch_idx)
+        lg = self.metrics_logger
+        if lg is None:
+            out = self._train_step(batch, batch_idx)
+        else:
+            lrs = [o.param_groups[0]["lr"] for o in self.opts]       # of the step about to run: the schedulers advance inside it
+            out = self._train_step(batch, batch_idx)
+            lg.after_step(self, int(self.model.global_step) - 1, batch, lrs)
         if self.check_every and (int(self.model.global_step) % self.check_every) == 0 and not replicas_equal(self.model):
             raise RuntimeError(f"data-parallel replicas diverged at global step {self.model.global_step}")
         return out
@@ -524,6 +535,9 @@ class Trainer:
         """the capturable part: every launch of the two-optimizer step (collectives are graph breaks)"""
         m = self.model
         losses = []
+        lg = self.metrics_logger
+        if lg is not None:                     # collect what THIS step logs apart from what earlier steps left in the shim's dict
+            logged_before, m._logged = getattr(m, "_logged", {}), {}
         K.arena_reset(self.buckets[0].fp.flat_g.device)
         # single-threaded autograd: the backward's launches come from this thread (one capture thread, no thread hops)
         with torch.autograd.set_multithreading_enabled(False):
@@ -539,6 +553,9 @@ class Trainer:
                 opt.step()
                 self.scheds[oi]["scheduler"].step()
                 losses.append(loss.detach())
+            if lg is not None:                 # the last launches of the step, recorded with it: no host read, no copy node
+                lg.push(m, m._logged)
+                m._logged = {**logged_before, **m._logged}
         m.global_step += 1
         return losses
 
@@ -566,7 +583,8 @@ class Trainer:
         if K.deterministic():                      # the ordered kernels are other launches: a recording made in one mode is not replayed in the other
             sig = sig + (("deterministic",),)
         # whether the EMA launch is part of the step; the decay is device data and not part of the signature
-        return sig + (("ema",) if self.ema_enabled else ())
+        sig = sig + (("ema",) if self.ema_enabled else ())
+        return sig + (("metrics",) if self.metrics_logger is not None else ())        # likewise the scalar push
 
     def _py_state(self):
         return ([o._fstate["step"] for o in self.opts], [s["scheduler"].state_dict() for s in self.scheds],
@@ -610,6 +628,8 @@ class Trainer:
             # the step's log tensors now live in the graph's pool and are refreshed by every replay
             self.model._logged = {**logged, **self.model._logged}
         self._graph = {"sg": sg, "sig": sig, "static": static, "losses": losses}
+        if self.metrics_logger is not None:
+            self._graph["metric_keys"] = self.metrics_logger.last_keys       # the keys the recorded push carries
         return True
 
     def _replay(self, batch):
@@ -633,6 +653,8 @@ class Trainer:
         rt.bump_codebook_epoch()
         self.model.global_step += 1
         self.graph_replays += 1
+        if self.metrics_logger is not None:
+            self.metrics_logger.last_keys = g["metric_keys"]
         return g["losses"]
 
     def drop_graph(self):
@@ -889,7 +911,9 @@ class Trainer:
         `epoch=<e>-<monitor>=<value>.ckpt` -- pytorch_lightning.callbacks.ModelCheckpoint(monitor, save_top_k, save_last=True, mode="min")
         of the reference's train.py:152-183.
         `image_logger` (imagelog.ImageLogger; None = no pictures, the default): offered every batch after its train step and every
-        validation batch; flushed before fit returns, also when a step raises"""
+        validation batch; flushed before fit returns, also when a step raises.
+        With a `metrics_logger` (constructor) the validation means are written as `<key>_epoch` rows, a partial last epoch gets its
+        epoch row and the log files are closed before fit returns"""
         self.model.train()
         best = []                                     # (value, path), ascending
         monitor = getattr(self.model, "monitor", None)
@@ -911,6 +935,8 @@ class Trainer:
         def run_validation(step):
             metrics = self.validate(val_fn(), image_logger=image_logger if is_rank0 else None)
             self.last_val_metrics = metrics
+            if self.metrics_logger is not None and is_rank0:
+                self.metrics_logger.log_validation(metrics, step // max(1, int(getattr(self.model, "steps_per_epoch", 1) or 1)), step)
             if is_rank0 and metrics:
                 print(f"validation @ step {step + 1}{' (EMA weights)' if self.ema_enabled else ''}: " + " ".join(f"{k}={v:.5f}" for k, v in metrics.items()), flush=True)
             if not (ckpt_path and is_rank0 and save_top_k and monitor and monitor in metrics):
@@ -947,8 +973,12 @@ class Trainer:
                     self.save_checkpoint(ckpt_path)
                 if val_fn is not None and val_every and ((step + 1) % val_every == 0 or step + 1 == self.max_steps):
                     run_validation(step)
+            if self.metrics_logger is not None:
+                self.metrics_logger.finish(self)          # the epoch row of a partial last epoch
         finally:
             if image_logger is not None:
                 image_logger.flush()
+            if self.metrics_logger is not None:
+                self.metrics_logger.close()
         if ckpt_path and is_rank0:
             self.save_checkpoint(ckpt_path)

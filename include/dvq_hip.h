@@ -46,7 +46,8 @@ const char* dvq_last_error(void);
  * written in csrc ("conv3x3_halo_kernel", "conv_nt_pipe_kernel", ...; no template arguments, no fold / reduce / transpose helpers), noted
  * at the dispatch branch that launches it.  "" when nothing was noted (those entry points clear it first).  For timing labels. */
 const char* dvq_last_kernel(void);
-int dvq_version(void);     /* 118: dvq_unordered_launches; dvq_set_deterministic orders every floating-point reduction of a training step;
+int dvq_version(void);     /* 119: dvq_scalar_push (+ dvq_scalar_push_state_bytes), dvq_codebook_health (training metric logs);
+                            * 118: dvq_unordered_launches; dvq_set_deterministic orders every floating-point reduction of a training step;
                             * 117: DVQ_IMPL_* names for the impl codes; one entry per convolution / GEMM pass (dvq_conv2d_fwd, _dgrad, _wgrad, dvq_gemm_tn
                             * take the arguments of their former _ex / _act / _mask / _oihw / _colsum variants; dvq_gemm_nt_res is gone);
                             * 116: dvq_grain_overlay, dvq_grain_lines, dvq_image_grid_u8 (+ dvq_image_grid_shape, dvq_imagelog_workspace_bytes):
@@ -650,6 +651,36 @@ int dvq_swap_f32(float* a, float* b, int64_t n, dvq_stream_t stream);
 /* dst[0..7] <- the eight scalars (passed by value in the launch: no pageable host copy, no host buffer to keep alive) */
 int dvq_set_f32x8(float* dst, float v0, float v1, float v2, float v3, float v4, float v5, float v6, float v7,
                   dvq_stream_t stream);
+/* Training metric logs (docs/design/22-metrics-logging.md).
+ * dvq_scalar_push gathers `count` <= 64 scalars into columns col0 .. col0 + count - 1 of a caller-owned state block of `columns` <= 256
+ * columns (dvq_scalar_push_state_bytes(columns) bytes, 8-byte aligned, zeroed by the caller before the first push and whenever the
+ * running sums restart):
+ *   state = { double sum[columns]; int64 cnt[columns]; int64 bad[columns]; float last[columns] }
+ * Scalar i is described BY VALUE in the record: code[i] one of DVQ_SCALAR_*, addr[i] the device address of one element of that type
+ * (naturally aligned), or for DVQ_SCALAR_IMM the value itself as the bit pattern of a double.  The record is copied into the launch
+ * arguments: the caller may free it at once, a recorded step keeps its own copy, no device pointer table exists.  Each value v is read
+ * once; column c = col0 + i then gets
+ *   last[c] = (float)v;   v finite: sum[c] += (double)v, cnt[c] += 1;   else: bad[c] += 1.
+ * One workgroup, one owner thread per column, no atomics: the order of the additions into a column is the order of the launches, equal
+ * inputs give bit-equal state, and the launch is not counted as unordered.  More than 64 scalars: several launches with rising col0.
+ * columns outside 1 .. 256, count outside 1 .. 64 or col0 + count > columns: DVQ_ESHAPE; the state_bytes call returns 0 then. */
+enum { DVQ_SCALAR_F32 = 0, DVQ_SCALAR_BF16 = 1, DVQ_SCALAR_F64 = 2, DVQ_SCALAR_I32 = 3, DVQ_SCALAR_I64 = 4, DVQ_SCALAR_IMM = 5,
+       DVQ_SCALAR_SKIP = 6 /* no scalar for this column in this launch: the column is left untouched */ };
+enum { DVQ_SCALAR_PUSH_MAX = 64, DVQ_SCALAR_COLUMNS_MAX = 256 };
+typedef struct {
+    uint64_t addr[64]; /* DVQ_SCALAR_PUSH_MAX device addresses (DVQ_SCALAR_IMM: fp64 bits of the value) */
+    uint8_t code[64];  /* DVQ_SCALAR_* of each */
+} dvq_scalar_record;
+size_t dvq_scalar_push_state_bytes(int64_t columns);
+int dvq_scalar_push(const dvq_scalar_record* rec, int32_t count, int32_t col0, int32_t columns, void* state, dvq_stream_t stream);
+/* Codebook usage of one step from per-code counts n[k] = counts[k * stride], k < K; counts_type DVQ_SCALAR_F32 or DVQ_SCALAR_I64 (the
+ * EMA quantiser's counts are column D of its fp32 [K, D + 1] statistics: stride D + 1).  Writes
+ *   out3 = { perplexity exp(-sum p log p) with p = n / sum n over the codes with n > 0;  number of codes with n > 0;  sum n }
+ * as fp32, computed in fp64 (out3_f64: NULL or three doubles that receive the same values before that rounding); sum n == 0 gives
+ * perplexity 0 and 0 active codes.  total: NULL or double [K], total[k] += n[k] (running usage of an epoch).  One workgroup; thread t
+ * owns the codes k = t mod 256 in ascending order, the 256 partials meet in a fixed tree: no atomics, bit-equal for equal inputs. */
+int dvq_codebook_health(const void* counts, int counts_type, int64_t K, int64_t stride, float* out3, double* out3_f64, double* total,
+                        dvq_stream_t stream);
 /* k distinct pseudo-random indices in [0, n) = prefix of a keyed Feistel permutation (replaces torch.randperm(n)[:k] of
  * quantize2_mask.py:93-98); state = uint64[2] {seed, counter} in device memory, the counter is advanced on the stream. */
 int dvq_sample_rows(int64_t* out, int64_t k, int64_t n, uint64_t* state, dvq_stream_t stream);

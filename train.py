@@ -18,6 +18,9 @@ path, without pytorch_lightning / OmegaConf:
 * `--deterministic` (Lightning's Trainer flag; off by default): every floating-point sum of the step in a fixed order and every host-side
   draw from the run's seed -- two runs with the same seed on one GPU walk the same trajectory bit for bit
   (docs/design/21-reproducible-training.md).  Stored in the run's saved config (`lightning.trainer.deterministic`), so `-r` keeps it.
+* `-l/--logger none|csv|tensorboard` (or a comma list; default none) with `--log_every_n_steps N` (Lightning's flag, default 50): every
+  scalar the model logs as `<key>_step` rows and `<key>_epoch` means in `<logdir>/metrics.csv` and / or a TensorBoard event file
+  (docs/design/22-metrics-logging.md).  Stored in the saved config (`lightning.trainer.logger`, `.log_every_n_steps`), so `-r` keeps logging.
 Unsupported Trainer flags are accepted and ignored with a warning, like unknown Lightning flags would be.
 """
 from __future__ import annotations
@@ -38,7 +41,10 @@ def get_parser():
     p.add_argument("-b", "--base", nargs="*", metavar="base_config.yaml", default=list())
     p.add_argument("-s", "--seed", type=int, default=2021)
     p.add_argument("-f", "--postfix", type=str, default="")
-    p.add_argument("-l", "--logger", type=str, default="none")
+    p.add_argument("-l", "--logger", type=str, default="none",
+                   help="scalar logs of the run: none | csv (<logdir>/metrics.csv) | tensorboard (<logdir>/tensorboard/) | a comma list; "
+                        "wandb is accepted and ignored")
+    p.add_argument("--log_every_n_steps", type=int, default=50, help="with --logger: a row of `<key>_step` values every N steps (Lightning's Trainer flag)")
     p.add_argument("-d", "--debug", action="store_true")
     p.add_argument("-p", "--project", type=str, default="dvq")
     p.add_argument("--save_n", type=int, default=3, help="save top-n checkpoints by the model's `monitor` (train.py:48 of the reference)")
@@ -142,6 +148,16 @@ def run(rank, world, opt, unknown):
     if opt.deterministic:
         config = cfg.merge(config, cfg.from_dotlist(["lightning.trainer.deterministic=true"]))
     deterministic = bool(config.get("lightning", {}).get("trainer", {}).get("deterministic", False))
+    # -l/--logger and --log_every_n_steps likewise (docs/design/22-metrics-logging.md): a resumed run keeps writing the logs it began
+    from dynamicvectorquantization_amd.metrics import parse_logger_flag
+    writers, unsupported = parse_logger_flag(opt.logger)
+    if unsupported and rank == 0:
+        print(f"[train.py] ignoring unsupported loggers: {unsupported}")
+    if writers:
+        config = cfg.merge(config, {"lightning": {"trainer": {"logger": ",".join(writers), "log_every_n_steps": int(opt.log_every_n_steps)}}})
+    saved_trainer = config.get("lightning", {}).get("trainer", {})
+    writers, _ = parse_logger_flag(saved_trainer.get("logger", "none"))
+    log_every_n_steps = int(saved_trainer.get("log_every_n_steps", opt.log_every_n_steps))
     if logdir is None:
         now = datetime.datetime.now().strftime("%Y-%m-%dT%H-%M-%S")
         logdir = os.path.join(opt.logdir, now + ("_" + opt.name if opt.name else "") + opt.postfix)
@@ -218,9 +234,13 @@ def run(rank, world, opt, unknown):
         token_iter = _token_batches()
 
     total = model.training_steps if opt.max_steps < 0 else min(opt.max_steps, model.training_steps)
+    metrics_logger = None
+    if writers and rank == 0:            # rank 0 writes its own values, like Lightning does for keys logged without sync_dist
+        from dynamicvectorquantization_amd.metrics import MetricsLogger
+        metrics_logger = MetricsLogger(logdir, writers=writers, log_every_n_steps=log_every_n_steps)
     trainer = Trainer(model, max_steps=total, log_every=10 if rank == 0 else 0, gradient_clip_val=opt.gradient_clip_val,
                       skip_nonfinite=opt.skip_nonfinite_grads, ema_decay=opt.ema_decay, ema_warmup=not opt.ema_no_warmup,
-                      deterministic=deterministic)
+                      deterministic=deterministic, metrics_logger=metrics_logger)
     pool = [torch.from_numpy(synth.half_flat_images(bs, size, seed=opt.seed + 977 * rank + i)).to(dev) for i in range(4)]
 
     image_key = getattr(model, "image_key", None) or getattr(model, "first_stage_key", "image")
