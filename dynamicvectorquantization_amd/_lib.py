@@ -81,6 +81,7 @@ SIGNATURES = {
     "dvq_gn_bwd_dx": (i32, [vp, vp, i32, i64, i64, i64, i32, vp, vp, vp, i32, vp, vp, vp, vp]),
     "dvq_conv2d_fwd": (i32, [C.POINTER(ConvDesc), vp, vp, vp, vp, vp, vp, vp, i32, i32, vp]),
     "dvq_conv3x3_fused_ok": (i32, [C.POINTER(ConvDesc)]),
+    "dvq_conv3x3_subpixel_ok": (i32, [C.POINTER(ConvDesc)]),
     "dvq_split_bf16_planes": (i32, [vp, vp, vp, i64, i64, i64, vp]),
     "dvq_conv3x3_x3_ok": (i32, [C.POINTER(ConvDesc), i32]),
     "dvq_conv3x3_x3_scratch_bytes": (i64, [C.POINTER(ConvDesc), i32]),

@@ -39,6 +39,9 @@ struct HaloParams {
     int tiles_x, tiles_y, gn;
     int flip;            // 1: weight tap index is 8 - tap (dgrad through the [Cin][3][3][Cout] pack)
     int up;              // 1: X is stored [N,H/2,W/2,Cin] and read through nearest x2 (Upsample, model.py:50)
+    int sub;             // nearest x2 + 3x3 as four 2x2 sub-pixel convolutions (template parameter SUB; H, W are the LOW resolution):
+                         //   1: forward, X [N,H,W,Cin] -> Y [N,2H,2W,Cout], Wt = Weff [class][Cout][4][Cin]
+                         //   2: input gradient, X = dY [N,2H,2W,Cin] -> Y = dX [N,H,W,Cout], Wt = WeffT [Cout][class][4][Cin]
     const float* gn_ss;  // optional fused GroupNorm+swish on the INPUT: per (n, ci) {scale, shift} fp32 [N][Cin][2];
                          //   the halo tile is transformed in LDS once per chunk (zero padding stays zero)
     double* out_stats;   // optional GroupNorm statistics of the OUTPUT: fp64 [N][G][2] += (sum, sum of squares)
@@ -91,7 +94,18 @@ constexpr int VOFF_OOB = 0x7ffffff0;            // beyond every descriptor's ran
 // products of the split scheme side by side on the channel axis -- x' = [x_hi | x_lo | x_hi], w' = [w_hi | w_hi | w_lo], 3 Cin channels --
 // so one launch forms x_hi.w_hi + x_lo.w_hi + x_hi.w_lo in its fp32 accumulators (dvq_conv2d_fwd_x3 / dvq_conv2d_dgrad_x3, igemm.hip).
 // Only the epilogue differs: the 256 px x CO_T tile is staged 64 channels (256-B fp32 rows) at a time through the same 64 KiB.
-template <int NT, bool TRACE = false, bool OUT32 = false>
+//
+// SUB (nearest x2 upsample + 3x3, Upsample of model.py:38-53): the upsampled image holds every source pixel four times, so an output pixel
+// of parity class (py, px) sees only 2 x 2 distinct source pixels and the convolution is four 2 x 2 convolutions on the LOW-resolution
+// input, their weights the sums of the 3x3 taps that fall on the same source pixel (rows: py = 0: {0}, {1, 2}; py = 1: {0, 1}, {2};
+// columns alike; dvq_pack_weight writes them).  16 tap products per 4 output pixels instead of 36.  The loop walks NTAPS = 4 taps:
+//   SUB = 1, forward: tiles are 8 x 32 low-res pixels, the class rides on the output-channel block index (4 x as many workgroups per
+//     pixel tile, neighbours in dispatch order: they share the halo in L2), tap t reads halo offset (py + (t >> 1), px + (t & 1)), the
+//     store loop writes pixel (2 y + py, 2 x + px);
+//   SUB = 2, input gradient: the contraction runs over 4 x Cin / 64 chunks, a chunk belongs to one class: its halo is the class's pixels
+//     (2 gy + py, 2 gx + px) of dY, its taps sit at the mirrored offsets (2 - py - (t >> 1), 2 - px - (t & 1)).  The low-resolution
+//     gradient leaves the kernel from ONE fp32 accumulation: no full-resolution workspace, no 2 x 2 sum pass.
+template <int NT, bool TRACE = false, bool OUT32 = false, int SUB = 0>
 __global__ __launch_bounds__(256, 2) void conv3x3_halo_kernel(HaloParams p) {
 #if defined(__HIP_DEVICE_COMPILE__)      // (buffer-descriptor builtins exist in the device pass only; the host pass needs just the stub)
     constexpr int NW = 4, MT = 2, NTH = 256;
@@ -99,6 +113,8 @@ __global__ __launch_bounds__(256, 2) void conv3x3_halo_kernel(HaloParams p) {
     constexpr int CPRW = CO_T / 8;      // 16-byte chunks per staged output row
     constexpr int ROWS = CO_T * 2;      // bytes of a staged output row
     constexpr int SWZ_SH = CPRW == 16 ? 0 : CPRW == 8 ? 1 : 2;
+    constexpr int NTAPS = SUB ? 4 : 9;  // taps the loop walks per channel chunk
+    static_assert(SUB == 0 || (!OUT32 && !TRACE), "sub-pixel forms: bf16 output only");
     extern __shared__ __attribute__((aligned(16))) char smem[];
     char* halo = smem;
     char* bst = smem + HALOB;
@@ -128,10 +144,12 @@ __global__ __launch_bounds__(256, 2) void conv3x3_halo_kernel(HaloParams p) {
     qd = fdiv_u32(wi, p.mg_ty);
     const int ty = (int)(wi - qd * p.tiles_y);
     const int n = (int)qd;
-    const int y0 = ty * TH, x0 = tx * TW, n0 = nt_blk * CO_T;
+    int cls = SUB == 1 ? (nt_blk & 3) : 0;             // parity class 2 py + px (SUB = 2: of the current chunk)
+    const int y0 = ty * TH, x0 = tx * TW, n0 = (SUB == 1 ? nt_blk >> 2 : nt_blk) * CO_T;
     if (tid < CO_T) sbias[tid] = (p.bias != nullptr && n0 + tid < p.Cout) ? p.bias[n0 + tid] : 0.f;
     const int SWd = p.W >> p.up;                       // stored input width
-    const bf16_t* Xn = p.X + (int64_t)n * (p.H >> p.up) * SWd * p.Cin;
+    const int xbytes = (SUB == 2 ? 4 : 1) * (p.H >> p.up) * SWd * p.Cin * 2;       // one stored input image
+    const bf16_t* Xn = p.X + (int64_t)n * (xbytes >> 1);
     const int lrow = lane >> 3, cpos = lane & 7;       // DMA lane roles: row within an 8-row piece, 16-B chunk position
 
     constexpr int NP = CO_T / NW / 8;           // weight DMA pieces per wave and tap
@@ -141,16 +159,28 @@ __global__ __launch_bounds__(256, 2) void conv3x3_halo_kernel(HaloParams p) {
     for (int i = 0; i < NP; ++i) {
         const int row = wave * (CO_T / NW) + i * 8 + lrow;
         // rows past Cout re-read the last real row: their output channels are never stored nor counted in the statistics
-        boff[i] = min(n0 + row, p.Cout - 1) * 9 * p.Cin + (cpos ^ ((row >> 1) & 7)) * 8;
+        if constexpr (SUB == 1) boff[i] = (cls * p.Cout + min(n0 + row, p.Cout - 1)) * 4 * p.Cin + (cpos ^ ((row >> 1) & 7)) * 8;
+        else boff[i] = min(n0 + row, p.Cout - 1) * (SUB == 2 ? 16 : 9) * p.Cin + (cpos ^ ((row >> 1) & 7)) * 8;
         if (p.dbg >= 35 && p.dbg <= 38) boff[i] = VOFF_OOB / 2;        // experiment: no weight traffic (the DMA writes zeros)
     }
     // DMA through buffer descriptors (base in SGPRs, one 32-bit lane offset, tap / channel chunk as the scalar offset): no
     // per-piece 64-bit address arithmetic, and padding pixels are simply out of the descriptor's range (they read as zero)
-    const __amdgpu_buffer_rsrc_t rsW = __builtin_amdgcn_make_buffer_rsrc(const_cast<bf16_t*>(p.Wt), 0, p.Cout * 9 * p.Cin * 2, 0x00020000);
-    const __amdgpu_buffer_rsrc_t rsX = __builtin_amdgcn_make_buffer_rsrc(const_cast<bf16_t*>(Xn), 0, (p.H >> p.up) * SWd * p.Cin * 2, 0x00020000);
+    const __amdgpu_buffer_rsrc_t rsW = __builtin_amdgcn_make_buffer_rsrc(const_cast<bf16_t*>(p.Wt), 0, p.Cout * (SUB ? 16 : 9) * p.Cin * 2, 0x00020000);
+    const __amdgpu_buffer_rsrc_t rsX = __builtin_amdgcn_make_buffer_rsrc(const_cast<bf16_t*>(Xn), 0, xbytes, 0x00020000);
     // halo pieces of this wave (wave, wave + 4, ...): byte offset of this lane's 16 bytes at channel 0, once per TILE
     int hvo[NHP];
-    if (p.up == 0) {
+    if constexpr (SUB == 2) {
+        // low-res halo pixel (gy, gx) reads dY at (2 gy + py, 2 gx + px): doubled strides here, the class's (py, px) and the channel
+        // chunk ride on the per-chunk scalar offset
+#pragma unroll
+        for (int i = 0; i < NHP; ++i) {
+            const int hp = (wave + NW * i) * 8 + lrow;
+            const int hy = hp / HW_, hx = hp - hy * HW_;
+            const int gy = y0 - 1 + hy, gx = x0 - 1 + hx;
+            const bool ok = hp < HROWS && (unsigned)gy < (unsigned)p.H && (unsigned)gx < (unsigned)p.W;
+            hvo[i] = ok ? ((4 * gy * p.W + 2 * gx) * p.Cin + (cpos ^ ((hp >> 1) & 7)) * 8) * 2 : VOFF_OOB;
+        }
+    } else if (p.up == 0) {
         // halo pixel hp = 32 i + h0 (h0 = 8 wave + lrow < 32 < HW_): (hy, hx) advance by (0, +32) or, past the row end, (+1, -2); the
         // swizzle term (hp >> 1) & 7 does not change with i.  Rows above / below the image lie outside the per-image descriptor by
         // themselves (negative or too large offsets); only the left / right padding columns need the explicit out-of-range offset
@@ -180,7 +210,7 @@ __global__ __launch_bounds__(256, 2) void conv3x3_halo_kernel(HaloParams p) {
         for (int i = 0; i < NHP; ++i) hvo[i] = VOFF_OOB;
     }
     auto issue_b_piece = [&](int i, int tapx, int c0, int buf) {
-        const int tb = p.flip ? 8 - tapx : tapx;
+        const int tb = SUB == 0 && p.flip ? 8 - tapx : tapx;       // (SUB: c0 is the chunk's weight base, class included)
         __builtin_amdgcn_raw_ptr_buffer_load_lds(
             rsW, (__attribute__((address_space(3))) void*)(bst + buf * BSTAGE + (wave * (CO_T / NW) + i * 8) * ROWB), 16, boff[i] * 2,
             p.dbg == 39 || p.dbg == 40 ? 0 : (tb * p.Cin + c0) * 2, 0, 0);      // (39 / 40: every tap re-reads the same 16 KB: L1 hits)
@@ -202,7 +232,8 @@ __global__ __launch_bounds__(256, 2) void conv3x3_halo_kernel(HaloParams p) {
     };
 
     const int swzB = (l31 >> 1) & 7;
-    const int nchunks = p.dbg == 2 ? 0 : (p.Cin >> 6);
+    const int cpc = p.Cin >> 6;                                     // 64-channel chunks (SUB = 2: per class)
+    const int nchunks = p.dbg == 2 ? 0 : (SUB == 2 ? 4 * cpc : cpc);
     // Residual add on the MATRIX pipe (128-channel tiles): y = conv + R is computed as acc += I * R^T -- 16 extra MFMAs per wave (3 % of
     // the tile's) on a residual tile that LDS-DMA drops into the dead halo / weight stages under the last MFMAs of the loop, instead
     // of ~450 unpack / add / pack vector instructions per lane in the store loop, which issue once per MFMA of the CU neighbour
@@ -253,7 +284,17 @@ __global__ __launch_bounds__(256, 2) void conv3x3_halo_kernel(HaloParams p) {
     const char* pb;
     int sa[MT];
     auto set_tap = [&](int tapx, int buf) {
-        const int kh = tapx / 3, kw = tapx - kh * 3;
+        int kh, kw;
+        if constexpr (SUB == 0) {
+            kh = tapx / 3;
+            kw = tapx - kh * 3;
+        } else if constexpr (SUB == 1) {
+            kh = (cls >> 1) + (tapx >> 1);
+            kw = (cls & 1) + (tapx & 1);
+        } else {
+            kh = 2 - (cls >> 1) - (tapx >> 1);
+            kw = 2 - (cls & 1) - (tapx & 1);
+        }
 #pragma unroll
         for (int mt = 0; mt < MT; ++mt) {
             const int hp = (MT * wm + mt + kh) * HW_ + l31 + kw;
@@ -297,8 +338,20 @@ __global__ __launch_bounds__(256, 2) void conv3x3_halo_kernel(HaloParams p) {
     using IVB = std::integral_constant<int, NP - NPH>;   // during the first step of the tap before it: a whole tap of MFMAs lies
                                                     //   between the last DMA and the barrier that waits for it
     int g = 0;                                      // taps done: weight stage of tap g is g & 1
+    int ck = 0;                                     // SUB = 2: chunk within the class
     for (int c = 0; c < nchunks; ++c) {
-        const int c0 = c * 64;
+        // element offsets of this chunk / the next one (past the last: chunk 0) in a weight row (c0, c0x) and in a halo pixel (hbx)
+        int c0 = c * 64, c0x = c + 1 < nchunks ? c0 + 64 : 0, hbx = c0x;
+        int cls_x = 0, cc_x = 0;
+        if constexpr (SUB == 2) {
+            if (c + 1 < nchunks) {
+                cc_x = ck + 1 < cpc ? ck + 1 : 0;
+                cls_x = ck + 1 < cpc ? cls : cls + 1;
+            }
+            c0 = cls * 4 * p.Cin + ck * 64;
+            c0x = cls_x * 4 * p.Cin + cc_x * 64;
+            hbx = ((cls_x >> 1) * 2 * p.W + (cls_x & 1)) * p.Cin + cc_x * 64;
+        }
         // {scale, shift} of channel pair (2 q, 2 q + 1) stored as {scale, scale', shift, shift'}: operands of the packed-fp32 instructions
         if (p.gn_ss != nullptr && tid < 128)
             ssl[(tid >> 2) * 4 + (tid & 1) * 2 + ((tid >> 1) & 1)] = p.gn_ss[((int64_t)n * p.Cin + c0) * 2 + tid];
@@ -338,12 +391,11 @@ __global__ __launch_bounds__(256, 2) void conv3x3_halo_kernel(HaloParams p) {
             for (int i = 0; i < NPH; ++i) issue_b_piece(i, 1, 0, 1);
         }
         auto tap_body = [&](int tap, auto last_tag) {
-            constexpr bool LAST = decltype(last_tag)::value;      // tap 8: what follows is the next chunk (or the epilogue)
+            constexpr bool LAST = decltype(last_tag)::value;      // last tap: what follows is the next chunk (or the epilogue)
             const int buf = g & 1;
             // taps g + 1 and g + 2 (past the last chunk: harmless re-fetches of chunk 0 into dead stages)
-            const int c0x = c + 1 < nchunks ? c0 + 64 : 0;
             const int tap1 = LAST ? 0 : tap + 1, c01 = LAST ? c0x : c0;
-            const int tap2 = tap + 2 < 9 ? tap + 2 : tap + 2 - 9, c02 = tap + 2 < 9 ? c0 : c0x;
+            const int tap2 = tap + 2 < NTAPS ? tap + 2 : tap + 2 - NTAPS, c02 = tap + 2 < NTAPS ? c0 : c0x;
             __builtin_amdgcn_sched_barrier(0);
             load_frags(1, 1);
 #pragma unroll
@@ -363,7 +415,7 @@ __global__ __launch_bounds__(256, 2) void conv3x3_halo_kernel(HaloParams p) {
                 mfma_step(1, IDS{}, IVA{});
             } else {
                 if (c + 1 < nchunks) {                         // (nothing may be in flight when the epilogue re-uses the LDS)
-                    issue_halo_buf(c0 + 64);                   // the halo tile is dead: refill it under the last MFMAs
+                    issue_halo_buf(hbx);                       // the halo tile is dead: refill it under the last MFMAs
 #pragma unroll
                     for (int i = 0; i < NPH; ++i) issue_b_piece(i, tap2, c02, buf);
                 } else if (res_mfma && p.dbg != 31) {
@@ -374,8 +426,12 @@ __global__ __launch_bounds__(256, 2) void conv3x3_halo_kernel(HaloParams p) {
             ++g;
         };
 #pragma unroll 1
-        for (int tap = 0; tap < 8; ++tap) tap_body(tap, std::false_type{});
-        tap_body(8, std::true_type{});
+        for (int tap = 0; tap < NTAPS - 1; ++tap) tap_body(tap, std::false_type{});
+        tap_body(NTAPS - 1, std::true_type{});
+        if constexpr (SUB == 2) {
+            cls = cls_x;
+            ck = cc_x;
+        }
     }
 
     if constexpr (NT == 4) {
@@ -493,15 +549,19 @@ __global__ __launch_bounds__(256, 2) void conv3x3_halo_kernel(HaloParams p) {
     const int trow = PPI == 64 ? tq >> 5 : 0, tcol = tq & 31;
     const int col = n0 + ch * 8;
     // per-image descriptors: lane offset fixed, the iteration's pixel step is the scalar offset
-    const int64_t img = (int64_t)n * p.H * p.W * p.Cout;
-    const __amdgpu_buffer_rsrc_t rsY = __builtin_amdgcn_make_buffer_rsrc(p.Y + img, 0, p.H * p.W * p.Cout * 2, 0x00020000);
+    // (SUB = 1: tile pixel (r, c) of class (py, px) is output pixel (2 (y0 + r) + py, 2 (x0 + c) + px) of the [2H, 2W] image: doubled
+    //  pixel and row strides, the class offset on the tile's scalar offset)
+    constexpr int PS = SUB == 1 ? 2 : 1;
+    const int OW = PS * p.W, ybytes = PS * PS * p.H * p.W * p.Cout * 2;
+    const int64_t img = (int64_t)n * (ybytes >> 1);
+    const __amdgpu_buffer_rsrc_t rsY = __builtin_amdgcn_make_buffer_rsrc(p.Y + img, 0, ybytes, 0x00020000);
     const __amdgpu_buffer_rsrc_t rsR = __builtin_amdgcn_make_buffer_rsrc(const_cast<bf16_t*>(p.R != nullptr ? p.R + img : p.Y + img), 0,
-                                                                         p.H * p.W * p.Cout * 2, 0x00020000);
-    const int vo_px = col < p.Cout ? ((trow * p.W + tcol) * p.Cout + col) * 2 : VOFF_OOB;
-    const int so_tile = ((y0 * p.W + x0) * p.Cout) * 2;
+                                                                         ybytes, 0x00020000);
+    const int vo_px = col < p.Cout ? ((trow * PS * OW + tcol * PS) * p.Cout + col) * 2 : VOFF_OOB;
+    const int so_tile = SUB == 1 ? (((y0 * 2 + (cls >> 1)) * OW + x0 * 2 + (cls & 1)) * p.Cout) * 2 : ((y0 * p.W + x0) * p.Cout) * 2;
     auto so_iter = [&](int i) {      // scalar byte offset of iteration i's pixel step
         const int r = PPI == 16 ? (i >> 1) : PPI == 32 ? i : 2 * i, cc = PPI == 16 ? 16 * (i & 1) : 0;
-        return so_tile + ((r * p.W + cc) * p.Cout) * 2;
+        return so_tile + ((r * PS * OW + cc * PS) * p.Cout) * 2;
     };
     // residual / gate tile: requested before the staging so that its latency hides behind it
     uint4 rpre[ITERS];
@@ -601,8 +661,10 @@ __global__ __launch_bounds__(256, 2) void conv3x3_halo_kernel(HaloParams p) {
             if (half == 0 && (l31 & (cpg - 1)) == 0 && n0 + c0ch < p.Cout) {
                 const int gg = (n0 + c0ch) / cpg;
                 if (p.stat_part != nullptr) {
-                    const int ntiles = p.tiles_y * p.tiles_x;
-                    float* dst = p.stat_part + ((((int64_t)n * p.out_groups + gg) * ntiles) + ty * p.tiles_x + tx) * 2;
+                    // (SUB = 1: the four classes of a tile own separate slots, folded in slot order by halo_stats_finalize_kernel)
+                    const int ntiles = p.tiles_y * p.tiles_x * (SUB == 1 ? 4 : 1);
+                    const int slot = SUB == 1 ? (ty * p.tiles_x + tx) * 4 + cls : ty * p.tiles_x + tx;
+                    float* dst = p.stat_part + ((((int64_t)n * p.out_groups + gg) * ntiles) + slot) * 2;
                     dst[0] = s1;
                     dst[1] = s2;
                 } else {
@@ -743,8 +805,10 @@ __global__ __launch_bounds__(256, 2) void conv3x3_halo_kernel(HaloParams p) {
             if ((c0ch & (cpg - 1)) == 0 && n0 + c0ch < p.Cout) {
                 const int gg = (n0 + c0ch) / cpg;
                 if (p.stat_part != nullptr) {
-                    const int ntiles = p.tiles_y * p.tiles_x;
-                    float* dst = p.stat_part + ((((int64_t)n * p.out_groups + gg) * ntiles) + ty * p.tiles_x + tx) * 2;
+                    // (SUB = 1: the four classes of a tile own separate slots, folded in slot order by halo_stats_finalize_kernel)
+                    const int ntiles = p.tiles_y * p.tiles_x * (SUB == 1 ? 4 : 1);
+                    const int slot = SUB == 1 ? (ty * p.tiles_x + tx) * 4 + cls : ty * p.tiles_x + tx;
+                    float* dst = p.stat_part + ((((int64_t)n * p.out_groups + gg) * ntiles) + slot) * 2;
                     dst[0] = s1;
                     dst[1] = s2;
                 } else {
@@ -807,14 +871,18 @@ extern "C" int dvq_halo_trace_read(unsigned long long* dst, int64_t max_records)
 
 // Returns 1 if the halo kernel handled the call, 0 if the shape is not eligible (caller falls back to igemm),
 // negative on error.  x: [N,H,W,Cin] bf16; w: rows of [9][Cin]; y: [N,H,W,Cout].
+// sub (HaloParams::sub): H, W are the LOW resolution, the other tensor is [N,2H,2W,.], w is the sub-pixel pack; the caller checked the shape
 static int halo_try_impl(const void* x, const void* w, const float* bias, const void* residual, void* y, int64_t N,
                          int64_t H, int64_t W, int64_t Cin, int64_t Cout, int flip, int up, const float* gn_ss,
                          double* out_stats, int out_groups, float act_slope, int res_mask, float mask_slope,
-                         hipStream_t stream, bool out32) {
+                         hipStream_t stream, bool out32, int sub = 0) {
     if (H % TH != 0 || W % TW != 0 || Cin % 64 != 0 || Cout % (out32 ? 4 : 8) != 0) return 0;
+    if (sub && (out32 || up || flip || residual != nullptr || gn_ss != nullptr || act_slope != 1.f || Cout % 64 != 0 ||
+                N * 4 * H * W * (Cin > Cout ? Cin : Cout) >= (1ll << 30) || Cout * 16 * Cin >= (1ll << 30)))
+        return 0;
     if (out32 && (gn_ss != nullptr || out_stats != nullptr || H * W * Cout * 4 >= (1ll << 31))) return 0;
 #ifdef DVQ_PROBES
-    if (!out32) {   // the persistent kernel (conv_halo2.hip, DVQ_HALO2=1) takes the launches it is built for: 128-channel output blocks, >= 2 tiles per CU
+    if (!out32 && !sub) {   // the persistent kernel (conv_halo2.hip, DVQ_HALO2=1) takes the launches it is built for: 128-channel output blocks, >= 2 tiles per CU
         const int rc2 = dvq_conv3x3_halo2_try(x, w, bias, residual, y, N, H, W, Cin, Cout, flip, up, gn_ss, out_stats, out_groups, act_slope,
                                               res_mask, mask_slope, stream);
         if (rc2 != 0) return rc2;
@@ -830,16 +898,17 @@ static int halo_try_impl(const void* x, const void* w, const float* bias, const 
     HaloParams p{};
     p.X = (const bf16_t*)x; p.Wt = (const bf16_t*)w; p.Y = (bf16_t*)y; p.R = (const bf16_t*)residual; p.bias = bias;
     p.N = (int)N; p.H = (int)H; p.W = (int)W; p.Cin = (int)Cin; p.Cout = (int)Cout;
-    p.tiles_x = (int)(W / TW); p.tiles_y = (int)(H / TH); p.gn = (int)cdiv64(Cout, cot);
+    p.tiles_x = (int)(W / TW); p.tiles_y = (int)(H / TH); p.gn = (int)cdiv64(Cout, cot) * (sub == 1 ? 4 : 1);
     p.flip = flip;
     p.up = up;
+    p.sub = sub;
     p.gn_ss = gn_ss; p.out_stats = out_stats; p.out_groups = out_groups;
     p.act_slope = act_slope; p.res_mask = res_mask; p.mask_slope = mask_slope;
     static const int nt_env = [] {
         const char* e = getenv("DVQ_HALO_NT");
         return e == nullptr ? 1 : atoi(e);
     }();
-    p.nt_out = nt_env && !out32 && N * H * W * Cout * 2 > (192ll << 20);
+    p.nt_out = nt_env && !out32 && N * H * W * Cout * 2 * (sub == 1 ? 4 : 1) > (192ll << 20);
     static const int ms_env = [] {
         const char* e = getenv("DVQ_HALO_MFMA_STATS");
         return e == nullptr ? 1 : atoi(e);
@@ -849,10 +918,10 @@ static int halo_try_impl(const void* x, const void* w, const float* bias, const 
         const char* e = getenv("DVQ_HALO_NT_IN");
         return e == nullptr ? 0 : atoi(e);
     }();
-    p.nt_in = nt_in_env && p.gn == 1 && (N * H * W * Cin * 2 >> up >> up) > (192ll << 20);
+    p.nt_in = nt_in_env && p.gn == 1 && !sub && (N * H * W * Cin * 2 >> up >> up) > (192ll << 20);
     static const int dbg_env = dvq_probe_env("DVQ_HALO_DBG");       // 0 unless built with -DDVQ_PROBES
     p.dbg = dbg_env;
-    const int ntiles = p.tiles_y * p.tiles_x;
+    const int ntiles = p.tiles_y * p.tiles_x * (sub == 1 ? 4 : 1);      // partial slots per (n, group): one per tile and class
     if (out_stats != nullptr) {
         int64_t ws_bytes = 0;
         void* ws = dvq_workspace_stream(stream, &ws_bytes);
@@ -882,7 +951,13 @@ static int halo_try_impl(const void* x, const void* w, const float* bias, const 
         dvq_ensure_dynamic_lds((const void*)kern, LDSB + lds_pad);
         kern<<<dim3((unsigned)blocks), dim3(256), LDSB + lds_pad, stream>>>(p);
     };
-    if (out32) {
+    if (sub == 1) {
+        if (cot == 128) go(conv3x3_halo_kernel<4, false, false, 1>);
+        else go(conv3x3_halo_kernel<2, false, false, 1>);
+    } else if (sub == 2) {
+        if (cot == 128) go(conv3x3_halo_kernel<4, false, false, 2>);
+        else go(conv3x3_halo_kernel<2, false, false, 2>);
+    } else if (out32) {
         if (cot == 128) go(conv3x3_halo_kernel<4, false, true>);
         else if (cot == 64) go(conv3x3_halo_kernel<2, false, true>);
         else go(conv3x3_halo_kernel<1, false, true>);
@@ -913,6 +988,15 @@ int dvq_conv3x3_halo_try(const void* x, const void* w, const float* bias, const 
                          hipStream_t stream) {
     return halo_try_impl(x, w, bias, residual, y, N, H, W, Cin, Cout, flip, up, gn_ss, out_stats, out_groups, act_slope, res_mask,
                          mask_slope, stream, false);
+}
+
+// nearest x2 + 3x3 as four 2x2 sub-pixel convolutions (see SUB at the kernel).  h, w: LOW resolution.  dgrad = 0: x [N,h,w,Cin], wsub =
+// Weff [4][Cout][4][Cin], y [N,2h,2w,Cout]; dgrad = 1: x = dy [N,2h,2w,Cout], wsub = WeffT [Cin][4][4][Cout], y = dx [N,h,w,Cin]
+int dvq_conv3x3_halo_subpixel_try(const void* x, const void* wsub, const float* bias, void* y, int64_t N, int64_t h, int64_t w, int64_t Cin,
+                                  int64_t Cout, int dgrad, double* out_stats, int out_groups, hipStream_t stream) {
+    if (dgrad)
+        return halo_try_impl(x, wsub, nullptr, nullptr, y, N, h, w, Cout, Cin, 0, 0, nullptr, nullptr, 0, 1.f, 0, 0.f, stream, false, 2);
+    return halo_try_impl(x, wsub, bias, nullptr, y, N, h, w, Cin, Cout, 0, 0, nullptr, out_stats, out_groups, 1.f, 0, 0.f, stream, false, 1);
 }
 
 // bf16 x / w, FP32 residual (or gate) and output: the fp32x3 form (see the OUT32 note at the kernel)

@@ -30,6 +30,7 @@ int conv_check(const dvq_conv_desc* d, const char* who) {
                 DVQ_ESHAPE, "%s: non-positive dimension", who);
     DVQ_REQUIRE(d->N * d->OH * d->OW < (1ll << 31) && d->N * d->H * d->W < (1ll << 31), DVQ_ESHAPE,
                 "%s: more than 2^31 pixels", who);
+    DVQ_REQUIRE(d->upsample == 0 || d->upsample == 1, DVQ_EINVAL, "%s: upsample must be 0 or 1 (2: dvq_conv2d_fwd / _dgrad only)", who);
     DVQ_REQUIRE(!d->upsample || (d->H % 2 == 0 && d->W % 2 == 0), DVQ_ESHAPE, "%s: upsample needs even H, W", who);
     DVQ_REQUIRE(d->dtype == DVQ_F32 || d->dtype == DVQ_BF16, DVQ_EINVAL, "%s: bad dtype", who);
     // the implied bottom/right padding must keep every tap within one pad of the input
@@ -57,6 +58,15 @@ int dvq_conv3x3_thin_k_try(const void* x, const void* w, const float* bias, void
 
 int dvq_tconv4x4s2_thin_try(const void* dy, const void* wt, void* dx, int64_t N, int64_t OH, int64_t OW, int64_t Cout, int creal,
                             hipStream_t stream);
+
+// conv_halo.hip: nearest x2 + 3x3 as four 2x2 sub-pixel convolutions on the low-resolution tensor (h, w); dgrad = 1: the input gradient
+int dvq_conv3x3_halo_subpixel_try(const void* x, const void* wsub, const float* bias, void* y, int64_t N, int64_t h, int64_t w, int64_t Cin,
+                                  int64_t Cout, int dgrad, double* out_stats, int out_groups, hipStream_t stream);
+
+// A/B builds: -DDVQ_UPS_SUBPIXEL=0 (DVQ_BUILD_EXTRA_FLAGS) keeps every folded upsample on the 9-tap form
+#ifndef DVQ_UPS_SUBPIXEL
+#define DVQ_UPS_SUBPIXEL 1
+#endif
 
 static float act_slope_of(int act) { return act == DVQ_ACT_RELU ? 0.f : act == DVQ_ACT_LRELU ? 0.2f : 1.f; }
 
@@ -105,6 +115,25 @@ static int split_concat3(const float* x, void* out, int64_t rows, int64_t c, int
 static bool halo_eligible(const dvq_conv_desc* d) {
     return d->dtype == DVQ_BF16 && d->KH == 3 && d->KW == 3 && d->stride == 1 && d->pad_t == 1 && d->pad_l == 1 &&
            d->OH == d->H && d->OW == d->W && (d->impl == DVQ_IMPL_AUTO || d->impl == DVQ_IMPL_HALO);
+}
+
+// Shapes whose folded nearest-x2 upsample runs as four 2x2 sub-pixel convolutions (conv_halo.hip, SUB): bf16 halo shapes with the tile
+// grid on the LOW resolution and whole 64-channel chunks on both sides
+static bool subpixel_eligible(const dvq_conv_desc* d) {
+    const int64_t h = d->H / 2, w = d->W / 2;
+    return DVQ_UPS_SUBPIXEL && d->upsample && halo_eligible(d) && d->H % 2 == 0 && d->W % 2 == 0 && h % 8 == 0 && w % 32 == 0 &&
+           d->Cin % 64 == 0 && d->Cout % 64 == 0 && d->N * d->H * d->W * (d->Cin > d->Cout ? d->Cin : d->Cout) < (1ll << 30) &&
+           d->Cout * 16 * d->Cin < (1ll << 30);
+}
+
+// dvq_conv2d_fwd / dvq_conv2d_dgrad: upsample == 2 is upsample == 1 with the sub-pixel pack behind the 3x3 pack of the weight argument
+// (dvq_pack_weight, bit 9 of dtype); every other entry, and everything behind these two, sees 0 / 1
+static int conv_check_up2(dvq_conv_desc* dd, const char* who) {
+    const bool sub = dd->upsample == 2;
+    if (sub) dd->upsample = 1;
+    if (int e = conv_check(dd, who)) return e;
+    DVQ_REQUIRE(!sub || subpixel_eligible(dd), DVQ_ESHAPE, "%s: upsample == 2 needs a shape accepted by dvq_conv3x3_subpixel_ok", who);
+    return sub ? 1 : DVQ_OK;
 }
 
 // NtParams of a convolution pass.  MODE_FWD: A = x streams d->Cin channels, C = y is the output map; MODE_TCONV (input gradient): A = dy
@@ -183,9 +212,21 @@ int dvq_conv3x3_fused_ok(const dvq_conv_desc* d) {
            d->N * d->H * d->W * (d->Cin > d->Cout ? d->Cin : d->Cout) < (1ll << 31);
 }
 
-int dvq_conv2d_fwd(const dvq_conv_desc* d, const void* x, const void* w, const float* bias, const void* residual, void* y,
+int dvq_conv3x3_subpixel_ok(const dvq_conv_desc* d) {
+    if (d == nullptr || d->upsample == 0) return 0;
+    dvq_conv_desc dd = *d;
+    dd.upsample = 1;
+    return subpixel_eligible(&dd);
+}
+
+int dvq_conv2d_fwd(const dvq_conv_desc* d_in, const void* x, const void* w, const float* bias, const void* residual, void* y,
                    const float* gn_scale_shift, double* out_stats, int out_groups, int act, dvq_stream_t stream) {
-    if (int e = conv_check(d, "dvq_conv2d_fwd")) return e;
+    dvq_note_kernel("");
+    DVQ_REQUIRE(d_in != nullptr, DVQ_EINVAL, "dvq_conv2d_fwd: null descriptor");
+    dvq_conv_desc dd = *d_in;
+    const dvq_conv_desc* d = &dd;
+    const int sub = conv_check_up2(&dd, "dvq_conv2d_fwd");
+    if (sub < 0) return sub;
     DVQ_REQUIRE(act == DVQ_ACT_NONE || act == DVQ_ACT_RELU || act == DVQ_ACT_LRELU, DVQ_EINVAL, "dvq_conv2d_fwd: bad act");
     DVQ_REQUIRE(act == DVQ_ACT_NONE || (residual == nullptr && gn_scale_shift == nullptr && out_stats == nullptr), DVQ_EINVAL,
                 "dvq_conv2d_fwd: activation together with residual, gn_scale_shift or out_stats");
@@ -193,6 +234,12 @@ int dvq_conv2d_fwd(const dvq_conv_desc* d, const void* x, const void* w, const f
     if (halo_eligible(d) && d->impl == DVQ_IMPL_AUTO && d->Cin == 8 && !d->upsample && residual == nullptr && gn_scale_shift == nullptr &&
         out_stats == nullptr) {          // image heads: 8 (padded) input channels
         const int rc = dvq_conv3x3_thin_k_try(x, w, bias, y, d->N, d->H, d->W, d->Cout, 0, act_slope_of(act), (hipStream_t)stream);
+        if (rc != 0) return rc < 0 ? rc : DVQ_OK;
+    }
+    if (sub && residual == nullptr && gn_scale_shift == nullptr && act == DVQ_ACT_NONE) {
+        const bf16_t* wsub = (const bf16_t*)w + d->Cout * 9 * d->Cin;
+        const int rc = dvq_conv3x3_halo_subpixel_try(x, wsub, bias, y, d->N, d->H / 2, d->W / 2, d->Cin, d->Cout, 0, out_stats, out_groups,
+                                                     (hipStream_t)stream);
         if (rc != 0) return rc < 0 ? rc : DVQ_OK;
     }
     if (halo_eligible(d)) {
@@ -213,12 +260,26 @@ int dvq_conv2d_fwd(const dvq_conv_desc* d, const void* x, const void* w, const f
 
 int dvq_sumpool2x2(const void* in, int dtype, int64_t N, int64_t h, int64_t w, int64_t C, void* out, dvq_stream_t stream);
 
-int dvq_conv2d_dgrad(const dvq_conv_desc* d, const void* dy, const void* wt, void* dx, void* ws, const void* mask, int mask_act,
+int dvq_conv2d_dgrad(const dvq_conv_desc* d_in, const void* dy, const void* wt, void* dx, void* ws, const void* mask, int mask_act,
                      dvq_stream_t stream) {
-    if (int e = conv_check(d, "dvq_conv2d_dgrad")) return e;
+    dvq_note_kernel("");
+    DVQ_REQUIRE(d_in != nullptr, DVQ_EINVAL, "dvq_conv2d_dgrad: null descriptor");
+    dvq_conv_desc dd = *d_in;
+    const dvq_conv_desc* d = &dd;
+    const int sub = conv_check_up2(&dd, "dvq_conv2d_dgrad");
+    if (sub < 0) return sub;
     DVQ_REQUIRE(mask == nullptr || ((mask_act == DVQ_ACT_RELU || mask_act == DVQ_ACT_LRELU) && !d->upsample), DVQ_EINVAL,
                 "dvq_conv2d_dgrad: mask needs act in {relu, lrelu} and no folded upsample");
-    DVQ_REQUIRE(dy && wt && dx && (!d->upsample || ws), DVQ_EINVAL, "dvq_conv2d_dgrad: null pointer");
+    DVQ_REQUIRE(dy && wt && dx && (!d->upsample || ws || sub), DVQ_EINVAL, "dvq_conv2d_dgrad: null pointer");
+    if (sub) {
+        // the low-resolution gradient straight from one fp32 accumulation: ws is not touched, no 2x2 sum pass
+        const bf16_t* wsub = (const bf16_t*)wt + d->Cin * 9 * d->Cout;
+        const int rc = dvq_conv3x3_halo_subpixel_try(dy, wsub, nullptr, dx, d->N, d->H / 2, d->W / 2, d->Cin, d->Cout, 1, nullptr, 0,
+                                                     (hipStream_t)stream);
+        if (rc < 0) return rc;
+        DVQ_REQUIRE(rc == 1, DVQ_ESHAPE, "dvq_conv2d_dgrad: the halo kernel refused the sub-pixel form");
+        return DVQ_OK;
+    }
     if (d->dtype == DVQ_BF16 && d->impl == DVQ_IMPL_AUTO && d->KH == 4 && d->KW == 4 && d->stride == 2 && d->pad_t == 1 && d->pad_l == 1 &&
         d->Cin == 8 && !d->upsample && mask == nullptr && d->H == 2 * d->OH && d->W == 2 * d->OW) {
         // input gradient of the PatchGAN's first conv (3 image channels): thin transposed conv

@@ -321,15 +321,40 @@ __global__ __launch_bounds__(256) void cast_kernel(const TI* __restrict__ in, TO
         ElemIO<TO>::store(out + e, ElemIO<TI>::load(in + e));
 }
 
-// master OIHW fp32 -> w [Cout][KH][KW][Cin_p] and wt [Cin][KH][KW][Cout_p] (zero padded)
+// Sub-pixel weight of a nearest-x2 upsample + 3x3 convolution (conv_halo.hip, SUB): output parity class cls = 2 py + px, tap t = 2 a + b
+// reads source pixel (i + a + py - 1, j + b + px - 1); the 3x3 taps that land on it are rows [a ? 1 + py : 0, a ? 2 : py], columns alike.
+// fp32 sum, rows then columns ascending; the caller rounds once.
+__device__ __forceinline__ float subpixel_weight(const float* m, int64_t co, int64_t ci, int cls, int t, int64_t Cin, bool ohwi) {
+    const int py = cls >> 1, px = cls & 1, a = t >> 1, b = t & 1;
+    const int u0 = a ? 1 + py : 0, u1 = a ? 2 : py, v0 = b ? 1 + px : 0, v1 = b ? 2 : px;
+    float s = 0.f;
+    for (int u = u0; u <= u1; ++u)
+        for (int v = v0; v <= v1; ++v) s += master_at(m, co, ci, u * 3 + v, Cin, 9, ohwi);
+    return s;
+}
+// element f of Weff [class][Cout][4][Cin] / of WeffT [Cin][class][4][Cout]
+__device__ __forceinline__ float subpixel_w_at(const float* m, unsigned f, unsigned Cout, unsigned Cin, bool ohwi) {
+    const unsigned row = f / Cin, ci = f - row * Cin, t = row & 3, r2 = row >> 2, cls = r2 / Cout, co = r2 - cls * Cout;
+    return subpixel_weight(m, co, ci, (int)cls, (int)t, Cin, ohwi);
+}
+__device__ __forceinline__ float subpixel_wt_at(const float* m, unsigned f, unsigned Cout, unsigned Cin, bool ohwi) {
+    const unsigned row = f / Cout, co = f - row * Cout, t = row & 3, cls = (row >> 2) & 3, ci = row >> 4;
+    return subpixel_weight(m, co, ci, (int)cls, (int)t, Cin, ohwi);
+}
+
+// master OIHW fp32 -> w [Cout][KH][KW][Cin_p] and wt [Cin][KH][KW][Cout_p] (zero padded); sub: + the sub-pixel packs behind them
 template <typename T>
 __global__ __launch_bounds__(256) void pack_weight_kernel(const float* __restrict__ m, int64_t Cout, int64_t Cin,
                                                           int64_t KH, int64_t KW, int64_t Cin_p, int64_t Cout_p,
-                                                          T* __restrict__ w, T* __restrict__ wt, bool ohwi) {
+                                                          T* __restrict__ w, T* __restrict__ wt, bool ohwi, bool sub) {
     const int64_t taps = KH * KW;
-    const int64_t nw = w ? Cout * taps * Cin_p : 0, nwt = wt ? Cin * taps * Cout_p : 0;
-    for (int64_t e = (int64_t)blockIdx.x * 256 + threadIdx.x; e < nw + nwt; e += (int64_t)gridDim.x * 256) {
-        if (e < nw) {
+    const int64_t nw = w ? Cout * taps * Cin_p : 0, nwt = wt ? Cin * taps * Cout_p : 0, nsub = sub ? 16 * Cout * Cin : 0;
+    for (int64_t e = (int64_t)blockIdx.x * 256 + threadIdx.x; e < nw + nwt + 2 * nsub; e += (int64_t)gridDim.x * 256) {
+        if (e >= nw + nwt) {        // (sub: both outputs given, no channel padding)
+            const int64_t f = e - nw - nwt;
+            if (f < nsub) ElemIO<T>::store(w + nw + f, subpixel_w_at(m, (unsigned)f, (unsigned)Cout, (unsigned)Cin, ohwi));
+            else ElemIO<T>::store(wt + nwt + f - nsub, subpixel_wt_at(m, (unsigned)(f - nsub), (unsigned)Cout, (unsigned)Cin, ohwi));
+        } else if (e < nw) {
             const int64_t ci = e % Cin_p, tap = (e / Cin_p) % taps, co = e / (Cin_p * taps);
             ElemIO<T>::store(w + e, ci < Cin ? master_at(m, co, ci, tap, Cin, taps, ohwi) : 0.f);
         } else {
@@ -347,7 +372,8 @@ struct PackEntry {       // mirrored by ctypes in _lib.py (7 x int64 + 3 pointer
     void* wt;
     int64_t Cout, Cin, taps, Cin_p, Cout_p;
     int64_t begin;       // first flat work index of this entry (prefix sum of nw + nwt)
-    int64_t dtype;       // bit 0: DVQ_F32/DVQ_BF16; bit 8: master is stored [Cout][taps][Cin] (OHWI) instead of OIHW
+    int64_t dtype;       // bit 0: DVQ_F32/DVQ_BF16; bit 8: master is stored [Cout][taps][Cin] (OHWI) instead of OIHW; bit 9: the sub-pixel
+                         //   packs follow w and wt (16 Cout Cin elements each, counted in `begin`; 3x3, unpadded channels)
 };
 
 __device__ __forceinline__ float master_at(const float* m, int64_t co, int64_t ci, int64_t tap, int64_t Cin, int64_t taps, bool ohwi) {
@@ -369,10 +395,19 @@ __global__ __launch_bounds__(256) void pack_weights_multi_kernel(const PackEntry
         const unsigned taps = (unsigned)t.taps, Cin = (unsigned)t.Cin, Cout = (unsigned)t.Cout;
         const unsigned nw = t.w ? Cout * taps * (unsigned)t.Cin_p : 0u;
         const bool ohwi = (t.dtype >> 8) & 1;
+        const unsigned nwt = t.wt ? Cin * taps * (unsigned)t.Cout_p : 0u;
         float v[4];
         void* dst;
         unsigned di;
-        if (f0 < nw) {
+        if (((t.dtype >> 9) & 1) && f0 >= nw + nwt) {
+            // sub-pixel packs (Cin, Cout multiples of 4: a quad stays in one row); destinations continue behind w / wt
+            const unsigned f = f0 - nw - nwt, nsub = 16u * Cout * Cin;
+#pragma unroll
+            for (int u = 0; u < 4; ++u)
+                v[u] = f < nsub ? subpixel_w_at(t.master, f + u, Cout, Cin, ohwi) : subpixel_wt_at(t.master, f - nsub + u, Cout, Cin, ohwi);
+            dst = f < nsub ? t.w : t.wt;
+            di = f < nsub ? nw + f : nwt + f - nsub;
+        } else if (f0 < nw) {
             const unsigned cp = (unsigned)t.Cin_p, row = f0 / cp, ci = f0 - row * cp, co = row / taps, tap = row - co * taps;
 #pragma unroll
             for (int u = 0; u < 4; ++u) v[u] = ci + u < Cin ? master_at(t.master, co, ci + u, tap, Cin, taps, ohwi) : 0.f;
@@ -974,7 +1009,7 @@ int dvq_set_fp32_split(int on) {
 
 const char* dvq_last_error(void) { return g_err; }
 const char* dvq_last_kernel(void) { return dvq_kernel_note; }
-int dvq_version(void) { return 119; }
+int dvq_version(void) { return 120; }
 long long dvq_unordered_launches(void) { return g_unordered.load(std::memory_order_relaxed); }
 
 int dvq_set_workspace(void* ptr, int64_t bytes) {
@@ -1163,11 +1198,14 @@ int dvq_cast(const void* in, int in_dtype, void* out, int out_dtype, int64_t n, 
 int dvq_pack_weight(const float* master, int64_t Cout, int64_t Cin, int64_t KH, int64_t KW, int64_t Cin_p,
                     int64_t Cout_p, int dtype, void* w, void* wt, dvq_stream_t stream) {
     DVQ_REQUIRE(master && (w || wt) && Cin_p >= Cin && Cout_p >= Cout, DVQ_EINVAL, "dvq_pack_weight: bad arguments");
-    const int64_t n = Cout * KH * KW * Cin_p + Cin * KH * KW * Cout_p;
     const bool ohwi = (dtype >> 8) & 1;      // bit 8: master stored [Cout][KH][KW][Cin]
+    const bool sub = (dtype >> 9) & 1;       // bit 9: sub-pixel packs behind w and wt
+    DVQ_REQUIRE(!sub || (w && wt && KH == 3 && KW == 3 && Cin_p == Cin && Cout_p == Cout && 16 * Cout * Cin < (1ll << 31)), DVQ_EINVAL,
+                "dvq_pack_weight: sub-pixel packs need both outputs, a 3x3 kernel and unpadded channels");
+    const int64_t n = Cout * KH * KW * Cin_p + Cin * KH * KW * Cout_p + (sub ? 32 * Cout * Cin : 0);
     dtype &= 0xff;
     DVQ_DISPATCH_DTYPE(dtype, T, pack_weight_kernel<T><<<dim3(nblocks(n, 256)), dim3(256), 0, (hipStream_t)stream>>>(
-                                     master, Cout, Cin, KH, KW, Cin_p, Cout_p, (T*)w, (T*)wt, ohwi););
+                                     master, Cout, Cin, KH, KW, Cin_p, Cout_p, (T*)w, (T*)wt, ohwi, sub););
     DVQ_CHECK_LAUNCH("pack_weight");
     return DVQ_OK;
 }

@@ -174,7 +174,8 @@ def _timed_conv(flops, nbytes, entry, call):
 
 
 def _conv_cost(d: ConvDesc, esize: int):
-    """algorithmic cost of one conv pass: 2*M*K*N flops; bytes = input + weights + output once each"""
+    """algorithmic cost of one conv pass: 2*M*K*N flops; bytes = input + weights + output once each.  A folded upsample that runs
+    as four 2x2 sub-pixel convolutions (conv_subpixel_ok) is still counted with the 9 taps of the function it computes."""
     flops = 2 * d.N * d.OH * d.OW * d.Cout * d.KH * d.KW * d.Cin
     sh, sw = (d.H // 2, d.W // 2) if d.upsample else (d.H, d.W)
     nbytes = esize * (d.N * sh * sw * d.Cin + d.Cout * d.KH * d.KW * d.Cin + d.N * d.OH * d.OW * d.Cout)
@@ -444,9 +445,27 @@ def conv_desc(n, h, w, cin, cout, kh, kw, stride, pad_t, pad_l, oh, ow, upsample
     return ConvDesc(n, h, w, cin, oh, ow, cout, kh, kw, stride, pad_t, pad_l, int(upsample), dt(dtype), impl)
 
 
-def pack_weight(master_oihw, cin_p, cout_p, dtype, want_w=True, want_wt=True):
+PACK_OHWI, PACK_SUBPIXEL = 256, 512      # bits 8 / 9 of dvq_pack_weight's dtype (include/dvq_hip.h)
+
+
+def subpixel_pack_views(wbuf, wtbuf, cout, cin):
+    """flat pack buffers of a sub-pixel-eligible 3x3 conv -> (w [Cout,3,3,Cin], wt [Cin,3,3,Cout], Weff [4,Cout,4,Cin],
+    WeffT [Cin,4,4,Cout]): the sub-pixel packs sit behind the 3x3 packs, the layout dvq_conv2d_fwd / _dgrad read with upsample == 2"""
+    n9 = cout * 9 * cin
+    return (wbuf[:n9].view(cout, 3, 3, cin), wtbuf[:n9].view(cin, 3, 3, cout), wbuf[n9:].view(4, cout, 4, cin),
+            wtbuf[n9:].view(cin, 4, 4, cout))
+
+
+def pack_weight(master_oihw, cin_p, cout_p, dtype, want_w=True, want_wt=True, subpixel=False):
+    """subpixel: flat (w | Weff) and (wt | WeffT) buffers, see subpixel_pack_views"""
     cout, cin, kh, kw = master_oihw.shape
     dev = master_oihw.device
+    if subpixel:
+        w = torch.empty(25 * cout * cin, dtype=dtype, device=dev)
+        wt = torch.empty(25 * cout * cin, dtype=dtype, device=dev)
+        check(lib().dvq_pack_weight(_p(master_oihw), cout, cin, kh, kw, cin_p, cout_p, dt(dtype) | PACK_SUBPIXEL, _p(w), _p(wt), _s()),
+              "dvq_pack_weight")
+        return w, wt
     w = torch.empty(cout, kh, kw, cin_p, dtype=dtype, device=dev) if want_w else None
     wt = torch.zeros(cin_p, kh, kw, cout_p, dtype=dtype, device=dev) if want_wt else None   # rows >= Cin stay zero
     check(lib().dvq_pack_weight(_p(master_oihw), cout, cin, kh, kw, cin_p, cout_p, dt(dtype), _p(w), _p(wt), _s()),
@@ -454,9 +473,9 @@ def pack_weight(master_oihw, cin_p, cout_p, dtype, want_w=True, want_wt=True):
     return w, wt
 
 
-def pack_weight_into(master, cin_p, cout_p, dtype, w, wt):
+def pack_weight_into(master, cin_p, cout_p, dtype, w, wt, subpixel=False):
     cout, cin, kh, kw = master.shape
-    flag = dt(dtype) | (256 if is_ohwi(master) else 0)
+    flag = dt(dtype) | (PACK_OHWI if is_ohwi(master) else 0) | (PACK_SUBPIXEL if subpixel else 0)
     check(lib().dvq_pack_weight(_praw(master), cout, cin, kh, kw, cin_p, cout_p, flag, _p(w), _p(wt), _s()),
           "dvq_pack_weight")
 
@@ -470,6 +489,18 @@ def conv_fused_ok(d: ConvDesc) -> bool:
     return bool(lib().dvq_conv3x3_fused_ok(C.byref(d)))
 
 
+def conv_subpixel_ok(d: ConvDesc) -> bool:
+    """a folded nearest-x2 upsample + 3x3 that the library runs as four 2x2 sub-pixel convolutions when handed the sub-pixel packs"""
+    return bool(lib().dvq_conv3x3_subpixel_ok(C.byref(d)))
+
+
+def _with_subpixel(d: ConvDesc) -> ConvDesc:
+    """the descriptor with upsample = 2: the weight argument carries the sub-pixel pack behind its 3x3 pack"""
+    d2 = ConvDesc.from_buffer_copy(d)
+    d2.upsample = 2
+    return d2
+
+
 ACT_NONE, ACT_SWISH, ACT_LRELU, ACT_RELU = 0, 1, 2, 3      # include/dvq_hip.h DVQ_ACT_*
 
 
@@ -480,7 +511,8 @@ def _x3_halo(d: ConvDesc, t, dgrad: bool) -> bool:
             bool(lib().dvq_fp32_split()) and bool(lib().dvq_conv3x3_x3_ok(C.byref(d), int(dgrad))))
 
 
-def conv2d_fwd(d: ConvDesc, x, w, bias, residual=None, gn_ss=None, out_stats=None, out_groups=0, act=ACT_NONE):
+def conv2d_fwd(d: ConvDesc, x, w, bias, residual=None, gn_ss=None, out_stats=None, out_groups=0, act=ACT_NONE, subpixel=False):
+    """subpixel: `w` is followed by the sub-pixel pack (subpixel_pack_views) and d is accepted by conv_subpixel_ok"""
     y = torch.empty(d.N, d.OH, d.OW, d.Cout, dtype=x.dtype, device=x.device)
     fl, nb = _conv_cost(d, x.element_size())
     if gn_ss is None and out_stats is None and _x3_halo(d, x, False):
@@ -496,16 +528,19 @@ def conv2d_fwd(d: ConvDesc, x, w, bias, residual=None, gn_ss=None, out_stats=Non
              ("+st" if out_stats is not None else "") + ("+act" if act != ACT_NONE else ""))
     if out_stats is not None:
         ensure_workspace(x.device)        # per-tile statistics partials of the halo kernel
+    dc = _with_subpixel(d) if subpixel else d
     _timed_conv(fl, nb, "dvq_conv2d_fwd", lambda:
-        lib().dvq_conv2d_fwd(C.byref(d), _p(x), _p(w), _p(bias), _p(residual), _p(y), _p(gn_ss), _p(out_stats), out_groups, act, _s()))
+        lib().dvq_conv2d_fwd(C.byref(dc), _p(x), _p(w), _p(bias), _p(residual), _p(y), _p(gn_ss), _p(out_stats), out_groups, act, _s()))
     return y
 
 
-def conv2d_dgrad(d: ConvDesc, dy, wt, mask=None, mask_act=ACT_NONE):
-    """mask: output of the activation that produced this conv's input; the gradient is gated through it"""
+def conv2d_dgrad(d: ConvDesc, dy, wt, mask=None, mask_act=ACT_NONE, subpixel=False):
+    """mask: output of the activation that produced this conv's input; the gradient is gated through it.
+    subpixel: `wt` is followed by the sub-pixel pack and d is accepted by conv_subpixel_ok -- the gradient of a folded upsample is
+    then formed at the stored resolution, without the full-resolution workspace"""
     sh, sw = (d.H // 2, d.W // 2) if d.upsample else (d.H, d.W)
     dx = torch.empty(d.N, sh, sw, d.Cin, dtype=dy.dtype, device=dy.device)
-    ws = torch.empty(d.N, d.H, d.W, d.Cin, dtype=dy.dtype, device=dy.device) if d.upsample else None
+    ws = torch.empty(d.N, d.H, d.W, d.Cin, dtype=dy.dtype, device=dy.device) if d.upsample and not subpixel else None
     fl, nb = _conv_cost(d, dy.element_size())
     if _x3_halo(d, dy, True):
         _tag(d, "dgrad x3 halo")
@@ -516,8 +551,9 @@ def conv2d_dgrad(d: ConvDesc, dy, wt, mask=None, mask_act=ACT_NONE):
             "dvq_conv2d_dgrad_x3"))
         return dx
     _tag(d, "dgrad")
+    dc = _with_subpixel(d) if subpixel else d
     _timed_conv(fl, nb, "dvq_conv2d_dgrad", lambda:
-        lib().dvq_conv2d_dgrad(C.byref(d), _p(dy), _p(wt), _p(dx), _p(ws), _p(mask), mask_act, _s()))
+        lib().dvq_conv2d_dgrad(C.byref(dc), _p(dy), _p(wt), _p(dx), _p(ws), _p(mask), mask_act, _s()))
     return dx
 
 

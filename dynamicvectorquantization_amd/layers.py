@@ -503,12 +503,21 @@ class Conv2d(HipModule):
         """persistent packed buffers (stable device pointers: the multi-tensor pack table refers to them)"""
         cin_p, cout_p = self._padded(dtype)
         k, dev = self.kernel_size, self.weight.device
-        w = torch.zeros(cout_p, k, k, cin_p, dtype=dtype, device=dev)          # rows >= Cout stay zero
-        wt = torch.zeros(cin_p, k, k, cout_p, dtype=dtype, device=dev)                # rows >= Cin stay zero (dgrad reads cin_p rows)
+        # a folded upsample whose channel counts the library runs as four 2x2 sub-pixel convolutions (asked on the smallest eligible
+        # image: the spatial conditions are checked per call) carries the sub-pixel packs behind its 3x3 packs, in the same buffers
+        sub = bool(self.upsample and k == 3 and self.stride == 1 and self.padding == 1 and not self.asym_pad and
+                   K.conv_subpixel_ok(K.conv_desc(1, 16, 64, cin_p, cout_p, 3, 3, 1, 1, 1, 16, 64, True, dtype)))
+        if sub:
+            w, wt, _, _ = K.subpixel_pack_views(torch.zeros(25 * cout_p * cin_p, dtype=dtype, device=dev),
+                                                torch.zeros(25 * cout_p * cin_p, dtype=dtype, device=dev), cout_p, cin_p)
+        else:
+            w = torch.zeros(cout_p, k, k, cin_p, dtype=dtype, device=dev)          # rows >= Cout stay zero
+            wt = torch.zeros(cin_p, k, k, cout_p, dtype=dtype, device=dev)                # rows >= Cin stay zero (dgrad reads cin_p rows)
         bias = None
         if self.bias is not None and cout_p != self.out_channels:
             bias = torch.zeros(cout_p, dtype=torch.float32, device=dev)
-        ent = {"epoch": -1, "w": w, "wt": wt, "bias": bias, "cin_p": cin_p, "cout_p": cout_p, "master": self.weight.data_ptr()}
+        ent = {"epoch": -1, "w": w, "wt": wt, "bias": bias, "cin_p": cin_p, "cout_p": cout_p, "master": self.weight.data_ptr(),
+               "sub": sub}
         self._packs[dtype] = ent
         PACKS.register(self, dtype)
         return ent
@@ -529,7 +538,7 @@ class Conv2d(HipModule):
                 # ONE launch refreshes every registered conv of this dtype / device / optimizer group
                 PACKS.repack(dtype, self.weight.device, getattr(self.weight, "_dvq_group", 0))
             if ent["epoch"] != ep:                       # not covered by the table yet (first use)
-                K.pack_weight_into(self.weight.detach(), ent["cin_p"], ent["cout_p"], dtype, ent["w"], ent["wt"])
+                K.pack_weight_into(self.weight.detach(), ent["cin_p"], ent["cout_p"], dtype, ent["w"], ent["wt"], subpixel=ent["sub"])
                 ent["epoch"] = ep
         if ent["bias"] is not None and ent.get("bias_epoch") != ep:
             # zero-padded bias copy (Cout not a multiple of the vector width): tracked on its own -- the multi-tensor
@@ -554,6 +563,11 @@ class Conv2d(HipModule):
         assert x.shape[-1] == cin_p, f"expected {cin_p} (padded) input channels, got {x.shape[-1]}"
         return K.conv_desc(n, h, w, cin_p, cout_p, k, k, s, pt, pl, oh, ow, self.upsample, x.dtype, rt.impl())
 
+    def _subpixel(self, d, dtype) -> bool:
+        """this call runs as four 2x2 sub-pixel convolutions: the packs are there and the library takes the shape"""
+        ent = self._packs.get(dtype)
+        return bool(self.upsample and ent is not None and ent["sub"] and K.conv_subpixel_ok(d))
+
     def fused_ok(self, x) -> bool:
         """True if this call runs on the halo kernels, which can apply GroupNorm+swish to their input tile and emit
         the GroupNorm statistics of their output"""
@@ -570,7 +584,8 @@ class Conv2d(HipModule):
         stats = None
         if want_stats and self.out_channels % 32 == 0 and 128 % (self.out_channels // 32) == 0 and self.fused_ok(x):
             stats = K.zeros_small((d.N, 32, 2), torch.float64, x.device)
-        y = K.conv2d_fwd(d, x, w, bias, residual, gn_ss=gn_ss, out_stats=stats, out_groups=32 if stats is not None else 0)
+        y = K.conv2d_fwd(d, x, w, bias, residual, gn_ss=gn_ss, out_stats=stats, out_groups=32 if stats is not None else 0,
+                         subpixel=self._subpixel(d, x.dtype))
         if stats is not None:
             y._gn_stats = stats            # consumed by the next Normalize (saves its statistics pass)
         if tape is not None:
@@ -588,7 +603,7 @@ class Conv2d(HipModule):
             # follows the input gradient on this stream -- the HBM-bound GroupNorm backward -- instead of beside the input
             # gradient itself, which wants the same matrix pipes
             _, wt, _ = self.packed(x.dtype)
-            dx = K.conv2d_dgrad(d, dy, wt, mask=mask, mask_act=mask_act)
+            dx = K.conv2d_dgrad(d, dy, wt, mask=mask, mask_act=mask_act, subpixel=self._subpixel(d, x.dtype))
         if need_dw:
             db = _grad_buf(self.bias) if self.bias is not None else None
             # weight / bias gradients are accumulated by the kernel straight into the reference-layout .grad buffers
@@ -603,7 +618,7 @@ class Conv2d(HipModule):
         if dx is not None:
             return dx
         _, wt, _ = self.packed(x.dtype)
-        return K.conv2d_dgrad(d, dy, wt, mask=mask, mask_act=mask_act)
+        return K.conv2d_dgrad(d, dy, wt, mask=mask, mask_act=mask_act, subpixel=self._subpixel(d, x.dtype))
 
 
 def conv1x1_bwd_accumulate(conv, dy, tape, acc):
@@ -668,8 +683,11 @@ class _PackRegistry:
                 e = m._packs[dtype]
                 k2 = m.kernel_size * m.kernel_size
                 arr[i] = PackEntry(m.weight.data_ptr(), e["w"].data_ptr(), e["wt"].data_ptr(), m.out_channels, m.in_channels,
-                                   k2, e["cin_p"], e["cout_p"], begin, K.dt(dtype) | (256 if K.is_ohwi(m.weight) else 0))
+                                   k2, e["cin_p"], e["cout_p"], begin, K.dt(dtype) | (K.PACK_OHWI if K.is_ohwi(m.weight) else 0) |
+                                   (K.PACK_SUBPIXEL if e["sub"] else 0))
                 begin += m.out_channels * k2 * e["cin_p"] + m.in_channels * k2 * e["cout_p"]
+                if e["sub"]:
+                    begin += 32 * m.out_channels * m.in_channels
             raw = torch.frombuffer(bytearray(bytes(arr)), dtype=torch.uint8).to(device)
             tab = {"sig": sig, "table": raw, "n": len(live), "total": begin}
             if key in self.tables:

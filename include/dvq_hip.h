@@ -46,7 +46,9 @@ const char* dvq_last_error(void);
  * written in csrc ("conv3x3_halo_kernel", "conv_nt_pipe_kernel", ...; no template arguments, no fold / reduce / transpose helpers), noted
  * at the dispatch branch that launches it.  "" when nothing was noted (those entry points clear it first).  For timing labels. */
 const char* dvq_last_kernel(void);
-int dvq_version(void);     /* 119: dvq_scalar_push (+ dvq_scalar_push_state_bytes), dvq_codebook_health (training metric logs);
+int dvq_version(void);     /* 120: dvq_conv3x3_subpixel_ok, dvq_conv_desc.upsample == 2, bit 9 of the weight packs' dtype (nearest x2 + 3x3 convolutions
+                            * as four 2x2 sub-pixel convolutions, forward and input gradient);
+                            * 119: dvq_scalar_push (+ dvq_scalar_push_state_bytes), dvq_codebook_health (training metric logs);
                             * 118: dvq_unordered_launches; dvq_set_deterministic orders every floating-point reduction of a training step;
                             * 117: DVQ_IMPL_* names for the impl codes; one entry per convolution / GEMM pass (dvq_conv2d_fwd, _dgrad, _wgrad, dvq_gemm_tn
                             * take the arguments of their former _ex / _act / _mask / _oihw / _colsum variants; dvq_gemm_nt_res is gone);
@@ -215,7 +217,9 @@ typedef struct dvq_conv_desc {
     int32_t KH, KW;
     int32_t stride;
     int32_t pad_t, pad_l; /* zero padding top/left; bottom/right padding is implied by OH/OW */
-    int32_t upsample; /* 1: the stored input is [N,H/2,W/2,Cin] and is read through nearest x2 (model.py:50) */
+    int32_t upsample; /* 1: the stored input is [N,H/2,W/2,Cin] and is read through nearest x2 (model.py:50);
+                       * 2 (dvq_conv2d_fwd / dvq_conv2d_dgrad only, shapes accepted by dvq_conv3x3_subpixel_ok): the same, and the
+                       * weight argument carries the sub-pixel pack behind its 3x3 pack (dvq_pack_weight, bit 9 of dtype) */
     int32_t dtype;    /* DVQ_F32 / DVQ_BF16: activations and packed weights */
     int32_t impl;     /* DVQ_IMPL_*: AUTO, NAIVE, MFMA, REGSTAGE, HALO, CONV_PIPE (DVQ_ESHAPE if the shape is not eligible) */
 } dvq_conv_desc;
@@ -236,6 +240,16 @@ enum { DVQ_ACT_NONE = 0, DVQ_ACT_SWISH = 1, DVQ_ACT_LRELU = 2, DVQ_ACT_RELU = 3 
  * out_stats (fp64 [N][out_groups][2], accumulated) receives sum / sum of squares of the OUTPUT per group, i.e. the
  * statistics pass of the next GroupNorm.  Either may be NULL. */
 int dvq_conv3x3_fused_ok(const dvq_conv_desc* d);
+/* Nearest x2 upsample + 3x3 as four 2x2 sub-pixel convolutions.  The upsampled image holds every source pixel four times, so an output
+ * pixel of parity class (py, px) reads 2 x 2 distinct source pixels: out[2i+py][2j+px] = sum_{a,b in {0,1}} Weff[py][px][a][b] .
+ * x[i+a+py-1][j+b+px-1], with Weff the sums of the 3x3 taps that land on the same source pixel (rows: py = 0: a = 0 <- {0}, a = 1 <-
+ * {1, 2}; py = 1: a = 0 <- {0, 1}, a = 1 <- {2}; columns alike), summed in fp32 and rounded once: 4/9 of the multiply-adds, and an
+ * input gradient that is formed at the low resolution (no workspace, no 2x2 sum pass).  Results are within bf16 rounding of the 9-tap
+ * form, not bit-identical to it.  dvq_conv3x3_subpixel_ok: 1 for descriptors with upsample != 0 that dvq_conv2d_fwd (without residual,
+ * gn_scale_shift or activation; with them it runs the 9-tap form on the 3x3 pack) and dvq_conv2d_dgrad run this way when upsample == 2:
+ * bf16, 3x3 / stride 1 / pad 1, (H/2) % 8 == 0, (W/2) % 32 == 0, Cin % 64 == 0, Cout % 64 == 0, impl AUTO or HALO.  The weight
+ * gradient, fp32 and fp32x3 keep upsample == 1. */
+int dvq_conv3x3_subpixel_ok(const dvq_conv_desc* d);
 int dvq_conv2d_fwd(const dvq_conv_desc* d, const void* x, const void* w, const float* bias, const void* residual, void* y,
                    const float* gn_scale_shift, double* out_stats, int out_groups, int act, dvq_stream_t stream);
 /* fp32x3 weight gradient (dvq_set_fp32_split) at launch level: x / dy fp32 (descriptor dtype DVQ_F32, channels padded to 4) are split
@@ -266,8 +280,8 @@ int dvq_gn_scale_shift(const double* stats, const float* gamma, const float* bet
 
 /* dx (stored-input shape, i.e. [N,H/2,W/2,Cin] when upsample) from dy [N,OH,OW,Cout].
  * wt: weights in IHWO layout [d->Cin,KH,KW,Cout] of `dtype` (dvq_pack_weight writes the first Cin_real rows; when the
- * descriptor's Cin is channel-padded the caller provides zero rows up to d->Cin).  When upsample is set,
- * ws must hold N*H*W*Cin elements of `dtype` (gradient at the upsampled resolution).
+ * descriptor's Cin is channel-padded the caller provides zero rows up to d->Cin).  When upsample is 1,
+ * ws must hold N*H*W*Cin elements of `dtype` (gradient at the upsampled resolution); with upsample == 2 ws is not used (may be NULL).
  * mask (may be NULL): dgrad through the conv AND the activation that produced the conv's input: mask = that activation's OUTPUT
  * (same shape as dx); dx = dgrad * (mask > 0 ? 1 : slope(mask_act)), mask_act DVQ_ACT_RELU / _LRELU, no folded upsample. */
 int dvq_conv2d_dgrad(const dvq_conv_desc* d, const void* dy, const void* wt, void* dx, void* ws, const void* mask, int mask_act,
@@ -300,7 +314,11 @@ int dvq_linear_pack_multi(const void* table_dev, int64_t n_entries, int64_t tota
 
 /* weight packing: master fp32 OIHW (the reference's nn.Conv2d parameter layout) -> `dtype`
  * w [Cout][KH][KW][Cin_p] (forward / wgrad layout) and wt [Cin][KH][KW][Cout_p] (dgrad layout), zero padded
- * to Cin_p / Cout_p channels (multiples of 8 for bf16, 4 for fp32); either output may be NULL. */
+ * to Cin_p / Cout_p channels (multiples of 8 for bf16, 4 for fp32); either output may be NULL.
+ * Bit 9 of dtype (3x3 kernels, Cin_p == Cin, Cout_p == Cout, both outputs given; the table entries of dvq_pack_weights_multi alike,
+ * whose `begin` then counts 16*Cout*Cin more elements per output): the sub-pixel packs of dvq_conv3x3_subpixel_ok are written BEHIND
+ * the 3x3 packs -- Weff [class 2py+px][Cout][tap 2a+b][Cin] at w + Cout*9*Cin and WeffT [Cin][class][tap][Cout] at wt + Cin*9*Cout,
+ * each element the fp32 sum of its group's taps (rows then columns, ascending) rounded once. */
 int dvq_pack_weight(const float* master, int64_t Cout, int64_t Cin, int64_t KH, int64_t KW, int64_t Cin_p,
                     int64_t Cout_p, int dtype, void* w, void* wt, dvq_stream_t stream);
 /* grad_oihw[co][ci][kh][kw] += dw[co][kh][kw][ci]   (dw: the fp32 [Cout][KH][KW][Cin_p] output of wgrad) */
