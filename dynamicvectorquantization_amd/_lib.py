@@ -6,8 +6,7 @@ import ctypes as C
 import os
 
 HERE = os.path.dirname(os.path.abspath(__file__))
-# DVQ_USE_PROBES_LIB=1 (tools/debug/ only): the -DDVQ_PROBES build with the wrong-result timing experiments (build.py --probes)
-LIB_PATH = os.path.join(HERE, "libdvq_hip_probes.so" if os.environ.get("DVQ_USE_PROBES_LIB", "0") == "1" else "libdvq_hip.so")
+LIB_PATH = os.path.join(HERE, "libdvq_hip.so")
 
 F32, BF16 = 0, 1
 # DVQ_IMPL_* of include/dvq_hip.h: kernel choice of ConvDesc.impl, dvq_gemm_nt and dvq_gemm_tn
@@ -97,7 +96,6 @@ SIGNATURES = {
     "dvq_cmdlist_replay": (i32, [vp, vp, vp]),
     "dvq_cmdlist_info": (i32, [vp, vp]),
     "dvq_cmdlist_destroy": (i32, [vp]),
-    "dvq_halo_trace_read": (i32, [vp, i64]),
     "dvq_permute_dual": (i32, [vp, vp, i64, i32, i32, i32, i64, i64, i64, i64, i64, i64, vp, vp, vp, vp, vp, vp]),
     "dvq_permute_dual_back": (i32, [vp, vp, vp, vp, i64, i64, i64, i32, i32, i64, i64, vp, vp]),
     "dvq_avgpool_slice": (i32, [vp, i32, i64, i64, i64, i64, i32, vp, i64, i64, vp]),

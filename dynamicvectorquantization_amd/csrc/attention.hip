@@ -43,8 +43,6 @@ struct AttnParams {
     float scale;                             // 1 / sqrt(hs)
     float inv_keep;                          // 1 / (1 - p)
     unsigned thr, rm, ra;                    // dropout: keep iff dvq_hash32(idx * rm + ra) >= thr (thr == 0: no dropout)
-    int dbg;                                 // DVQ_ATTN_DBG (timing experiments on the dQ kernel, results wrong): 1 no tile refills,
-                                             //    2 no element-wise pass, 4 no second GEMM, 8 no first GEMMs
     unsigned long long* mask;                // optional keep-decision words, [B * nh][nqt][nkt][16] (see drop_tile): written by the
                                              //    forward, read by the backward kernels instead of hashing every element again
 };
@@ -290,28 +288,6 @@ __global__ __launch_bounds__(256, 2) void attn_fwd_kernel(AttnParams p) {
     }
 }
 
-// dsum[b][h][t] = sum_ch dO * O    (one thread per (row, head))
-template <int HS>
-__global__ __launch_bounds__(256) void attn_rowdot_kernel(AttnParams p, int64_t rows) {
-    const int64_t e = (int64_t)blockIdx.x * 256 + threadIdx.x;
-    if (e >= rows * p.nh) return;
-    const int h = (int)(e % p.nh);
-    const int64_t row = e / p.nh;                                // b * T + t
-    const int64_t b = row / p.T, t = row - b * p.T;
-    const bf16_t* a = p.dout + row * p.C + h * HS;
-    const bf16_t* o = p.o + row * p.C + h * HS;
-    float acc = 0.f;
-#pragma unroll
-    for (int c = 0; c < HS; c += 8) {
-        float x[8], y[8];
-        load8(a + c, x);
-        load8(o + c, y);
-#pragma unroll
-        for (int j = 0; j < 8; ++j) acc = fmaf(x[j], y[j], acc);
-    }
-    p.dsum[(b * p.nh + h) * p.T + t] = acc;
-}
-
 // ------------------------------------------------------------------------------------------------------------------
 // backward, dQ: one wave per 32 queries (same walk as the forward); LDS stage = K, V (row-major) and K^T tiles
 // ------------------------------------------------------------------------------------------------------------------
@@ -345,9 +321,7 @@ __global__ __launch_bounds__(256, 2) void attn_bwd_dq_kernel(AttnParams p) {
     // dsum[query] = sum_ch dO * O: taken here from the dO fragments this wave holds anyway (+ the matching O fragments) and left in
     // p.dsum for the dK kernel, which is launched after this one (a separate one-thread-per-row pass over dO and O was 38 us per layer)
     float dq_ = 0.f;
-    if (p.dbg & 16) {                                            // (DVQ_ATTN_DBG=16: A/B against the separate pass)
-        dq_ = qok ? p.dsum[(int64_t)bh * T + qrow] : 0.f;
-    } else {
+    {
         const bf16_t* op = p.o + (rowbase + qrow) * C + h * HS + 8 * half;
 #pragma unroll
         for (int s = 0; s < NS; ++s) {
@@ -386,7 +360,7 @@ __global__ __launch_bounds__(256, 2) void attn_bwd_dq_kernel(AttnParams p) {
         const char* kl = smem + (kt & 1) * STAGE;
         const char* vl = kl + G::RTILE;
         const char* tl = kl + 2 * G::RTILE;
-        const bool more = kt < kt_last && !(p.dbg & 1);
+        const bool more = kt < kt_last;
         if (more) {
             gload_rows<HS>(kbase, rowbase, 32 * (kt + 1), T, C, tid, rk);
             gload_rows<HS>(vbase, rowbase, 32 * (kt + 1), T, C, tid, rv);
@@ -401,12 +375,10 @@ __global__ __launch_bounds__(256, 2) void attn_bwd_dq_kernel(AttnParams p) {
                 for (int r = 0; r < 16; ++r) mk[r] = mw[r];
             }
             f32x16 s = zero16(), dp = zero16();
-            if (!(p.dbg & 8)) {
 #pragma unroll
-                for (int st = 0; st < NS; ++st) {
-                    s = MFMA(frag_r<HS>(kl, l31, half, st), qf[st], s);
-                    dp = MFMA(frag_r<HS>(vl, l31, half, st), dof[st], dp);
-                }
+            for (int st = 0; st < NS; ++st) {
+                s = MFMA(frag_r<HS>(kl, l31, half, st), qf[st], s);
+                dp = MFMA(frag_r<HS>(vl, l31, half, st), dof[st], dp);
             }
             const bool diag = p.causal && kt == qt;
             auto elementwise = [&](auto diag_c) {
@@ -425,23 +397,13 @@ __global__ __launch_bounds__(256, 2) void attn_bwd_dq_kernel(AttnParams p) {
                     s[r] = pr * (g - dq_);                        // d loss / d (scaled score)
                 }
             };
-            if (p.dbg & 2) {
+            if (diag) elementwise(std::true_type{});
+            else elementwise(std::false_type{});
 #pragma unroll
-                for (int r = 0; r < 16; ++r) s[r] += dp[r];
-            } else {
-                if (diag) elementwise(std::true_type{});
-                else elementwise(std::false_type{});
-            }
-            if (p.dbg & 4) {
+            for (int s2 = 0; s2 < 2; ++s2) {
+                const bf16x8 df = pack8(s, s2);
 #pragma unroll
-                for (int r = 0; r < 16; ++r) acc[0][r] += s[r];
-            } else {
-#pragma unroll
-                for (int s2 = 0; s2 < 2; ++s2) {
-                    const bf16x8 df = pack8(s, s2);
-#pragma unroll
-                    for (int mt = 0; mt < NM; ++mt) acc[mt] = MFMA(frag_c<HS>(tl, l31, half, mt, s2), df, acc[mt]);
-                }
+                for (int mt = 0; mt < NM; ++mt) acc[mt] = MFMA(frag_c<HS>(tl, l31, half, mt, s2), df, acc[mt]);
             }
         }
         if (more) {
@@ -618,9 +580,8 @@ int launch_fwd(const AttnParams& p, dim3 grid, hipStream_t stream) {
 }
 
 template <int HS, bool MASKED>
-int launch_bwd_m(const AttnParams& p, dim3 grid, int64_t rows, hipStream_t stream) {
+int launch_bwd_m(const AttnParams& p, dim3 grid, hipStream_t stream) {
     using G = Geo<HS>;
-    if (p.dbg & 16) attn_rowdot_kernel<HS><<<dim3((unsigned)cdiv64(rows * p.nh, 256)), dim3(256), 0, stream>>>(p, rows);
     const int lds_kv = 2 * (2 * G::RTILE + 2 * G::CTILE), lds_q = 2 * (2 * G::RTILE + G::CTILE);
     dvq_ensure_dynamic_lds((const void*)attn_bwd_dq_kernel<HS, MASKED>, lds_q);
     attn_bwd_dq_kernel<HS, MASKED><<<grid, dim3(256), lds_q, stream>>>(p);        // first: it also produces dsum for the dK kernel
@@ -629,9 +590,9 @@ int launch_bwd_m(const AttnParams& p, dim3 grid, int64_t rows, hipStream_t strea
     return 0;
 }
 template <int HS>
-int launch_bwd(const AttnParams& p, dim3 grid, int64_t rows, hipStream_t stream) {
-    if (p.thr != 0 && p.mask != nullptr) return launch_bwd_m<HS, true>(p, grid, rows, stream);
-    return launch_bwd_m<HS, false>(p, grid, rows, stream);
+int launch_bwd(const AttnParams& p, dim3 grid, hipStream_t stream) {
+    if (p.thr != 0 && p.mask != nullptr) return launch_bwd_m<HS, true>(p, grid, stream);
+    return launch_bwd_m<HS, false>(p, grid, stream);
 }
 
 // geometry the fused kernels take, stated once: fill_params (every entry point) and the exported predicates dvq_attn_causal_ok /
@@ -660,8 +621,6 @@ int fill_params(AttnParams& p, const char* who, int dtype, int64_t B, int64_t T,
     p.inv_keep = 1.f / (1.f - p_drop);
     p.thr = (unsigned)((double)p_drop * 4294967296.0);
     dvq_dropout_seed(seed, &p.rm, &p.ra);
-    static const int dbg = dvq_probe_env("DVQ_ATTN_DBG");           // 0 unless built with -DDVQ_PROBES
-    p.dbg = dbg;
     return DVQ_OK;
 }
 
@@ -793,7 +752,7 @@ static int attn_causal_bwd_impl(const void* q, const void* k, const void* v, int
     if ((rc = dvq_transpose(k, dtype, B, T, p.C, kt, stream)) != DVQ_OK) return rc;
     if ((rc = dvq_transpose(dout, dtype, B, T, p.C, dot, stream)) != DVQ_OK) return rc;
     const int nt = (int)((T + 31) / 32);
-    launch_bwd<64>(p, dim3((unsigned)((nt + 3) / 4), (unsigned)(B * n_head)), B * T, (hipStream_t)stream);
+    launch_bwd<64>(p, dim3((unsigned)((nt + 3) / 4), (unsigned)(B * n_head)), (hipStream_t)stream);
     DVQ_CHECK_LAUNCH("attn_causal_bwd");
     return DVQ_OK;
 }

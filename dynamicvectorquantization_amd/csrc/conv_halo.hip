@@ -51,18 +51,12 @@ struct HaloParams {
     float act_slope;     // output activation v > 0 ? v : act_slope * v (1: none, 0: ReLU, 0.2: LeakyReLU), applied last
     int res_mask;        // 1: R is not added but gates the result: v *= (R > 0 ? 1 : mask_slope)  (backward of ReLU / LeakyReLU)
     float mask_slope;
-    int dbg;             // profiling experiments only (DVQ_HALO_DBG): 1 = skip the epilogue, 2 = skip the MFMA loop, 6 = per-workgroup
-                         //   time stamps (tools/debug/halo_trace.py)
     int nt_out;          // 1: the output tensor is larger than the Infinity Cache -- nontemporal stores (DVQ_HALO_NT=0: never)
     int mfma_stats;      // 1: output statistics on the matrix pipe where the epilogue supports it (DVQ_HALO_MFMA_STATS=0: vector path)
     int nt_in;           // 1: the same for the input halo loads, when one workgroup column covers all output channels (DVQ_HALO_NT_IN)
     int nblocks;         // N * tiles_y * tiles_x * gn
     unsigned mg_gn, mg_tx, mg_ty;      // fdiv_u32 magics of gn, tiles_x, tiles_y
 };
-
-// DVQ_HALO_DBG=6: per workgroup {CU key, start, end of the main loop, end, ...} in 10-ns ticks (dvq_halo_trace_read)
-constexpr int HALO_TRACE_MAX = 32768;
-__device__ unsigned long long g_halo_trace[HALO_TRACE_MAX][6];
 
 // n / d for n * d < 2^32 with magic = ceil(2^32 / d) (0 encodes d == 1): scalar-unit arithmetic (s_mul_hi_u32) instead of the float
 // division sequence the compiler emits for a runtime divisor -- VALU instructions are what a workgroup pays dearly for outside its
@@ -83,8 +77,8 @@ constexpr int VOFF_OOB = 0x7ffffff0;            // beyond every descriptor's ran
 //
 // Prologue and epilogue are written for the FEWEST VECTOR-ALU INSTRUCTIONS, not the fewest cycles: they run beside the CU
 // neighbour's main loop, and while that wave keeps the SIMD's matrix pipe busy another wave's VALU instruction issues only once
-// per MFMA -- ~36 cycles each instead of 4 (tools/debug/valu_under_mfma.hip; DVQ_HALO_DBG=6 traces showed the 700-instruction
-// staging of the round-2 epilogue taking 11 us per tile).  Hence: the tile decode runs on the scalar unit, the halo offsets are
+// per MFMA -- ~36 cycles each instead of 4 (tools/debug/valu_under_mfma.hip; the per-workgroup traces of docs/design/03b showed
+// the 700-instruction staging of the round-2 epilogue taking 11 us per tile).  Hence: the tile decode runs on the scalar unit, the halo offsets are
 // computed once per tile (not per channel chunk), the accumulators start from the bias (LDS reads, no adds later), a no-op
 // activation is skipped, staging and store addresses are lane constants + immediate / scalar offsets (buffer stores through a
 // per-image descriptor), the GroupNorm statistics use v_dot2_f32_bf16 on channel PAIRS (2 instead of 6 instructions per dword).
@@ -105,7 +99,7 @@ constexpr int VOFF_OOB = 0x7ffffff0;            // beyond every descriptor's ran
 //   SUB = 2, input gradient: the contraction runs over 4 x Cin / 64 chunks, a chunk belongs to one class: its halo is the class's pixels
 //     (2 gy + py, 2 gx + px) of dY, its taps sit at the mirrored offsets (2 - py - (t >> 1), 2 - px - (t & 1)).  The low-resolution
 //     gradient leaves the kernel from ONE fp32 accumulation: no full-resolution workspace, no 2 x 2 sum pass.
-template <int NT, bool TRACE = false, bool OUT32 = false, int SUB = 0>
+template <int NT, bool OUT32 = false, int SUB = 0>
 __global__ __launch_bounds__(256, 2) void conv3x3_halo_kernel(HaloParams p) {
 #if defined(__HIP_DEVICE_COMPILE__)      // (buffer-descriptor builtins exist in the device pass only; the host pass needs just the stub)
     constexpr int NW = 4, MT = 2, NTH = 256;
@@ -114,7 +108,7 @@ __global__ __launch_bounds__(256, 2) void conv3x3_halo_kernel(HaloParams p) {
     constexpr int ROWS = CO_T * 2;      // bytes of a staged output row
     constexpr int SWZ_SH = CPRW == 16 ? 0 : CPRW == 8 ? 1 : 2;
     constexpr int NTAPS = SUB ? 4 : 9;  // taps the loop walks per channel chunk
-    static_assert(SUB == 0 || (!OUT32 && !TRACE), "sub-pixel forms: bf16 output only");
+    static_assert(SUB == 0 || !OUT32, "sub-pixel forms: bf16 output only");
     extern __shared__ __attribute__((aligned(16))) char smem[];
     char* halo = smem;
     char* bst = smem + HALOB;
@@ -124,14 +118,6 @@ __global__ __launch_bounds__(256, 2) void conv3x3_halo_kernel(HaloParams p) {
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
     const int wm = wave;                // wave row: image rows MT * wm ..
     const int l31 = lane & 31, half = lane >> 5;
-
-    unsigned long long tr[5] = {0, 0, 0, 0, 0};
-    unsigned tr_key = 0;
-    if constexpr (TRACE) {
-        const unsigned hw = __builtin_amdgcn_s_getreg((31 << 11) | 4), xcc = __builtin_amdgcn_s_getreg((31 << 11) | 20);
-        tr_key = ((xcc & 15u) << 8) | ((hw >> 8) & 0xffu);
-        tr[0] = wall_clock64();
-    }
 
     // ---- tile decode (scalar) ----
     unsigned wi = (unsigned)xcd_remap(blockIdx.x, p.nblocks);
@@ -161,7 +147,6 @@ __global__ __launch_bounds__(256, 2) void conv3x3_halo_kernel(HaloParams p) {
         // rows past Cout re-read the last real row: their output channels are never stored nor counted in the statistics
         if constexpr (SUB == 1) boff[i] = (cls * p.Cout + min(n0 + row, p.Cout - 1)) * 4 * p.Cin + (cpos ^ ((row >> 1) & 7)) * 8;
         else boff[i] = min(n0 + row, p.Cout - 1) * (SUB == 2 ? 16 : 9) * p.Cin + (cpos ^ ((row >> 1) & 7)) * 8;
-        if (p.dbg >= 35 && p.dbg <= 38) boff[i] = VOFF_OOB / 2;        // experiment: no weight traffic (the DMA writes zeros)
     }
     // DMA through buffer descriptors (base in SGPRs, one 32-bit lane offset, tap / channel chunk as the scalar offset): no
     // per-piece 64-bit address arithmetic, and padding pixels are simply out of the descriptor's range (they read as zero)
@@ -205,15 +190,11 @@ __global__ __launch_bounds__(256, 2) void conv3x3_halo_kernel(HaloParams p) {
             hvo[i] = ok ? (((gy >> p.up) * SWd + (gx >> p.up)) * p.Cin + (cpos ^ ((hp >> 1) & 7)) * 8) * 2 : VOFF_OOB;
         }
     }
-    if (p.dbg == 36 || p.dbg == 37) {                                  // experiment: no halo traffic either
-#pragma unroll
-        for (int i = 0; i < NHP; ++i) hvo[i] = VOFF_OOB;
-    }
     auto issue_b_piece = [&](int i, int tapx, int c0, int buf) {
         const int tb = SUB == 0 && p.flip ? 8 - tapx : tapx;       // (SUB: c0 is the chunk's weight base, class included)
         __builtin_amdgcn_raw_ptr_buffer_load_lds(
             rsW, (__attribute__((address_space(3))) void*)(bst + buf * BSTAGE + (wave * (CO_T / NW) + i * 8) * ROWB), 16, boff[i] * 2,
-            p.dbg == 39 || p.dbg == 40 ? 0 : (tb * p.Cin + c0) * 2, 0, 0);      // (39 / 40: every tap re-reads the same 16 KB: L1 hits)
+            (tb * p.Cin + c0) * 2, 0, 0);
     };
     auto issue_halo_buf = [&](int c0) {
         if (p.nt_in) {                      // (aux 2 = nontemporal: an input far larger than the caches streams past them, the weights stay)
@@ -233,13 +214,13 @@ __global__ __launch_bounds__(256, 2) void conv3x3_halo_kernel(HaloParams p) {
 
     const int swzB = (l31 >> 1) & 7;
     const int cpc = p.Cin >> 6;                                     // 64-channel chunks (SUB = 2: per class)
-    const int nchunks = p.dbg == 2 ? 0 : (SUB == 2 ? 4 * cpc : cpc);
+    const int nchunks = SUB == 2 ? 4 * cpc : cpc;
     // Residual add on the MATRIX pipe (128-channel tiles): y = conv + R is computed as acc += I * R^T -- 16 extra MFMAs per wave (3 % of
     // the tile's) on a residual tile that LDS-DMA drops into the dead halo / weight stages under the last MFMAs of the loop, instead
     // of ~450 unpack / add / pack vector instructions per lane in the store loop, which issue once per MFMA of the CU neighbour
     // (fwd + residual at 128 -> 128, 256^2, B = 64: 1.166 ms with the vector adds against 1.011 ms without a residual).  The sum is
-    // rounded once (fp32 accumulator) where the reference rounds the conv output and the sum.  DVQ_HALO_DBG=3 keeps the vector path.
-    const bool res_mfma = !OUT32 && NT == 4 && p.R != nullptr && !p.res_mask && p.dbg != 3 && p.dbg != 9;
+    // rounded once (fp32 accumulator) where the reference rounds the conv output and the sum (docs/design/03b).
+    const bool res_mfma = !OUT32 && NT == 4 && p.R != nullptr && !p.res_mask;
     auto issue_residual = [&]() {
         // wave's own 64 pixels x 128 channels, one 1-KiB DMA per 4 pixels; 16-byte chunk c of pixel px sits at position c ^ (px & 7)
         const __amdgpu_buffer_rsrc_t rsRd = __builtin_amdgcn_make_buffer_rsrc(
@@ -418,7 +399,7 @@ __global__ __launch_bounds__(256, 2) void conv3x3_halo_kernel(HaloParams p) {
                     issue_halo_buf(hbx);                       // the halo tile is dead: refill it under the last MFMAs
 #pragma unroll
                     for (int i = 0; i < NPH; ++i) issue_b_piece(i, tap2, c02, buf);
-                } else if (res_mfma && p.dbg != 31) {
+                } else if (res_mfma) {
                     issue_residual();                          // every stage is dead: the residual tile lands under the last MFMAs
                 }
                 mfma_step(1, I0{}, I0{});
@@ -449,7 +430,6 @@ __global__ __launch_bounds__(256, 2) void conv3x3_halo_kernel(HaloParams p) {
             }
             asm volatile("s_waitcnt vmcnt(0)" : : : "memory");
             const char* rl = smem + (wave * 64 + l31) * 256;
-            if (p.dbg != 32)
 #pragma unroll
             for (int mt = 0; mt < MT; ++mt)
 #pragma unroll
@@ -535,11 +515,6 @@ __global__ __launch_bounds__(256, 2) void conv3x3_halo_kernel(HaloParams p) {
     // ---- epilogue: stage the 256 px x CO_T tile as bf16 rows, then 16-byte stores -------------------------------------------
     // (measured alternatives, all slower: 4-byte stores straight from the accumulators after a DPP lane-pair exchange; 8 waves x
     //  (1 x 4) tiles at 4 waves per SIMD -- 5 fragment reads per 4 MFMAs instead of 6 per 8 makes the loop LDS-bound.)
-    if (p.dbg == 1 || p.dbg == 37 || p.dbg == 38 || p.dbg == 40) {
-        if (acc[0][0][0] == 12345.678f) p.Y[0] = 0;       // keep the accumulators alive
-        return;
-    }
-    if constexpr (TRACE) tr[1] = wall_clock64();
     const bool act = p.act_slope != 1.f;
     const bool resv = p.R != nullptr && !res_mfma;                    // residual / gate tile handled by the store loop
     const bool early_act = act && (!resv || p.res_mask);              // no residual add between the accumulator and the activation
@@ -600,9 +575,8 @@ __global__ __launch_bounds__(256, 2) void conv3x3_halo_kernel(HaloParams p) {
     // LDS-only barrier: __syncthreads() would also drain vmcnt, i.e. make every wave wait for ALL of its residual loads before
     // the first row may be stored; this way each store waits for its own load only
     asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" : : : "memory");
-    if constexpr (TRACE) tr[2] = wall_clock64();
     const int cpg = p.out_stats != nullptr ? p.Cout / p.out_groups : 0;     // channels per group: power of two <= 32 (launcher)
-    const bool pairs = cpg >= 2 && p.dbg != 8 && p.dbg != 9;        // statistics per channel PAIR (v_dot2_f32_bf16: one instruction per dword and moment)
+    const bool pairs = cpg >= 2;        // statistics per channel PAIR (v_dot2_f32_bf16: one instruction per dword and moment)
     // GroupNorm statistics on the MATRIX pipe (round 6; 128-channel tiles, groups of 4 or 8 channels, no vector-path residual): wave w
     // takes channel tile w of the staged bf16 tile as MFMA operands Y^T (lane = channel, 8 pixels per k-step, formed by
     // ds_read_b64_tr_b16 from the pixel-major rows) and accumulates  Y^T Y  (its diagonal = sums of squares) and  Y^T 1  (sums) over the
@@ -610,7 +584,7 @@ __global__ __launch_bounds__(256, 2) void conv3x3_halo_kernel(HaloParams p) {
     // cross-lane folds per lane in the store loop -- instructions that issue once per MFMA of the CU neighbour (see the kernel header).
     // Same values as stored (bf16), fp32 accumulation; HaloParams::mfma_stats = 0 (DVQ_HALO_MFMA_STATS=0) keeps the vector path.
     bool mfma_stats = false;
-    if constexpr (NT == 4 && !OUT32) mfma_stats = p.mfma_stats && p.out_stats != nullptr && !resv && (cpg == 4 || cpg == 8) && p.dbg == 0;
+    if constexpr (NT == 4 && !OUT32) mfma_stats = p.mfma_stats && p.out_stats != nullptr && !resv && (cpg == 4 || cpg == 8);
     if constexpr (NT == 4 && !OUT32) {
         if (mfma_stats) {
             const int g4 = lane >> 4, li = lane & 15;
@@ -719,26 +693,7 @@ __global__ __launch_bounds__(256, 2) void conv3x3_halo_kernel(HaloParams p) {
             // (aux 2 = nontemporal: an output far larger than the Infinity Cache is not worth keeping there, see HaloParams::nt_out)
             if (p.nt_out) __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(dvq_u32x4, v), rsY, vo_px, so_iter(i), 2);
             else __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(dvq_u32x4, v), rsY, vo_px, so_iter(i), 0);
-            if (p.out_stats != nullptr && p.dbg == 9 && p.R != nullptr) {
-                // MEASUREMENT ONLY (DVQ_HALO_DBG=9, tools/debug/halo_data_probe.py): the arithmetic a GroupNorm-backward reduction
-                // fused into this epilogue would execute per element -- xhat, z, sigmoid, swish', dz, two accumulations -- on the
-                // staged value (as dy) and the residual tile (as x); the sums land in the statistics buffer (results meaningless)
-                const unsigned* pv = &v.x;
-                const unsigned* px = &rpre[i].x;
-#pragma unroll
-                for (int k = 0; k < 4; ++k) {
-#pragma unroll
-                    for (int hh = 0; hh < 2; ++hh) {
-                        const float dyv = __uint_as_float(hh ? (pv[k] & 0xffff0000u) : (pv[k] << 16));
-                        const float xv = __uint_as_float(hh ? (px[k] & 0xffff0000u) : (px[k] << 16));
-                        const float xh = fmaf(xv, p.act_slope, p.mask_slope);          // (x - mean) * rstd as one fma
-                        const float z = fmaf(xh, 1.0625f, 0.03125f);                    // gamma * xhat + beta
-                        const float dz = dyv * swish_grad(z);
-                        gs[2 * k + hh] += dz;
-                        gq[2 * k + hh] = fmaf(dz, xh, gq[2 * k + hh]);
-                    }
-                }
-            } else if (p.out_stats != nullptr && !mfma_stats) {
+            if (p.out_stats != nullptr && !mfma_stats) {
                 const unsigned* pv = &v.x;
                 if (pairs) {
 #pragma unroll
@@ -760,7 +715,6 @@ __global__ __launch_bounds__(256, 2) void conv3x3_halo_kernel(HaloParams p) {
             }
         }
     }
-    if constexpr (TRACE) tr[3] = wall_clock64();
     if (p.out_stats != nullptr && !mfma_stats) {
         // lanes l, l + CPRW, l + 2 CPRW, ... of a wave hold partials of the same 8 channels: fold them with shuffles, park one
         // row per wave in LDS, add the NW rows per channel (or pair), fold the channels of a group (a power of two, lanes adjacent)
@@ -818,18 +772,6 @@ __global__ __launch_bounds__(256, 2) void conv3x3_halo_kernel(HaloParams p) {
             }
         }
     }
-    if constexpr (TRACE) {
-        if (tid == 0 && blockIdx.x < HALO_TRACE_MAX) {
-            tr[4] = wall_clock64();
-            asm volatile("s_waitcnt vmcnt(0)" : : : "memory");            // the tile's stores have been acknowledged
-            g_halo_trace[blockIdx.x][0] = tr_key | (tr[4] << 16);
-            g_halo_trace[blockIdx.x][1] = tr[0];
-            g_halo_trace[blockIdx.x][2] = tr[1];
-            g_halo_trace[blockIdx.x][3] = wall_clock64();
-            g_halo_trace[blockIdx.x][4] = tr[2];
-            g_halo_trace[blockIdx.x][5] = tr[3];
-        }
-    }
 #endif
 }
 
@@ -852,23 +794,6 @@ __global__ __launch_bounds__(64) void halo_stats_finalize_kernel(const float* __
 
 }  // namespace
 
-#ifdef DVQ_PROBES
-// the persistent form (conv_halo2.hip: measured slower) is part of probe builds only
-int dvq_conv3x3_halo2_try(const void* x, const void* w, const float* bias, const void* residual, void* y, int64_t N, int64_t H, int64_t W,
-                          int64_t Cin, int64_t Cout, int flip, int up, const float* gn_ss, double* out_stats, int out_groups,
-                          float act_slope, int res_mask, float mask_slope, hipStream_t stream);
-#endif
-
-extern "C" int dvq_halo_trace_read(unsigned long long* dst, int64_t max_records) {
-    DVQ_REQUIRE(dst != nullptr && max_records > 0, DVQ_EINVAL, "dvq_halo_trace_read: bad arguments");
-    const int64_t n = max_records < HALO_TRACE_MAX ? max_records : HALO_TRACE_MAX;
-    if (hipMemcpyFromSymbol(dst, HIP_SYMBOL(g_halo_trace), (size_t)n * 6 * sizeof(unsigned long long)) != hipSuccess) {
-        dvq_set_error("dvq_halo_trace_read: copy failed");
-        return DVQ_ELAUNCH;
-    }
-    return DVQ_OK;
-}
-
 // Returns 1 if the halo kernel handled the call, 0 if the shape is not eligible (caller falls back to igemm),
 // negative on error.  x: [N,H,W,Cin] bf16; w: rows of [9][Cin]; y: [N,H,W,Cout].
 // sub (HaloParams::sub): H, W are the LOW resolution, the other tensor is [N,2H,2W,.], w is the sub-pixel pack; the caller checked the shape
@@ -881,13 +806,6 @@ static int halo_try_impl(const void* x, const void* w, const float* bias, const 
                 N * 4 * H * W * (Cin > Cout ? Cin : Cout) >= (1ll << 30) || Cout * 16 * Cin >= (1ll << 30)))
         return 0;
     if (out32 && (gn_ss != nullptr || out_stats != nullptr || H * W * Cout * 4 >= (1ll << 31))) return 0;
-#ifdef DVQ_PROBES
-    if (!out32 && !sub) {   // the persistent kernel (conv_halo2.hip, DVQ_HALO2=1) takes the launches it is built for: 128-channel output blocks, >= 2 tiles per CU
-        const int rc2 = dvq_conv3x3_halo2_try(x, w, bias, residual, y, N, H, W, Cin, Cout, flip, up, gn_ss, out_stats, out_groups, act_slope,
-                                              res_mask, mask_slope, stream);
-        if (rc2 != 0) return rc2;
-    }
-#endif
     const int cot = Cout <= 32 ? 32 : Cout <= 64 ? 64 : 128;          // output-channel tile of the kernel instance
     if (out_stats != nullptr && (out_groups <= 0 || Cout % out_groups != 0 || cot % (Cout / out_groups) != 0)) return 0;
     if (out_stats != nullptr) {
@@ -919,8 +837,6 @@ static int halo_try_impl(const void* x, const void* w, const float* bias, const 
         return e == nullptr ? 0 : atoi(e);
     }();
     p.nt_in = nt_in_env && p.gn == 1 && !sub && (N * H * W * Cin * 2 >> up >> up) > (192ll << 20);
-    static const int dbg_env = dvq_probe_env("DVQ_HALO_DBG");       // 0 unless built with -DDVQ_PROBES
-    p.dbg = dbg_env;
     const int ntiles = p.tiles_y * p.tiles_x * (sub == 1 ? 4 : 1);      // partial slots per (n, group): one per tile and class
     if (out_stats != nullptr) {
         int64_t ws_bytes = 0;
@@ -944,28 +860,22 @@ static int halo_try_impl(const void* x, const void* w, const float* bias, const 
     if (blocks * dmax >= (1ll << 32)) return 0;        // (exactness range of the scalar tile decode)
     p.nblocks = (int)blocks;
     p.mg_gn = magic(p.gn); p.mg_tx = magic(p.tiles_x); p.mg_ty = magic(p.tiles_y);
-    // experiment (DVQ_HALO_LDS_PAD=1, probe builds): > 80 KB of LDS = ONE workgroup per CU
-    static const int lds_pad = dvq_probe_env("DVQ_HALO_LDS_PAD") != 0 ? 90 * 1024 - LDSB : 0;
     dvq_note_kernel("conv3x3_halo_kernel");
     auto go = [&](auto kern) {
-        dvq_ensure_dynamic_lds((const void*)kern, LDSB + lds_pad);
-        kern<<<dim3((unsigned)blocks), dim3(256), LDSB + lds_pad, stream>>>(p);
+        dvq_ensure_dynamic_lds((const void*)kern, LDSB);
+        kern<<<dim3((unsigned)blocks), dim3(256), LDSB, stream>>>(p);
     };
     if (sub == 1) {
-        if (cot == 128) go(conv3x3_halo_kernel<4, false, false, 1>);
-        else go(conv3x3_halo_kernel<2, false, false, 1>);
+        if (cot == 128) go(conv3x3_halo_kernel<4, false, 1>);
+        else go(conv3x3_halo_kernel<2, false, 1>);
     } else if (sub == 2) {
-        if (cot == 128) go(conv3x3_halo_kernel<4, false, false, 2>);
-        else go(conv3x3_halo_kernel<2, false, false, 2>);
+        if (cot == 128) go(conv3x3_halo_kernel<4, false, 2>);
+        else go(conv3x3_halo_kernel<2, false, 2>);
     } else if (out32) {
-        if (cot == 128) go(conv3x3_halo_kernel<4, false, true>);
-        else if (cot == 64) go(conv3x3_halo_kernel<2, false, true>);
-        else go(conv3x3_halo_kernel<1, false, true>);
+        if (cot == 128) go(conv3x3_halo_kernel<4, true>);
+        else if (cot == 64) go(conv3x3_halo_kernel<2, true>);
+        else go(conv3x3_halo_kernel<1, true>);
     } else if (cot == 128) {
-#ifdef DVQ_PROBES
-        if (p.dbg == 6) go(conv3x3_halo_kernel<4, true>);       // per-workgroup time stamps (dvq_halo_trace_read)
-        else
-#endif
         go(conv3x3_halo_kernel<4>);
     } else if (cot == 64) {
         go(conv3x3_halo_kernel<2>);
@@ -1038,7 +948,6 @@ struct WgParams {
     const float* gn_ss;  // optional fused GroupNorm+swish on x: {scale, shift} fp32 [N][Cin][2] (recomputed, never stored)
     float* ws;           // split-K partials: [nsplit][gi*gj][9][128][64] fp32 (+ bias partials behind), or null -> atomics
     float* ws_bias;      // [nsplit][gi*gj][128]
-    int dbg;             // profiling experiments only (DVQ_WGRAD_DBG): 2 = skip the MFMA loop, 3 = no DMA  (1, "do not wait for the DMA", is gone: racy)
     int nt;              // 1: operands larger than the Infinity Cache, read by one workgroup column -- nontemporal DMA (DVQ_WGRAD_NT)
     int plane_n;         // fp32x3 in ONE launch (round 6): X and DY each hold two bf16 planes [hi; lo] of plane_n images, N = 3 plane_n, and
                          // "image" n of the tile walk is the product (x_lo, dy_hi), (x_hi, dy_lo), (x_hi, dy_hi) for n / plane_n = 0, 1, 2 --
@@ -1226,7 +1135,7 @@ __global__ __launch_bounds__(512, 2) void conv3x3_halo_wgrad_kernel(WgParams p) 
         for (int t = tbeg; t < tend; ++t) {
             const int buf = (t - tbeg) & 1;
             const bool do_bias = do_bias_wg && t >= bias_from;
-            if (p.gn_ss == nullptr && t + 1 < tend && p.dbg != 3) issue(t + 1, buf ^ 1);
+            if (p.gn_ss == nullptr && t + 1 < tend) issue(t + 1, buf ^ 1);
             const char* sdy = smem + buf * WSTAGE;
             const char* shl = sdy + WDYB;
             if (p.gn_ss != nullptr) {
@@ -1257,8 +1166,7 @@ __global__ __launch_bounds__(512, 2) void conv3x3_halo_wgrad_kernel(WgParams p) 
                 __syncthreads();
                 if (t + 1 < tend) issue(t + 1, buf ^ 1);     // prefetch after the barrier
             }
-            if (p.dbg == 2) {
-            } else if constexpr (!THIN) {
+            if constexpr (!THIN) {
                 // Software pipeline over the tile's 8 x 9 (pixel step, tap) MFMAs: the transpose reads of x fragment q + 3 are issued
                 // before MFMA q (a ds_read_b64_tr round trip is ~100+ cycles under load; read -> wait -> MFMA one deep left each wave
                 // waiting on the LDS for most of every MFMA slot, both waves of a SIMD alike).  Fully unrolled: every fragment address is
@@ -1450,8 +1358,6 @@ static int halo_wgrad_impl(const void* x, const void* dy, float* dw, float* db, 
     p.c_oihw = c_oihw;
     p.up = up;
     p.gn_ss = gn_ss;
-    static const int wdbg_env = dvq_probe_env("DVQ_WGRAD_DBG");     // 0 unless built with -DDVQ_PROBES
-    p.dbg = wdbg_env;
     static const int wnt_env = [] {
         const char* e = getenv("DVQ_WGRAD_NT");
         return e == nullptr ? 0 : atoi(e);

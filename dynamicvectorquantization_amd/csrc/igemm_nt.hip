@@ -1480,16 +1480,6 @@ int launch_nt_glds(NtParams p, int64_t batch, hipStream_t s) {
         kern<<<grid, dim3(256), 2 * GSTAGEB, s>>>(p);
     };
     constexpr bool F32 = sizeof(T) == 4;
-#ifdef DVQ_PROBES
-    {
-        static const int x3dbg = dvq_probe_env("DVQ_X3_DBG");
-        static bool x3set = false;
-        if (!x3set) {
-            x3set = true;
-            (void)hipMemcpyToSymbol(HIP_SYMBOL(g_x3_dbg), &x3dbg, sizeof(int));
-        }
-    }
-#endif
     if (F32 && p.split3) {              // fp32x3: the split-bf16 instantiations (separate kernels: the exact-fp32 code is untouched)
         if (p.mode == MODE_GEMM) go(igemm_nt_glds_kernel<T, MODE_GEMM, false, F32>);
         else if (p.mode == MODE_FWD && tapu) go(igemm_nt_glds_kernel<T, MODE_FWD, true, F32>);

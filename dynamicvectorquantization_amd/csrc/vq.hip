@@ -247,7 +247,7 @@ union Bf16x8U {
 // (x = x1 + x2 + r, |r| <= 2^-18 |x|) take the places of the two row blocks: x1.e1 + x1.e2 into one accumulator, x2.e1 into the other
 // (3 MFMAs per k-step; x2.e2 is below the bound's 2^-18 term), one retirement per row on their sum -- half the bookkeeping per MFMA of
 // the bf16 form.  128 rows per workgroup.
-template <int KSTEPS, int dbg = 0, typename XT = bf16_t>
+template <int KSTEPS, typename XT = bf16_t>
 __global__ __launch_bounds__(256, 1) void vq_argmin_mfma_rb2_kernel(const XT* __restrict__ x, const void* prep_c, int64_t N, int64_t K,
                                                                     int64_t* __restrict__ idx_out, VqWs* ws) {
     constexpr bool XF32 = std::is_same<XT, float>::value;
@@ -274,12 +274,6 @@ __global__ __launch_bounds__(256, 1) void vq_argmin_mfma_rb2_kernel(const XT* __
     const int half = lane >> 5;
     const int l31 = lane & 31;
     const int64_t row0 = (int64_t)blockIdx.x * (RPW * NW) + wave * RPW;
-    // (dbg bit 5: shader-clock stamps of workgroup 7, wave 0 in ws->pad[8 ..]: start, rows loaded, first stage landed, loop done, end)
-    unsigned long long stamps[5];
-    auto stamp = [&](int i) {
-        if constexpr (dbg & 32) stamps[i] = __builtin_readcyclecounter();
-    };
-    stamp(0);
 
     // ---- x fragments: the bf16 rows ARE the operand (x = x1 exactly).  The loads are issued here, the codebook DMA of the first two
     // stages right behind them, and only then are the norms computed: the 33 MB of rows and the first stages travel together ---------
@@ -444,44 +438,28 @@ __global__ __launch_bounds__(256, 1) void vq_argmin_mfma_rb2_kernel(const XT* __
                 // the barrier (the D = 64 float kernel had one stage body of its loop without any vmcnt: another wave's fragment reads
                 // could overtake this wave's pieces; seen as run-to-run different indices once a second process shared the GPU)
                 asm volatile("s_waitcnt vmcnt(0)" ::: "memory");        // this wave's pieces of stage c + 1 (and en of stage c) have landed
-                if constexpr (!(dbg & 16)) __syncthreads();             // all waves are inside stage c     (dbg bit 4: no stage barrier -- racy)
+                __syncthreads();                                        // all waves are inside stage c
                 // |e|^2 of the NEXT stage, requested behind the barrier and before this stage's DMA pieces: a whole stage old at the next wait
                 en_nxt = pv.en[c1 * 32 + l31];
             }
             if (ks + PF < KSTEPS) {
-                if constexpr (dbg & 8) {                // (dbg bit 3: no fragment reads past the first two k-steps)
-                    f1[ks + PF] = f1[ks];
-                    f2[ks + PF] = f2[ks];
-                } else {
-                    frag_at(f1[ks + PF], f2[ks + PF], ks + PF, 0);
-                }
+                frag_at(f1[ks + PF], f2[ks + PF], ks + PF, 0);
             } else {
                 frag_at(g1[ks + PF - KSTEPS], g2[ks + PF - KSTEPS], ks + PF - KSTEPS, 1);       // k-steps 0, 1 of stage c + 1 (behind the barrier)
             }
-            if constexpr (!(dbg & 4)) {
-                if (ks >= KB && ks - KB < NPOST) issue_piece(c2, b2n, ks - KB, pvo[ks - KB]);
-                if (ks + NPOST < NPW) issue_piece(c1, b1n, ks + NPOST, pvo[ks + NPOST]);
-            }
-            if constexpr (!(dbg & 2)) {      // (dbg: timing experiments only -- bit 0 no bookkeeping, bit 1 no MFMA, bit 2 no DMA)
-                cur[0] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(xa[0][ks], f1[ks], ks == 0 ? zero : cur[0], 0, 0, 0);
-                cur[1] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(xa[1][ks], f1[ks], ks == 0 ? zero : cur[1], 0, 0, 0);
-                cur[0] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(xa[0][ks], f2[ks], cur[0], 0, 0, 0);
-                if constexpr (!XF32) cur[1] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(xa[1][ks], f2[ks], cur[1], 0, 0, 0);
-            } else {
-                const float v = __builtin_bit_cast(float, (unsigned)__builtin_bit_cast(unsigned short, f1[ks][0]) << 16) +
-                                __builtin_bit_cast(float, (unsigned)__builtin_bit_cast(unsigned short, f2[ks][0]) << 16);
-                if (ks == 0) cur[0] = cur[1] = zero;
-                cur[0][ks & 15] += v;
-            }
-            if constexpr (!(dbg & 1)) {
+            if (ks >= KB && ks - KB < NPOST) issue_piece(c2, b2n, ks - KB, pvo[ks - KB]);
+            if (ks + NPOST < NPW) issue_piece(c1, b1n, ks + NPOST, pvo[ks + NPOST]);
+            cur[0] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(xa[0][ks], f1[ks], ks == 0 ? zero : cur[0], 0, 0, 0);
+            cur[1] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(xa[1][ks], f1[ks], ks == 0 ? zero : cur[1], 0, 0, 0);
+            cur[0] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(xa[0][ks], f2[ks], cur[0], 0, 0, 0);
+            if constexpr (!XF32) cur[1] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(xa[1][ks], f2[ks], cur[1], 0, 0, 0);
 #pragma unroll
-                for (int j = 0; j < RPK; ++j) {
-                    if constexpr (XF32) {
-                        retire_row(0, ks * RPK + j, prev[0][ks * RPK + j] + prev[1][ks * RPK + j], en_prev, kprev);
-                    } else {
-                        retire_row(0, ks * RPK + j, prev[0][ks * RPK + j], en_prev, kprev);
-                        retire_row(1, ks * RPK + j, prev[1][ks * RPK + j], en_prev, kprev);
-                    }
+            for (int j = 0; j < RPK; ++j) {
+                if constexpr (XF32) {
+                    retire_row(0, ks * RPK + j, prev[0][ks * RPK + j] + prev[1][ks * RPK + j], en_prev, kprev);
+                } else {
+                    retire_row(0, ks * RPK + j, prev[0][ks * RPK + j], en_prev, kprev);
+                    retire_row(1, ks * RPK + j, prev[1][ks * RPK + j], en_prev, kprev);
                 }
             }
             // issue order of the k-step: MFMA, the two fragment reads, MFMA, [DMA piece], bookkeeping spread over the rest
@@ -505,10 +483,8 @@ __global__ __launch_bounds__(256, 1) void vq_argmin_mfma_rb2_kernel(const XT* __
         ++c;
     };
 
-    stamp(1);
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");    // stage 0 and the first pieces of stage 1 (explicit: see the stage barrier)
     __syncthreads();
-    stamp(2);
 #pragma unroll
     for (int ks = 0; ks < PF; ++ks) {
         const char* a = smem + fo[ks % NJ] + (ks / NJ) * (NJ * 32);
@@ -536,19 +512,11 @@ __global__ __launch_bounds__(256, 1) void vq_argmin_mfma_rb2_kernel(const XT* __
                 for (int r = 0; r < 16; ++r) retire_row(rb, r, lastA ? accA[rb][r] : accB[rb][r], en_prev, klast);
         }
     }
-    stamp(3);
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");    // the trailing (unread) DMA pieces have landed too
     __syncthreads();                                    // every wave is done with the stage ring: it becomes the selection scratch
     float* scr = reinterpret_cast<float*>(smem) + wave * VQ_SEL_WORDS;
     vq_select_rows_lds<D>(b1[0], b2[0], i1[0], xnorm + wave * 64, pv, lane, row0, N, idx_out, ws, scr);
     if constexpr (!XF32) vq_select_rows_lds<D>(b1[1], b2[1], i1[1], xnorm + wave * 64 + 32, pv, lane, row0 + 32, N, idx_out, ws, scr);
-    stamp(4);
-    if constexpr (dbg & 32) {
-        if (blockIdx.x == 7 && tid == 0) {
-            unsigned long long* t = reinterpret_cast<unsigned long long*>(&ws->pad[9]);
-            for (int i = 0; i < 5; ++i) t[i] = stamps[i];
-        }
-    }
 }
 
 __global__ void vq_flag_all_kernel(VqWs* ws, int64_t N) {
@@ -1033,38 +1001,15 @@ __global__ __launch_bounds__(256) void vq_distances_kernel(const XT* __restrict_
 
 }  // namespace
 
-// bf16 rows: 4 waves x 64 rows.  DVQ_VQ_DBG = 1 / 2 / 4 (D = 256 only): timing experiments without bookkeeping / MFMAs / DMA (WRONG results)
-template <int KS, int DB, typename XT>
-static void vq_launch_rb2_dbg(const XT* x, const void* prep, int64_t N, int64_t K, int64_t* idx, VqWs* ws, hipStream_t s) {
+// bf16 rows: 4 waves x 64 rows; fp32 rows: 4 waves x 32 rows
+template <int KS, typename XT>
+static void vq_launch_rb2(const XT* x, const void* prep, int64_t N, int64_t K, int64_t* idx, VqWs* ws, hipStream_t s) {
     constexpr int Dc = KS * 16;
     const size_t ring = 3 * (2 * 32 * (Dc * 2)), sel = 4 * VQ_SEL_WORDS * 4;
     const size_t lds = (ring > sel ? ring : sel) + 64 * 4 * 4;          // a ring of three 32-code stages (later: selection scratch) + the row norms
     const int rows_wg = std::is_same<XT, float>::value ? 128 : 256;
-    dvq_ensure_dynamic_lds((const void*)vq_argmin_mfma_rb2_kernel<KS, DB, XT>, (int)lds);
-    vq_argmin_mfma_rb2_kernel<KS, DB, XT><<<dim3((unsigned)cdiv64(N, rows_wg)), dim3(256), lds, s>>>(x, prep, N, K, idx, ws);
-}
-template <int KS>
-static void vq_launch_rb2(const float* x, const void* prep, int64_t N, int64_t K, int64_t* idx, VqWs* ws, hipStream_t s) {
-    vq_launch_rb2_dbg<KS, 0, float>(x, prep, N, K, idx, ws, s);
-}
-template <int KS>
-static void vq_launch_rb2(const bf16_t* x, const void* prep, int64_t N, int64_t K, int64_t* idx, VqWs* ws, hipStream_t s) {
-#ifdef DVQ_PROBES
-    static const int vdbg = dvq_probe_env("DVQ_VQ_DBG");            // cycle-stamp / piece-removal variants: probe builds only
-    if constexpr (KS == 16) {
-        if (vdbg == 1) return vq_launch_rb2_dbg<KS, 1, bf16_t>(x, prep, N, K, idx, ws, s);
-        if (vdbg == 2) return vq_launch_rb2_dbg<KS, 2, bf16_t>(x, prep, N, K, idx, ws, s);
-        if (vdbg == 4) return vq_launch_rb2_dbg<KS, 4, bf16_t>(x, prep, N, K, idx, ws, s);
-        if (vdbg == 8) return vq_launch_rb2_dbg<KS, 8, bf16_t>(x, prep, N, K, idx, ws, s);
-        if (vdbg == 9) return vq_launch_rb2_dbg<KS, 9, bf16_t>(x, prep, N, K, idx, ws, s);
-        if (vdbg == 16) return vq_launch_rb2_dbg<KS, 16, bf16_t>(x, prep, N, K, idx, ws, s);
-        if (vdbg == 13) return vq_launch_rb2_dbg<KS, 13, bf16_t>(x, prep, N, K, idx, ws, s);
-        if (vdbg == 29) return vq_launch_rb2_dbg<KS, 29, bf16_t>(x, prep, N, K, idx, ws, s);
-        if (vdbg == 32) return vq_launch_rb2_dbg<KS, 32, bf16_t>(x, prep, N, K, idx, ws, s);
-        if (vdbg == 61) return vq_launch_rb2_dbg<KS, 61, bf16_t>(x, prep, N, K, idx, ws, s);
-    }
-#endif
-    vq_launch_rb2_dbg<KS, 0, bf16_t>(x, prep, N, K, idx, ws, s);
+    dvq_ensure_dynamic_lds((const void*)vq_argmin_mfma_rb2_kernel<KS, XT>, (int)lds);
+    vq_argmin_mfma_rb2_kernel<KS, XT><<<dim3((unsigned)cdiv64(N, rows_wg)), dim3(256), lds, s>>>(x, prep, N, K, idx, ws);
 }
 
 template <typename XT>

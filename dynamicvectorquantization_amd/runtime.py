@@ -21,7 +21,7 @@ _impl = _lib.IMPL_AUTO
 
 # Every environment variable the Python package honours as a switch: name -> (default, what the non-default selects).  All of them
 # are read through switch(), at call time.  (Paths and build inputs are not switches: DVQ_IMAGENET_ROOT, DVQ_VGG16_WEIGHTS,
-# DVQ_LPIPS_LIN_WEIGHTS, DVQ_USE_PROBES_LIB, DVQ_BUILD_EXTRA_FLAGS.)  A new row takes a row in the switch table of
+# DVQ_LPIPS_LIN_WEIGHTS, DVQ_BUILD_EXTRA_FLAGS.)  A new row takes a row in the switch table of
 # docs/design/03-kernels.md too; tests/test_host_cpu.py pins both.
 SWITCHES = {
     "DVQ_FUSE_GN": ("0", "1: GroupNorm+swish inside the consuming 3x3 conv on taped forwards too"),

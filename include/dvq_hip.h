@@ -13,7 +13,7 @@
  *     eight equal slots that are handed to the streams using them; a slot requested during stream capture stays with its
  *     stream until dvq_workspace_release(); set it once before the first call that uses it; calls that find no slot or a slot
  *     too small fall back to atomics) and caches of one-off hipFuncSetAttribute calls.
- *     dvq_probe_mfma_rate, dvq_halo_trace_read (diagnostics) and dvq_decode_stack_status are the entry points that allocate or synchronise;
+ *     dvq_probe_mfma_rate (diagnostics) and dvq_decode_stack_status are the entry points that allocate or synchronise;
  *     no vendor BLAS / DNN library is linked or loaded: every product is a kernel of this library;
  *   - every entry point issues KERNEL launches only (no memset / memcpy nodes), so a sequence of calls can be recorded by
  *     HIP stream capture after its first eager execution and replayed (the training step and the sampler do);
@@ -46,7 +46,8 @@ const char* dvq_last_error(void);
  * written in csrc ("conv3x3_halo_kernel", "conv_nt_pipe_kernel", ...; no template arguments, no fold / reduce / transpose helpers), noted
  * at the dispatch branch that launches it.  "" when nothing was noted (those entry points clear it first).  For timing labels. */
 const char* dvq_last_kernel(void);
-int dvq_version(void);     /* 120: dvq_conv3x3_subpixel_ok, dvq_conv_desc.upsample == 2, bit 9 of the weight packs' dtype (nearest x2 + 3x3 convolutions
+int dvq_version(void);     /* 121: dvq_halo_trace_read is gone (the timing experiments and the persistent 3x3 kernel left the sources: one library);
+                            * 120: dvq_conv3x3_subpixel_ok, dvq_conv_desc.upsample == 2, bit 9 of the weight packs' dtype (nearest x2 + 3x3 convolutions
                             * as four 2x2 sub-pixel convolutions, forward and input gradient);
                             * 119: dvq_scalar_push (+ dvq_scalar_push_state_bytes), dvq_codebook_health (training metric logs);
                             * 118: dvq_unordered_launches; dvq_set_deterministic orders every floating-point reduction of a training step;
@@ -63,7 +64,7 @@ int dvq_version(void);     /* 120: dvq_conv3x3_subpixel_ok, dvq_conv_desc.upsamp
                             * 110: dvq_recon_metrics (+ _workspace_bytes), dvq_code_histogram (reconstruction evaluation);
                             * 109: round 5 (dvq_conv2d_fwd_x3 / dvq_conv2d_dgrad_x3: fp32x3 3 x 3 convolutions on the halo kernel, fp32 output);
                             * 108: round 5 (dvq_split_bf16_planes, dvq_conv2d_wgrad_oihw_x3: fp32x3 weight gradients on the bf16 kernels);
-                            * 107: round 5 (dvq_lpips_head_drop; probe modes compiled out of the product library: -DDVQ_PROBES);
+                            * 107: round 5 (dvq_lpips_head_drop; probe modes compiled out of the product library);
                             * 106: round 4 (launch lists dvq_cmdlist_*, dvq_add_uniform, dvq_decode_stack_status + 64 sequences, drop_mask argument
                             * of dvq_attn_causal_fwd / bwd + dvq_attn_causal_mask_bytes, dvq_layernorm_bwd_res, dvq_dropout_add, eight
                             * workspace slots + dvq_workspace_release, vq_argmin workspace report slots);
@@ -365,9 +366,6 @@ int dvq_cmdlist_create(void* hip_graph, dvq_cmdlist_t* out);
 int dvq_cmdlist_replay(dvq_cmdlist_t list, dvq_stream_t main_stream, dvq_stream_t side_stream);
 int dvq_cmdlist_info(dvq_cmdlist_t list, int64_t* info4);
 int dvq_cmdlist_destroy(dvq_cmdlist_t list);
-/* diagnostics (DVQ_HALO_DBG=6): per workgroup of the LAST 3x3 halo-conv launch {CU key | (time before the final store drain) << 16,
- * start, end of the main loop, end, tile staged, tile stored} in 10-ns ticks; dst holds max_records x 6 uint64.  Synchronises. */
-int dvq_halo_trace_read(unsigned long long* dst, int64_t max_records);
 
 /* ---- loss networks (LPIPS + PatchGAN), modules/losses/lpips.py, modules/discriminator/model.py -------------------
  * BatchNorm2d (training mode) = dvq_gn_* with N=1, HW=N*H*W, G=C (one group per channel over the whole batch). */

@@ -17,4 +17,4 @@ def test_no_barrier_with_unwaited_lds_dma():
     flagged = [l for l in r.stdout.splitlines() if "[CHECK]" in l]
     assert r.returncode == 0 and not flagged, "\n".join(flagged) + r.stderr[-2000:]
     checked = [l for l in r.stdout.splitlines() if "barriers," in l]
-    assert len(checked) >= 20, len(checked)          # every DMA kernel of vq / igemm / conv_halo / conv_halo2 was walked
+    assert len(checked) >= 20, len(checked)          # every DMA kernel of vq / igemm / conv_halo was walked

@@ -3,7 +3,6 @@ profiling) and the eligibility predicates against the entry points they speak fo
 
 One bf16, impl 0 case per branch of the conv entry points that notes a family and is reachable with the default environment, each at
 the smallest shape that meets the branch's conditions in csrc/igemm.hip, csrc/igemm_nt.hip, csrc/igemm_tn.hip / csrc/conv_halo.hip.  Noted branches WITHOUT a case here:
-  * conv3x3_halo2_kernel: exists in the probes build only (-DDVQ_PROBES, DVQ_HALO2=1);
   * gemm_nt_wide_kernel, igemm_nt_kernel: plain GEMMs at K >= 8192 / impl 3 only -- no conv call reaches them with impl 0;
   * gemm_tn_8phase_kernel, gemm_tn_wide_pipe_kernel: no conv call reaches them (gemm_tn calls do by default, under the fixed label
     "gemm_tn");

@@ -452,7 +452,7 @@ def test_build_staleness_covers_every_header_and_sources_exist():
     on_disk = {os.path.realpath(os.path.join(build.CSRC, f)) for f in os.listdir(build.CSRC) if f.endswith(".h")}
     assert on_disk and on_disk <= watched, sorted(on_disk - watched)
     assert os.path.realpath(os.path.join(REPO, "include", "dvq_hip.h")) in watched
-    for src in build.SOURCES + build.PROBE_SOURCES:
+    for src in build.SOURCES:
         assert os.path.isfile(os.path.join(build.CSRC, src)), src
 
 
@@ -463,26 +463,45 @@ CSRC_GETENV_SWITCHES = {
     "DVQ_DECODE_MODE", "DVQ_DECODE_ATTN_SPLIT", "DVQ_DECODE_WAVE_ATTN", "DVQ_DECODE_TRACE",          # sampler: tests and tools name them
     "DVQ_DETERMINISTIC", "DVQ_FP32_SPLIT",                                                           # API defaults
     "DVQ_CMDLIST_LAUNCH", "DVQ_CMDLIST_DEBUG", "DVQ_LN_BWD_WAVES",
-    "DVQ_HALO2", "DVQ_HALO2_DBG", "DVQ_HALO_DBG",                                                    # conv_halo2.hip: probe library only
 }
-CSRC_PROBE_SWITCHES = {"DVQ_ATTN_DBG", "DVQ_ATTN2_DBG", "DVQ_HALO_DBG", "DVQ_HALO_LDS_PAD", "DVQ_VQ_DBG", "DVQ_WGRAD_DBG", "DVQ_X3_DBG"}
 
 
 def test_csrc_environment_switches_are_listed_and_documented():
     csrc = os.path.join(REPO, "dynamicvectorquantization_amd", "csrc")
     text = "".join(open(os.path.join(csrc, f)).read() for f in sorted(os.listdir(csrc)) if f.endswith((".hip", ".h")))
     assert set(re.findall(r'\bgetenv\("(DVQ_[A-Z0-9_]+)"\)', text)) == CSRC_GETENV_SWITCHES
-    assert set(re.findall(r'\bdvq_probe_env\("(DVQ_[A-Z0-9_]+)"\)', text)) == CSRC_PROBE_SWITCHES
-    # no other spelling reads the environment: the one getenv without a literal name is dvq_probe_env's own
-    assert len(re.findall(r"\bgetenv\(", text)) == len(re.findall(r'\bgetenv\("DVQ_', text)) + 1
+    # no other spelling reads the environment: every getenv has a literal DVQ_ name
+    assert len(re.findall(r"\bgetenv\(", text)) == len(re.findall(r'\bgetenv\("DVQ_', text))
     doc = open(os.path.join(REPO, "docs", "design", "03-kernels.md")).read()
     table = doc[doc.index("| variable | effect |"):doc.index("**Retired switches.**")]
-    for name in sorted(CSRC_GETENV_SWITCHES | CSRC_PROBE_SWITCHES):
+    for name in sorted(CSRC_GETENV_SWITCHES):
         assert re.search(r"\b%s\b" % name, table), f"{name} is read in csrc/ but has no row in the switch table of docs/design/03-kernels.md"
 
 
+def test_one_library_without_probe_code():
+    """the timing experiments, the persistent 3x3 kernel and the per-workgroup trace export are gone: no source names the probe build,
+    and the library exports neither of their entry points"""
+    from dynamicvectorquantization_amd import _lib, build
+    roots = [os.path.join(REPO, "dynamicvectorquantization_amd"), os.path.join(REPO, "include")]
+    checked = 0
+    for root in roots:
+        for d, _, files in os.walk(root):
+            for f in files:
+                if f.endswith((".hip", ".h", ".py")):
+                    text = open(os.path.join(d, f)).read()
+                    checked += 1
+                    for word in ("DVQ_PROBES", "dvq_probe_env"):
+                        assert word not in text, f"{os.path.join(d, f)} names {word}"
+    assert checked >= len(build.SOURCES) + 10
+    build.build(verbose=False)
+    lib = _lib.load()
+    assert not hasattr(lib, "dvq_halo_trace_read")
+    assert not hasattr(lib, "dvq_conv3x3_halo2_try")
+    assert lib.dvq_version() == 121
+
+
 # the environment names the Python package reads that are paths or build inputs, not switches: read where they are used
-PY_ENV_NOT_SWITCHES = {"DVQ_IMAGENET_ROOT", "DVQ_VGG16_WEIGHTS", "DVQ_LPIPS_LIN_WEIGHTS", "DVQ_USE_PROBES_LIB", "DVQ_BUILD_EXTRA_FLAGS"}
+PY_ENV_NOT_SWITCHES = {"DVQ_IMAGENET_ROOT", "DVQ_VGG16_WEIGHTS", "DVQ_LPIPS_LIN_WEIGHTS", "DVQ_BUILD_EXTRA_FLAGS"}
 
 
 def _switch_table():
@@ -492,7 +511,7 @@ def _switch_table():
 
 def test_python_environment_reads_go_through_the_registry():
     """every DVQ_* name the package's modules read from the environment is a row of runtime.SWITCHES, read through runtime.switch(),
-    or one of the five path / build-input names; nothing else in the package touches os.environ / getenv"""
+    or one of the four path / build-input names; nothing else in the package touches os.environ / getenv"""
     from dynamicvectorquantization_amd import losses
     from dynamicvectorquantization_amd import runtime as rt
     pkg = os.path.join(REPO, "dynamicvectorquantization_amd")
