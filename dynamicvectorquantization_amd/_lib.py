@@ -44,6 +44,16 @@ class ScalarRecord(C.Structure):
     _fields_ = [("addr", C.c_uint64 * 64), ("code", C.c_uint8 * 64)]
 
 
+class JpegInfo(C.Structure):
+    """dvq_jpeg_info_t of include/dvq_hip.h"""
+    _fields_ = [("width", i32), ("height", i32), ("components", i32), ("restart_interval", i32), ("h_samp", i32 * 4), ("v_samp", i32 * 4),
+                ("qtab_index", i32 * 4), ("supported", i32), ("reserved", i32), ("coef_count", i64)]
+
+
+# DVQ_JPEG_* of include/dvq_hip.h: why dvq_jpeg_info leaves a file to another decoder
+(JPEG_SUPPORTED, JPEG_NOT_JPEG, JPEG_MALFORMED, JPEG_PROGRESSIVE, JPEG_ARITHMETIC, JPEG_SOF_KIND, JPEG_PRECISION, JPEG_COMPONENTS,
+ JPEG_SAMPLING, JPEG_COLORSPACE, JPEG_MULTISCAN) = range(11)
+
 # DVQ_SCALAR_* of include/dvq_hip.h: element types of dvq_scalar_push and dvq_codebook_health
 SCALAR_F32, SCALAR_BF16, SCALAR_F64, SCALAR_I32, SCALAR_I64, SCALAR_IMM, SCALAR_SKIP = range(7)
 SCALAR_PUSH_MAX, SCALAR_COLUMNS_MAX = 64, 256
@@ -170,6 +180,10 @@ SIGNATURES = {
     "dvq_fill_f32": (i32, [vp, f32, i64, vp]),
     "dvq_image_desc_bytes": (sz, []),
     "dvq_image_batch_transform": (i32, [vp, vp, vp, vp, i64, i32, i32, vp, vp]),
+    "dvq_jpeg_info": (i32, [vp, sz, C.POINTER(JpegInfo)]),
+    "dvq_jpeg_entropy_decode": (i32, [vp, sz, vp, i64, vp]),
+    "dvq_jpeg_desc_bytes": (sz, []),
+    "dvq_jpeg_batch_decode": (i32, [vp, vp, i64, vp, vp, vp]),
     "dvq_adamw_dev": (i32, [vp, vp, vp, vp, i64, vp, vp]),
     "dvq_grad_sqnorm_workspace_bytes": (sz, [i64]),
     "dvq_grad_sqnorm": (i32, [vp, i64, f32, i32, vp, sz, vp, vp]),

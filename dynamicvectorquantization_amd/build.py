@@ -19,8 +19,10 @@ HERE = os.path.dirname(os.path.abspath(__file__))
 CSRC = os.path.join(HERE, "csrc")
 OBJ = os.path.join(CSRC, "_obj")
 LIB = os.path.join(HERE, "libdvq_hip.so")
-SOURCES = ["vq.hip", "vq_trained.hip", "entropy.hip", "groupnorm.hip", "igemm.hip", "igemm_nt.hip", "igemm_tn.hip", "conv_halo.hip", "misc.hip", "lossnet.hip", "router.hip", "permuter.hip", "transformer.hip", "attention.hip", "attention2.hip", "imgproc.hip", "decode.hip", "cmdlist.hip", "metrics.hip", "nll.hip", "tokens.hip", "imagelog.hip", "trainlog.hip"]
+SOURCES = ["vq.hip", "vq_trained.hip", "entropy.hip", "groupnorm.hip", "igemm.hip", "igemm_nt.hip", "igemm_tn.hip", "conv_halo.hip", "misc.hip", "lossnet.hip", "router.hip", "permuter.hip", "transformer.hip", "attention.hip", "attention2.hip", "imgproc.hip", "decode.hip", "cmdlist.hip", "metrics.hip", "nll.hip", "tokens.hip", "imagelog.hip", "trainlog.hip", "jpeg.hip", "jpeg_host.cpp"]
 FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-munsafe-fp-atomics", "-Wno-unused-result"]
+# a .cpp source is host code with no HIP in it (jpeg_host.cpp: the Huffman pass, which also builds with g++ alone)
+HOST_FLAGS = ["-O3", "-std=c++17", "-fPIC"]
 # per-file additions.  vq.hip: no SLP vectorisation -- it pairs the scalar fp32 bookkeeping between the MFMAs of the argmin main loop
 # into v_pk_fma_f32 / v_pk_add_f32, which issue more slowly beside a busy matrix pipe than the two instructions they replace
 # imagelog.hip: no contraction -- its bytes are specified operation by operation in fp32 (docs/design/18-image-logging.md); an fma in
@@ -57,10 +59,10 @@ def build(force: bool = False, verbose: bool = True) -> str:
     objs = []
     for src in SOURCES:
         s = os.path.join(CSRC, src)
-        o = os.path.join(OBJ, src.replace(".hip", ".o"))
+        o = os.path.join(OBJ, os.path.splitext(src)[0] + ".o")
         objs.append(o)
         if force or _stale(o, [s] + hdrs):
-            jobs.append([hipcc] + flags + EXTRA_FLAGS.get(src, []) + ["-c", s, "-o", o])
+            jobs.append([hipcc] + (flags if src.endswith(".hip") else HOST_FLAGS) + EXTRA_FLAGS.get(src, []) + ["-c", s, "-o", o])
 
     def run(cmd):
         r = subprocess.run(cmd, capture_output=True, text=True)

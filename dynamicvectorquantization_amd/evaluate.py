@@ -381,10 +381,11 @@ def folder_dataset(root: str, limit: int | None = None):
 
 
 def image_batches(batch_size: int, size: int, device, images: str | None = None, synthetic: int = 0, limit: int | None = None,
-                  seed: int = 2021, num_workers: int = 8):
+                  seed: int = 2021, num_workers: int = 8, device_decode: bool = False):
     """NCHW fp32 [b,3,size,size] device batches in [-1, 1], streamed (never the whole set in host memory):
     synthetic > 0: synth.half_flat_images per batch; images = *.npy: memory-mapped [N,3,H,W] fp32, read per batch; images = folder:
-    decoded on host threads, transformed on the GPU (data.GpuBatchLoader, the eval transform: Resize + CenterCrop)"""
+    decoded on host threads, transformed on the GPU (data.GpuBatchLoader, the eval transform: Resize + CenterCrop); device_decode: its
+    JPEG files through the device decoder (docs/design/23-device-jpeg.md) -- the same pixels, less host work per image"""
     import numpy as np
 
     from . import data, synth
@@ -401,7 +402,7 @@ def image_batches(batch_size: int, size: int, device, images: str | None = None,
             yield torch.from_numpy(np.array(a[i:min(i + batch_size, n)], dtype=np.float32)).to(device)     # a writable copy of the slice
     elif images is not None:
         loader = data.GpuBatchLoader(folder_dataset(images, limit), batch_size, device, size=size, shuffle=False,
-                                     num_workers=num_workers, drop_last=False)
+                                     num_workers=num_workers, drop_last=False, device_decode=device_decode)
         for b in loader:
             yield b["image"]
     else:
@@ -438,6 +439,9 @@ def add_eval_args(ap) -> None:
     ap.add_argument("--synthetic", type=int, default=0, help="N half-flat synthetic images instead of a dataset")
     ap.add_argument("--limit", type=int, default=None, help="evaluate the first N images only")
     ap.add_argument("--dtype", default="bf16", choices=["bf16", "fp32", "fp32x3"])
+    ap.add_argument("--device_jpeg", action="store_true",
+                    help="image folders: decode JPEG files on the GPU after a Huffman pass on host threads (same pixels as PIL; other "
+                         "files are decoded by PIL as before)")
 
 
 def image_source(opt, ap) -> str | None:

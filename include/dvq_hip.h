@@ -717,6 +717,53 @@ size_t dvq_image_desc_bytes(void);
 int dvq_image_batch_transform(const uint8_t* src, const void* desc, const int32_t* tables, uint8_t* tmp, int64_t B, int S,
                               int max_rows, float* out, dvq_stream_t stream);
 
+/* ---- device JPEG decode (docs/design/23-device-jpeg.md): the Huffman pass on the host, everything after the coefficients on the GPU,
+ * pixel for pixel what libjpeg-turbo's default path gives (integer "islow" IDCT, fancy upsampling, fixed-point colour).
+ *
+ * Host pass (csrc/jpeg_host.cpp: no GPU, no allocation, no state; safe to call from many threads on any bytes).
+ * dvq_jpeg_info parses the markers up to the first SOS and fills `info`.  info->supported is DVQ_JPEG_SUPPORTED for what the decoder
+ * takes: 8-bit baseline or extended-sequential Huffman (SOF0 / SOF1), one interleaved scan, 1 component or 3 (YCbCr) with luma sampling
+ * 1x1, 2x1 or 2x2 over 1x1 chroma; otherwise the reason, and the caller decodes the file some other way.  Returns DVQ_EINVAL only for
+ * null pointers.
+ * dvq_jpeg_entropy_decode byte-unstuffs and Huffman-decodes every MCU of a supported stream (restart markers included):
+ *   coef  int16 [component][block_row][block_col][64], natural (de-zigzagged) order, NOT dequantised, the block grid of each component
+ *         padded to whole MCUs; info->coef_count elements (coef_capacity smaller: DVQ_EWORKSPACE)
+ *   qtab  uint16 [component][64], natural order: the quantisation table of each component
+ * A stream that is unsupported, malformed or ends early returns DVQ_EINVAL with the message in dvq_last_error; it never reads outside
+ * [data, data + n) and never writes past coef_capacity. */
+enum {
+    DVQ_JPEG_SUPPORTED = 0,
+    DVQ_JPEG_NOT_JPEG = 1,     /* no SOI at the start */
+    DVQ_JPEG_MALFORMED = 2,    /* markers cut short or inconsistent, tables missing, dimensions of 0 */
+    DVQ_JPEG_PROGRESSIVE = 3,  /* SOF2 */
+    DVQ_JPEG_ARITHMETIC = 4,   /* SOF9 .. SOF15 */
+    DVQ_JPEG_SOF_KIND = 5,     /* lossless or hierarchical frames */
+    DVQ_JPEG_PRECISION = 6,    /* not 8 bits per sample */
+    DVQ_JPEG_COMPONENTS = 7,   /* neither 1 nor 3 components (CMYK, YCCK) */
+    DVQ_JPEG_SAMPLING = 8,     /* a sampling grid other than 1x1, 2x1, 2x2 luma over 1x1 chroma */
+    DVQ_JPEG_COLORSPACE = 9,   /* 3 components that are not YCbCr (Adobe transform 0, or ids R G B without JFIF) */
+    DVQ_JPEG_MULTISCAN = 10    /* the first scan does not hold every component */
+};
+typedef struct dvq_jpeg_info_t {
+    int32_t width, height, components, restart_interval;
+    int32_t h_samp[4], v_samp[4], qtab_index[4]; /* per component; a one-component stream reports 1x1 */
+    int32_t supported;                           /* DVQ_JPEG_* */
+    int32_t reserved;
+    int64_t coef_count;                          /* int16 elements dvq_jpeg_entropy_decode writes; 0 unless supported */
+} dvq_jpeg_info_t;
+int dvq_jpeg_info(const uint8_t* data, size_t n, dvq_jpeg_info_t* info);
+int dvq_jpeg_entropy_decode(const uint8_t* data, size_t n, int16_t* coef, int64_t coef_capacity, uint16_t* qtab);
+/* Device stage (csrc/jpeg.hip), two launches for a whole batch of differently sized images:
+ *   (a) dequantise, 8x8 inverse DCT, + 128, clamp -> uint8 component planes in planes_tmp (each plane as large as its padded block grid)
+ *   (b) fancy chroma upsampling on the unpadded chroma planes, YCbCr -> RGB, packed uint8 [h][w][3] at each image's offset in rgb_out
+ *       (a one-component image writes its sample to all three channels)
+ * coef: the batch's coefficients back to back (device); desc: B records of dvq_jpeg_desc_bytes() bytes in device memory (layout: JpegDesc
+ * in csrc/jpeg.hip, mirrored by data._JpegDesc) with per image its offsets into coef, planes_tmp and rgb_out, size, sampling, tables and
+ * its share of the two grids; a record with 0 components is skipped (its slot in rgb_out is the caller's to fill).  rgb_out is what
+ * dvq_image_batch_transform reads as `src`. */
+size_t dvq_jpeg_desc_bytes(void);
+int dvq_jpeg_batch_decode(const int16_t* coef, const void* desc, int64_t B, uint8_t* planes_tmp, uint8_t* rgb_out, dvq_stream_t stream);
+
 /* ---- reconstruction evaluation (no reference kernel: its codebook-usage tool collects codes on the host,
  * scripts/tools/codebook_usage_dqvae.py:52-69; SSIM as Wang et al. 2004) -----------------------------------------------------------
  * dvq_recon_metrics: x (target), y (reconstruction) NCHW fp32 [B][3][H][W] in [-1, 1]; per image fp64 outputs

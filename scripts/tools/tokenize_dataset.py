@@ -87,8 +87,9 @@ def tensor_view_batches(batches, views, lo, hi):
         i += b
 
 
-def decoded_view_batches(ds, views, lo, hi, batch_size, size, device, seed, workers):
-    """decoded images (a folder, the YAML's dataset): data.plan_batch per view with the view's crops / flips, the transforms on the GPU"""
+def decoded_view_batches(ds, views, lo, hi, batch_size, size, device, seed, workers, device_decode=False):
+    """decoded images (a folder, the YAML's dataset): data.plan_batch per view with the view's crops / flips, the transforms on the GPU.
+    device_decode: JPEG files are decoded on the GPU too, once per batch (data.decode_batch_gpu); every view reads that buffer"""
     from concurrent.futures import ThreadPoolExecutor
 
     import numpy as np
@@ -97,22 +98,29 @@ def decoded_view_batches(ds, views, lo, hi, batch_size, size, device, seed, work
     with ThreadPoolExecutor(max(1, workers)) as pool:
         for i in range(lo, hi, batch_size):
             idx = list(range(i, min(hi, i + batch_size)))
-            ex = list(pool.map(ds.__getitem__, idx))
-            ims = [e["image_u8"] for e in ex]
+            ex = list(pool.map((lambda j: ds.example(j, True)) if device_decode else ds.__getitem__, idx))
+            dec = None
+            if any("jpeg" in e for e in ex):
+                dec = data.decode_batch_gpu([e["jpeg"] if "jpeg" in e else e["image_u8"] for e in ex], device)
+            sizes = dec["sizes"] if dec else [(int(e["image_u8"].shape[1]), int(e["image_u8"].shape[0])) for e in ex]
             out = []
             for v, name in enumerate(views):
                 crops = flips = None
                 if name == "flip":
-                    flips = [True] * len(ims)
+                    flips = [True] * len(ex)
                 elif name.startswith("random:"):
                     crops, flips = [], []
-                    for j, im in zip(idx, ims):
+                    for j, (w, h) in zip(idx, sizes):
                         rng = np.random.default_rng([seed, j, v])
-                        nw, nh = data.resized_size(int(im.shape[1]), int(im.shape[0]), size)
+                        nw, nh = data.resized_size(w, h, size)
                         cy, cx = int(rng.integers(0, nh - size + 1)), int(rng.integers(0, nw - size + 1))      # RandomCrop.get_params: i, j
                         crops.append((cx, cy))
                         flips.append(bool(rng.random() < 0.5))
-                out.append(data.transform_batch_gpu(data.plan_batch(ims, size, crops=crops, flips=flips), device))
+                if dec:
+                    plan = data.plan_batch_sizes(sizes, size, crops=crops, flips=flips, src_offs=dec["offs"])
+                    out.append(data.transform_batch_device(plan, dec["rgb"], device))
+                else:
+                    out.append(data.transform_batch_gpu(data.plan_batch([e["image_u8"] for e in ex], size, crops=crops, flips=flips), device))
             labels = np.array([int(e.get("class_label", -1)) for e in ex], dtype=np.int64)
             yield out, labels, np.array(idx)
 
@@ -161,9 +169,9 @@ def main():
     if ds is None:
         if any(v.startswith("random:") for v in views):
             ap.error("--views random:N draws crops of decoded images: give a folder (--images DIR) or --split")
-        batches = tensor_view_batches(E.image_batches(opt.batch_size, size, dev, source, opt.synthetic, n), views, lo, hi)
+        batches = tensor_view_batches(E.image_batches(opt.batch_size, size, dev, source, opt.synthetic, n, device_decode=opt.device_jpeg), views, lo, hi)
     else:
-        batches = decoded_view_batches(ds, views, lo, hi, opt.batch_size, size, dev, opt.seed, opt.num_workers)
+        batches = decoded_view_batches(ds, views, lo, hi, opt.batch_size, size, dev, opt.seed, opt.num_workers, opt.device_jpeg)
     writer = T.TokenShardWriter(opt.out, hw1, hw2, codebook_of(model.quantize)[1], views, shard_size=opt.shard_size,
                                 compute_dtype=E.dtype_name(), fingerprint=T.first_stage_fingerprint(model), dataset=described, part=part)
     stats = T.tokenize_batches(model, batches, writer)

@@ -59,6 +59,9 @@ def get_parser():
     p.add_argument("--real_data", action="store_true",
                    help="instantiate the config's `data:` section (data.build.DataModuleFromConfig -> GPU input pipeline, "
                         "$DVQ_IMAGENET_ROOT/train|val) instead of synthetic batches")
+    p.add_argument("--device_jpeg", action="store_true",
+                   help="with --real_data: JPEG files go through the device decoder (Huffman pass on host threads, inverse DCT, upsampling "
+                        "and colour in HIP kernels; same pixels as PIL); other files are decoded by PIL as before")
     p.add_argument("--token_data", type=str, default="",
                    help="stage 2 only: train from this token set (scripts/tools/tokenize_dataset.py) instead of images -- no first-stage "
                         "forward, no image decoding")
@@ -192,6 +195,10 @@ def run(rank, world, opt, unknown):
         # Built BEFORE the Trainer: configure_optimizers() bakes steps_per_epoch / training_steps into the LR schedules
         config.data.params["device"] = str(dev)
         config.data.params["size"] = size
+        if opt.device_jpeg:
+            config.data.params["device_decode"] = True      # docs/design/23-device-jpeg.md
+            if rank == 0:
+                print("[train.py] device JPEG decode: Huffman pass on host threads, the rest on the GPU")
         dm = cfg.instantiate_from_config(config.data)
         loader = dm.train_dataloader()
         loader.rng = __import__("numpy").random.default_rng(opt.seed + 977 * rank)
@@ -314,6 +321,8 @@ def main():
     opt, unknown = get_parser().parse_known_args()
     if not opt.base and not opt.resume:
         raise SystemExit("-b/--base <config.yaml> is required")
+    if opt.device_jpeg and not opt.real_data:
+        raise SystemExit("--device_jpeg needs --real_data")
     import torch
     if "WORLD_SIZE" in os.environ:          # launched by torchrun
         return run(int(os.environ["RANK"]), int(os.environ["WORLD_SIZE"]), opt, unknown)
