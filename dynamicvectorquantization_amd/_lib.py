@@ -190,6 +190,12 @@ SIGNATURES = {
     "dvq_adamw_clip_dev": (i32, [vp, vp, vp, vp, i64, vp, vp, vp]),
     "dvq_ema_update": (i32, [vp, vp, i64, vp, vp, vp]),
     "dvq_swap_f32": (i32, [vp, vp, i64, vp]),
+    "dvq_segment_stats_workspace_bytes": (sz, [i64, i64]),
+    "dvq_segment_stats_state_bytes": (sz, [i64]),
+    "dvq_segment_plan_bytes": (sz, [vp, i64, i64]),
+    "dvq_segment_plan_build": (i32, [vp, i64, i64, vp, sz]),
+    "dvq_segment_stats": (i32, [vp, vp, i64, vp, i64, vp, sz, vp, sz, vp, i32, vp, vp]),
+    "dvq_copy_f32_armed": (i32, [vp, vp, i64, vp, vp]),
     "dvq_set_f32x8": (i32, [vp, f32, f32, f32, f32, f32, f32, f32, f32, vp]),
     "dvq_sample_rows": (i32, [vp, i64, i64, vp, vp]),
     "dvq_add_uniform": (i32, [vp, i64, f32, vp, vp]),

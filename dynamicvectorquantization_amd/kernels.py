@@ -1276,6 +1276,66 @@ def swap_f32(a, b):
     check(lib().dvq_swap_f32(_p(a), _p(b), a.numel(), _s()), "dvq_swap_f32")
 
 
+# ---- per-segment statistics (docs/design/24-norm-tracking.md) ------------------------------------------------------------------
+class SegmentPlan:
+    """the segment table of segment_stats: `offsets` (S + 1 ascending element offsets, 0 .. n) as the host array the library checks on
+    every call, and the plan the library built from it -- offsets, first chunk of each segment, one record per chunk -- in device
+    memory.  Built once at set-up; a bad table raises DvqError (DVQ_ESHAPE)."""
+
+    def __init__(self, offsets, device):
+        offs = [int(o) for o in offsets]
+        self.S, self.n = len(offs) - 1, (offs[-1] if offs else 0)
+        self.offsets = (C.c_int64 * max(1, len(offs)))(*offs)
+        nbytes = int(lib().dvq_segment_plan_bytes(self.offsets, self.S, self.n))
+        if nbytes == 0:
+            raise _lib.DvqError(f"segment plan: {self.S} segments over {self.n} elements: the offsets must rise from 0 to n in steps >= 1 (DVQ_ESHAPE)")
+        host = torch.empty(nbytes // 8, dtype=torch.int64)
+        check(lib().dvq_segment_plan_build(self.offsets, self.S, self.n, C.c_void_p(host.data_ptr()), nbytes), "dvq_segment_plan_build")
+        self.nchunks = int(host[2])
+        self.plan = host.to(device)
+
+    @property
+    def plan_bytes(self):
+        return self.plan.numel() * 8
+
+
+def segment_stats_workspace(n, S, device):
+    """the chunk partials of segment_stats for any table of S segments over n elements; passes on one stream may share it"""
+    return torch.empty(int(lib().dvq_segment_stats_workspace_bytes(int(n), int(S))) // 8, dtype=torch.int64, device=device)
+
+
+def segment_stats_state(S, device):
+    """state block of segment_stats before any launch (include/dvq_hip.h): zero, first_bad_call = -1"""
+    S = int(S)
+    host = torch.zeros(int(lib().dvq_segment_stats_state_bytes(S)) // 8, dtype=torch.int64)
+    host[3 * S:4 * S] = -1
+    return host.to(device)
+
+
+def segment_stats_views(state, S) -> dict:
+    """named views of a state block, or of a host copy of one"""
+    S = int(S)
+    return {"sumsq": state[:S].view(torch.float64), "nonfinite": state[S:2 * S], "nonfinite_total": state[2 * S:3 * S],
+            "first_bad_call": state[3 * S:4 * S], "calls": state[4 * S:5 * S], "absmax": state[5 * S:].view(torch.float32)[:S]}
+
+
+def segment_stats(a, b, plan, workspace, state, sticky=False, armed=None):
+    """state <- per-segment {sum of squares, abs-max, Inf / NaN count} of the flat fp32 buffer a, or of a - b (exact in fp64); two
+    launches, ordered sums, no host read.  sticky: also the running counters.  armed: device int32, 0 = both launches return at once"""
+    assert a.dtype == torch.float32 and a.numel() == plan.n and (b is None or (b.dtype == torch.float32 and b.numel() == plan.n))
+    check(lib().dvq_segment_stats(_p(a), _p(b), plan.n, plan.offsets, plan.S, _p(plan.plan), plan.plan_bytes, _p(workspace),
+                                  workspace.numel() * workspace.element_size(), _p(state), int(bool(sticky)), _p(armed), _s()),
+          "dvq_segment_stats")
+    return state
+
+
+def copy_f32_armed(dst, src, armed=None):
+    """dst <- src over flat fp32 buffers in one launch that returns at once when the device int32 `armed` is 0"""
+    assert dst.dtype == torch.float32 and src.dtype == torch.float32 and dst.numel() == src.numel()
+    check(lib().dvq_copy_f32_armed(_p(dst), _p(src), dst.numel(), _p(armed), _s()), "dvq_copy_f32_armed")
+    return dst
+
+
 def set_f32x8(dst, values):
     """dst[0:8] <- values (by-value launch arguments: safe to call with the host running many steps ahead)"""
     vals = [float(x) for x in values] + [0.0] * (8 - len(values))

@@ -290,6 +290,9 @@ class MetricsLogger:
                 for i, st in enumerate(trainer.grad_stats()):
                     if st:
                         row.update({f"grad_norm_opt{i}": st["norm"], f"clip_coef_opt{i}": st["coef"], f"skipped_opt{i}": st["skipped"]})
+            nt = getattr(trainer, "norm_tracker", None)          # per-parameter norm tracking: the totals its row of THIS step left
+            if nt is not None and nt.last_row[0] == step:
+                row.update(nt.last_row[1])
             self._write(row, step // spe, step)
         if (step + 1) % spe == 0:
             self.epoch_end(step // spe, step)

@@ -118,6 +118,7 @@ class HipAdam(torch.optim.Optimizer):
         self._fstate = None
         self._guard = None            # set_grad_guard: dict(clip, skip, ws, gstat)
         self._ema = None              # set_weight_ema: dict(decay, warmup, rec, last); the shadow buffer is self.flat_e
+        self._norm = None             # set_norm_tracking: dict(plan, names, ws, grad / weight / update state blocks, snap, armed, ...)
 
     def set_weight_ema(self, decay=0.0, warmup=True):
         """Exponential moving average of this optimizer's parameters (docs/design/20-weight-ema.md): after every step()
@@ -188,6 +189,69 @@ class HipAdam(torch.optim.Optimizer):
         None when neither clipping nor the guard is enabled."""
         return K.read_grad_stats(self._guard["gstat"]) if self._guard else None
 
+    def set_norm_tracking(self, names, track_updates=True):
+        """Per-parameter gradient, weight and update norms on the device (docs/design/24-norm-tracking.md; Lightning's
+        `track_grad_norm`).  `names`: {id(p): dotted name of model.named_parameters()}; None switches the feature off and frees its
+        buffers.  Every step() then takes the statistics of flat_g per parameter (sum of squares, abs-max, Inf / NaN count, with
+        running counts and the first offending step -- BEFORE clipping, which never rewrites flat_g); steps armed through
+        arm_norm_row() also take those of flat_p after the update and, with `track_updates`, of flat_p minus a snapshot taken in
+        front of Adam.  Unarmed, the weight / update launches return at once: a recorded step carries them, only row steps pay.
+        Everything is allocated here, never inside step()."""
+        if self.flat is None:
+            raise ValueError("set_norm_tracking works on a flattened HipAdam only (call flatten() first): the per-tensor path has no "
+                             "flat buffers to cut into segments")
+        if names is None:
+            self._norm = None
+            return
+        params = self.flat.params
+        offsets = [0]
+        for p in params:
+            offsets.append(offsets[-1] + p.numel())
+        dev = self.flat.flat_p.device
+        plan = K.SegmentPlan(offsets, dev)
+        S = plan.S
+        self._norm = {"plan": plan, "names": [names.get(id(p), f"param{i}") for i, p in enumerate(params)],
+                      "numel": [p.numel() for p in params], "track_updates": bool(track_updates),
+                      "ws": K.segment_stats_workspace(plan.n, S, dev),
+                      "grad": K.segment_stats_state(S, dev), "weight": K.segment_stats_state(S, dev),
+                      "update": K.segment_stats_state(S, dev) if track_updates else None,
+                      "snap": torch.empty_like(self.flat.flat_p) if track_updates else None,
+                      "armed": torch.zeros(1, dtype=torch.int32, device=dev),
+                      "bits": torch.tensor([0, 1], dtype=torch.int32, device=dev).view(torch.float32),      # the two values of `armed`
+                      "arm_next": True}
+        self._prepared = False
+
+    def arm_norm_row(self, armed=True):
+        """whether the NEXT step() takes the weight / update statistics (uploaded by prepare_step; the Trainer calls this before
+        every step, a bare optimizer arms every step)"""
+        if self._norm is not None:
+            self._norm["arm_next"] = bool(armed)
+            self._prepared = False
+
+    def norm_stats(self):
+        """{name: {numel, grad_norm, grad_absmax, grad_nonfinite, grad_nonfinite_total, first_bad_step, weight_norm, update_norm,
+        update_ratio}} -- the gradient entries of the last step(), the last three of the most recent armed step (update_norm /
+        update_ratio None without track_updates).  first_bad_step: the optimizer's 0-based step index, -1 = never.  A host read
+        (synchronises): between steps only.  None with the feature off."""
+        nt = self._norm
+        if nt is None:
+            return None
+        S = nt["plan"].S
+        g = {k: v.numpy() for k, v in K.segment_stats_views(nt["grad"].cpu(), S).items()}
+        w = {k: v.numpy() for k, v in K.segment_stats_views(nt["weight"].cpu(), S).items()}
+        u = {k: v.numpy() for k, v in K.segment_stats_views(nt["update"].cpu(), S).items()} if nt["update"] is not None else None
+        base = int(self._fstate["step"]) - int(g["calls"][0])      # optimizer step index of the block's first launch
+        out = {}
+        for i, name in enumerate(nt["names"]):
+            wn = math.sqrt(float(w["sumsq"][i]))
+            un = math.sqrt(float(u["sumsq"][i])) if u is not None else None
+            first = int(g["first_bad_call"][i])
+            out[name] = {"numel": int(nt["numel"][i]), "grad_norm": math.sqrt(float(g["sumsq"][i])), "grad_absmax": float(g["absmax"][i]),
+                         "grad_nonfinite": int(g["nonfinite"][i]), "grad_nonfinite_total": int(g["nonfinite_total"][i]),
+                         "first_bad_step": first + base if first >= 0 else -1, "weight_norm": wn, "update_norm": un,
+                         "update_ratio": (un / wn if wn > 0.0 else (0.0 if un == 0.0 else math.inf)) if un is not None else None}
+        return out
+
     def flatten(self) -> FlatParams:
         if self.flat is None:
             allp = [p for g in self.param_groups for p in g["params"] if p.requires_grad]
@@ -221,6 +285,9 @@ class HipAdam(torch.optim.Optimizer):
         if em is not None:                 # 1 - d of the NEXT EMA update, in fp64 here, rounded to fp32 once on its way to the device
             em["last"] = ema_decay_at(self._fstate["ema_updates"] + 1, em["decay"], em["warmup"])
             K.set_f32x8(em["rec"], [1.0 - em["last"]])
+        nt = self._norm
+        if nt is not None:                 # the 4-byte `armed` record of the NEXT step: a kernel launch, like the uploads above
+            K.copy_f32_armed(nt["armed"].view(torch.float32), nt["bits"][1:2] if nt["arm_next"] else nt["bits"][0:1])
         self._prepared = True
 
     @torch.no_grad()
@@ -232,8 +299,13 @@ class HipAdam(torch.optim.Optimizer):
             self._prepared = False
             st["step"] += 1
             gd = self._guard
+            nt = self._norm
+            if nt is not None:             # per-parameter gradient statistics, EVERY step (sticky counters): a NaN is localised after the fact
+                K.segment_stats(self.flat.flat_g, None, nt["plan"], nt["ws"], nt["grad"], sticky=True)
             if gd is not None:             # norm / coefficient / finite flag of the WHOLE buffer (all groups), on the device
                 K.grad_sqnorm(self.flat.flat_g, gd["ws"], gd["gstat"], gd["clip"], gd["skip"])
+            if nt is not None and nt["snap"] is not None:      # row steps: the parameters in front of Adam
+                K.copy_f32_armed(nt["snap"], self.flat.flat_p, nt["armed"])
             for gi, (off, n) in enumerate(self._segments):
                 if n == 0:
                     continue
@@ -245,6 +317,10 @@ class HipAdam(torch.optim.Optimizer):
             if self._ema is not None:      # ONE launch over the whole buffer (all groups), after Adam; follows the guard's skip
                 K.ema_update(self.flat_e, self.flat.flat_p, self._ema["rec"], gd["gstat"] if gd is not None else None)
                 st["ema_updates"] += 1
+            if nt is not None:             # row steps: weight norms of the updated parameters, update norms against the snapshot
+                K.segment_stats(self.flat.flat_p, None, nt["plan"], nt["ws"], nt["weight"], armed=nt["armed"])
+                if nt["snap"] is not None:
+                    K.segment_stats(self.flat.flat_p, nt["snap"], nt["plan"], nt["ws"], nt["update"], armed=nt["armed"])
             rt.bump_group_epoch(id(self))      # only this optimizer's packed weights are stale
             return
         for group in self.param_groups:
@@ -449,7 +525,8 @@ class Trainer:
     static input buffers.  `DVQ_STEP_GRAPH=0` (or use_graph=False) keeps every step eager."""
 
     def __init__(self, model, max_steps, log_every=0, use_graph=None, graph_after=3, gradient_clip_val=0.0, skip_nonfinite=False,
-                 ema_decay=0.0, ema_warmup=True, deterministic=False, metrics_logger=None):
+                 ema_decay=0.0, ema_warmup=True, deterministic=False, metrics_logger=None, track_grad_norm=-1, track_updates=True,
+                 norm_every=50, norm_depth=0, norm_logdir=None):
         self.model, self.max_steps, self.log_every = model, max_steps, log_every
         # scalar logs (metrics.MetricsLogger, docs/design/22-metrics-logging.md): the model's logged scalars gathered on the device at the
         # end of every step, rows written every log_every_n_steps steps and at epoch ends.  None (the default): no launch, no file
@@ -481,6 +558,13 @@ class Trainer:
         broadcast_model(model)             # identical start on every rank (DDP's parameter / buffer broadcast), not just equal seeds
         if self.ema_decay != 0.0:          # after the broadcast: flat_e starts as a copy of the weights every rank holds
             self.opts[0].set_weight_ema(self.ema_decay, self.ema_warmup)
+        # Lightning's Trainer(track_grad_norm=...) (docs/design/24-norm-tracking.md): per-parameter gradient / weight / update norms of
+        # every optimizer on the device; -1 (the default): off -- no launch, no buffer, no file.  2 / "inf" choose what the total keys
+        # report.  Rows at the metrics logger's cadence, or every `norm_every` steps without one; norms.csv in `norm_logdir` (default:
+        # the metrics logger's directory; neither: statistics through norm_stats() only)
+        self.norm_every = metrics_logger.log_every_n_steps if metrics_logger is not None else max(1, int(norm_every))
+        self._norm_out = (norm_depth, norm_logdir or (metrics_logger.logdir if metrics_logger is not None else None))
+        self.set_norm_tracking(track_grad_norm, track_updates)
         self.check_every = int(rt.switch("DVQ_DP_CHECK_EVERY"))
         import inspect
         # Lightning passes optimizer_idx only to modules that declare it (two-optimizer stage 1); stage 2 has one optimizer
@@ -500,9 +584,11 @@ class Trainer:
         lg = self.metrics_logger
         if lg is None:
             out = self._train_step(batch, batch_idx)
+            self._norm_row()
         else:
             lrs = [o.param_groups[0]["lr"] for o in self.opts]       # of the step about to run: the schedulers advance inside it
             out = self._train_step(batch, batch_idx)
+            self._norm_row()                                         # before the metrics row, which takes its totals
             lg.after_step(self, int(self.model.global_step) - 1, batch, lrs)
         if self.check_every and (int(self.model.global_step) % self.check_every) == 0 and not replicas_equal(self.model):
             raise RuntimeError(f"data-parallel replicas diverged at global step {self.model.global_step}")
@@ -526,9 +612,56 @@ class Trainer:
                 return self._replay(batch)
         return self._eager_step(batch, batch_idx)
 
-    def _eager_step(self, batch, batch_idx):
+    def _prepare_opts(self):
+        """hyper-parameters of the step about to run -> device memory, outside any capture and before any replay; with norm tracking
+        also whether it is a row step (the `armed` record the recorded weight / update launches read)"""
+        if self.norm_tracker is not None:
+            armed = self._is_norm_row(int(self.model.global_step))
+            for o in self.opts:
+                o.arm_norm_row(armed)
         for o in self.opts:
-            o.prepare_step()                       # hyper-parameters of this step -> device memory
+            o.prepare_step()
+
+    def set_norm_tracking(self, track_grad_norm=-1, track_updates=True):
+        """switch per-parameter norm tracking of every optimizer between steps (-1 = off: the buffers are freed, the sticky counters
+        with them); a step recorded under the other setting is not replayed: the signature differs"""
+        from . import normtrack
+        self.track_grad_norm, self.track_updates = normtrack.parse_track_grad_norm(track_grad_norm), bool(track_updates)
+        if self.track_grad_norm == -1:
+            for o in self.opts:
+                o.set_norm_tracking(None)
+            self.norm_tracker = None
+            return
+        names = {id(p): n for n, p in self.model.named_parameters()}
+        for o in self.opts:
+            o.set_norm_tracking(names, self.track_updates)
+        self.norm_tracker = normtrack.NormTracker(self.track_grad_norm, *self._norm_out)
+
+    def _is_norm_row(self, step):
+        return (step + 1) % self.norm_every == 0
+
+    def _norm_row(self):
+        """behind a row step: read the statistics (a host read, the step has been issued) and hand them to the tracker"""
+        nt = self.norm_tracker
+        step = int(self.model.global_step) - 1
+        if nt is None or not self._is_norm_row(step):
+            return
+        lg = self.metrics_logger
+        from .metrics import TensorBoardWriter
+        tb = next((w for w in lg.writers if isinstance(w, TensorBoardWriter)), None) if lg is not None else None
+        spe = max(1, int(getattr(self.model, "steps_per_epoch", 1) or 1))
+        nt.row(step, step // spe, self.norm_stats(), tensorboard=tb)
+
+    def norm_stats(self):
+        """one {parameter name: {numel, grad_norm, grad_absmax, grad_nonfinite, grad_nonfinite_total, first_bad_step, weight_norm,
+        update_norm, update_ratio}} per optimizer (HipAdam.norm_stats): the gradient entries of the last step, eager or replayed,
+        the last three of the most recent row step.  A host read: between steps only.  None with the feature off."""
+        if self.norm_tracker is None:
+            return None
+        return [o.norm_stats() for o in self.opts]
+
+    def _eager_step(self, batch, batch_idx):
+        self._prepare_opts()                       # hyper-parameters of this step -> device memory
         return self._step_body(batch, batch_idx)
 
     def _step_body(self, batch, batch_idx):
@@ -584,7 +717,9 @@ class Trainer:
             sig = sig + (("deterministic",),)
         # whether the EMA launch is part of the step; the decay is device data and not part of the signature
         sig = sig + (("ema",) if self.ema_enabled else ())
-        return sig + (("metrics",) if self.metrics_logger is not None else ())        # likewise the scalar push
+        sig = sig + (("metrics",) if self.metrics_logger is not None else ())         # likewise the scalar push
+        # and the norm-tracking launches; which steps are rows is device data (`armed`) and not part of the signature
+        return sig + ((("norms", self.track_grad_norm, self.track_updates),) if self.norm_tracker is not None else ())
 
     def _py_state(self):
         return ([o._fstate["step"] for o in self.opts], [s["scheduler"].state_dict() for s in self.scheds],
@@ -609,8 +744,7 @@ class Trainer:
         static = {k: (v.clone() if torch.is_tensor(v) else v) for k, v in batch.items()}
         saved = self._py_state()
         logged = dict(getattr(self.model, "_logged", {}))
-        for o in self.opts:
-            o.prepare_step()
+        self._prepare_opts()
         sg = rt.StepGraph(dev)
         try:
             with sg.capture():
@@ -637,8 +771,7 @@ class Trainer:
         for k, v in batch.items():
             if torch.is_tensor(v) and v.data_ptr() != g["static"][k].data_ptr():
                 g["static"][k].copy_(v, non_blocking=True)
-        for o in self.opts:
-            o.prepare_step()
+        self._prepare_opts()
         g["sg"].replay()
         # host-side bookkeeping the recorded launches do not carry
         for o, sc in zip(self.opts, self.scheds):

@@ -664,6 +664,40 @@ int dvq_adamw_clip_dev(float* p, const float* g, float* m, float* v, int64_t n, 
 int dvq_ema_update(float* e, const float* p, int64_t n, const float* rec, const void* gstat, dvq_stream_t stream);
 /* exchange the contents of two non-overlapping fp32 buffers in one launch, without a third buffer (overlap: DVQ_EINVAL) */
 int dvq_swap_f32(float* a, float* b, int64_t n, dvq_stream_t stream);
+/* Per-segment statistics of a flat fp32 buffer -- per-parameter gradient, weight and update norms (Lightning's --track_grad_norm;
+ * docs/design/24-norm-tracking.md).  The buffer [0, n) is cut into S back-to-back segments by S + 1 ascending element offsets
+ * (offsets[0] = 0, offsets[S] = n, every length >= 1); the element value is a[i], or with b != NULL (double)a[i] - (double)b[i].
+ * The ordered two-stage form of dvq_grad_sqnorm, segmented: every segment is cut into chunks of 32768 elements (the last one shorter),
+ * (1) one workgroup per chunk stores one partial into `workspace` with plain stores, (2) one wave per segment adds that segment's
+ * partials in index order and writes the segment's row of
+ *   state = { double sumsq[S]            sum of v^2 over the finite elements, squares in fp64;
+ *             int64  nonfinite[S]        Inf / NaN elements of THIS launch (with b: either operand), left out of the other two;
+ *             int64  nonfinite_total[S]  sticky: += nonfinite;
+ *             int64  first_bad_call[S]   sticky: the launch counter at the first launch with nonfinite != 0, -1 before (set by the caller);
+ *             int64  calls[S]            sticky: the launch counter, one copy per segment, += 1 per launch;
+ *             float  absmax[S] }         max |v| over the finite elements, rounded to fp32
+ * (dvq_segment_stats_state_bytes(S) bytes, 8-byte aligned; the caller zeroes it and sets first_bad_call to -1 before the first launch).
+ * sticky == 0 leaves the three sticky arrays untouched.  No atomics; the order of every addition depends on the offsets alone: equal
+ * inputs give bit-equal state on every launch, whatever the alignment of a and b (16-byte loads where a chunk starts on a 16-byte
+ * boundary, 4-byte loads elsewhere, the same element-to-accumulator assignment in both).  Never counted as an unordered launch.
+ * The chunk table lives in device memory: dvq_segment_plan_build writes the plan (the offsets, each segment's first chunk, one
+ * {start, segment, length} record per chunk) into HOST memory, dvq_segment_plan_bytes(offsets, S, n) bytes (0 for a bad table); the
+ * caller copies it to the device once.  `offsets` is a HOST pointer in all three calls: dvq_segment_stats checks it on every call
+ * (DVQ_ESHAPE for a table that is not ascending from 0 to n, or a plan whose size does not belong to it; DVQ_EWORKSPACE for a
+ * workspace below dvq_segment_stats_workspace_bytes(n, S)) before it launches anything; that plan_dev holds the plan built from the same
+ * offsets is the caller's contract.
+ * armed: NULL, or a device int32 -- when it is 0 both kernels return before touching any other memory (one wave-uniform load, like the
+ * skip flag of dvq_adamw_clip_dev), so a recorded step carries the launches and only row steps pay for them. */
+size_t dvq_segment_stats_workspace_bytes(int64_t n, int64_t S);
+size_t dvq_segment_stats_state_bytes(int64_t S);
+size_t dvq_segment_plan_bytes(const int64_t* offsets, int64_t S, int64_t n);
+int dvq_segment_plan_build(const int64_t* offsets, int64_t S, int64_t n, void* plan_host, size_t plan_host_bytes);
+int dvq_segment_stats(const float* a, const float* b, int64_t n, const int64_t* offsets, int64_t S, const void* plan_dev,
+                      size_t plan_bytes, void* workspace, size_t workspace_bytes, void* state, int sticky, const int* armed,
+                      dvq_stream_t stream);
+/* dst[i] <- src[i], 16-byte accesses when both are 16-byte aligned; returns at once when armed != NULL and *armed == 0 (the snapshot
+ * of the parameters in front of Adam on row steps) */
+int dvq_copy_f32_armed(float* dst, const float* src, int64_t n, const int* armed, dvq_stream_t stream);
 /* dst[0..7] <- the eight scalars (passed by value in the launch: no pageable host copy, no host buffer to keep alive) */
 int dvq_set_f32x8(float* dst, float v0, float v1, float v2, float v3, float v4, float v5, float v6, float v7,
                   dvq_stream_t stream);

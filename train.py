@@ -21,6 +21,9 @@ path, without pytorch_lightning / OmegaConf:
 * `-l/--logger none|csv|tensorboard` (or a comma list; default none) with `--log_every_n_steps N` (Lightning's flag, default 50): every
   scalar the model logs as `<key>_step` rows and `<key>_epoch` means in `<logdir>/metrics.csv` and / or a TensorBoard event file
   (docs/design/22-metrics-logging.md).  Stored in the saved config (`lightning.trainer.logger`, `.log_every_n_steps`), so `-r` keeps logging.
+* `--track_grad_norm -1|2|inf` (Lightning's Trainer flag; -1 = off, the default) with `--track_norm_depth N` and `--no_track_updates`:
+  per-parameter gradient, weight and update norms taken on the device, `<logdir>/norms.csv` and totals in the metrics row
+  (docs/design/24-norm-tracking.md).  Stored in the saved config (`lightning.trainer.track_grad_norm`, ...), so `-r` keeps them.
 Unsupported Trainer flags are accepted and ignored with a warning, like unknown Lightning flags would be.
 """
 from __future__ import annotations
@@ -88,6 +91,13 @@ def get_parser():
     p.add_argument("--deterministic", action="store_true",
                    help="bit-reproducible training (Lightning's Trainer flag): ordered sums in every kernel of the step, host-side draws "
                         "seeded by --seed; slower.  One process on one GPU: with several ranks the collective's reduction order also counts")
+    p.add_argument("--track_grad_norm", type=str, default="-1", choices=["-1", "2", "inf"],
+                   help="per-parameter gradient, weight and update norms, taken on the device (Lightning's Trainer flag): -1 off, 2 or inf "
+                        "choose what the total keys report.  <logdir>/norms.csv, rows at --log_every_n_steps")
+    p.add_argument("--track_norm_depth", type=int, default=0,
+                   help="with --track_grad_norm: one line per name prefix of N dotted components instead of one per parameter (0)")
+    p.add_argument("--no_track_updates", action="store_true",
+                   help="with --track_grad_norm: no update norms (saves the snapshot buffer, one copy of the parameters)")
     return p
 
 
@@ -161,6 +171,14 @@ def run(rank, world, opt, unknown):
     saved_trainer = config.get("lightning", {}).get("trainer", {})
     writers, _ = parse_logger_flag(saved_trainer.get("logger", "none"))
     log_every_n_steps = int(saved_trainer.get("log_every_n_steps", opt.log_every_n_steps))
+    # --track_grad_norm, --track_norm_depth, --no_track_updates likewise (docs/design/24-norm-tracking.md)
+    if opt.track_grad_norm != "-1":
+        config = cfg.merge(config, {"lightning": {"trainer": {"track_grad_norm": opt.track_grad_norm, "track_norm_depth": int(opt.track_norm_depth),
+                                                              "track_updates": not opt.no_track_updates, "log_every_n_steps": int(opt.log_every_n_steps)}}})
+        saved_trainer = config.get("lightning", {}).get("trainer", {})
+    track_grad_norm = str(saved_trainer.get("track_grad_norm", "-1"))
+    track_norm_depth = int(saved_trainer.get("track_norm_depth", 0))
+    track_updates = bool(saved_trainer.get("track_updates", True))
     if logdir is None:
         now = datetime.datetime.now().strftime("%Y-%m-%dT%H-%M-%S")
         logdir = os.path.join(opt.logdir, now + ("_" + opt.name if opt.name else "") + opt.postfix)
@@ -247,7 +265,9 @@ def run(rank, world, opt, unknown):
         metrics_logger = MetricsLogger(logdir, writers=writers, log_every_n_steps=log_every_n_steps)
     trainer = Trainer(model, max_steps=total, log_every=10 if rank == 0 else 0, gradient_clip_val=opt.gradient_clip_val,
                       skip_nonfinite=opt.skip_nonfinite_grads, ema_decay=opt.ema_decay, ema_warmup=not opt.ema_no_warmup,
-                      deterministic=deterministic, metrics_logger=metrics_logger)
+                      deterministic=deterministic, metrics_logger=metrics_logger, track_grad_norm=track_grad_norm,
+                      track_updates=track_updates, norm_every=log_every_n_steps, norm_depth=track_norm_depth,
+                      norm_logdir=logdir if rank == 0 else None)
     pool = [torch.from_numpy(synth.half_flat_images(bs, size, seed=opt.seed + 977 * rank + i)).to(dev) for i in range(4)]
 
     image_key = getattr(model, "image_key", None) or getattr(model, "first_stage_key", "image")
