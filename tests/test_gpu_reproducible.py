@@ -185,8 +185,11 @@ def test_embedding_gradient_ordered(dev):
 # ---- cross entropy ----------------------------------------------------------------------------------------------------------------
 @pytest.mark.parametrize("ldl", [1027, 1032], ids=["scalar-rows", "vector-rows"])
 def test_cross_entropy_ordered(dev, ldl):
-    """1000 rows x 1027 classes (250 workgroups), every seventh row ignored.  Bound: the loss bound of test_stackgpt_golden (fp32 2e-4)"""
+    """1000 rows x 1027 classes (250 workgroups), every seventh row ignored.  Bound: the loss bound of test_stackgpt_golden (fp32 2e-4);
+    the returned dlogits per element with the cross-entropy bound of test_gpu_stage2_kernels.py (docs/design/25-stage2-kernel-pins.md),
+    exact zeros in its ignored rows and in the padding columns of the ldl = 1032 case"""
     from dynamicvectorquantization_amd import kernels as K
+    from test_gpu_stage2_kernels import ce_grad_check
     rs = np.random.RandomState(13)
     rows, v = 1000, 1027
     logits = np.zeros((rows, ldl), dtype=np.float32)
@@ -207,6 +210,7 @@ def test_cross_entropy_ordered(dev, ldl):
     def check(out):
         np.testing.assert_allclose(float(out[0]), ref_sum, rtol=2e-4)
         assert float(out[1]) == ref_cnt
+        ce_grad_check(logits, v, target, 1.0, out[2], torch.float32, f"ordered ldl {ldl}", ignore_index=-100)
 
     _family(launch, check)
 
