@@ -1,5 +1,6 @@
-// Fused causal multi-head self-attention of the stage-2 transformer (bf16), forward and backward.  The kernels of this file serve
-// head size 64; causal head size 128 and the DQ-VAE's full attention (one head of 256) run on attention2.hip, entered from here:
+// Fused causal multi-head self-attention of the stage-2 transformer (bf16), forward and backward.  The kernels of this file are causal
+// only and serve head size 64; causal head size 128 and the DQ-VAE's full attention (one head of 256) run on attention2.hip.  The C ABI
+// entry points and the geometry check of both kernel sets are at the end of this file:
 //   CausalSelfAttention.forward   modules/dynamic_modules/stackgpt.py:41-69
 //       att = softmax(mask(q k^T / sqrt(hs)));  att = attn_drop(att);  y = att v
 // The unfused path (per-head GEMMs + softmax + dropout kernels, stackgpt.py of this package) moves the [B, nh, T, T] score
@@ -24,45 +25,9 @@
 // fragments (padded rows: conflict-free ds_read_b128 / ds_read_b64).  Waves beyond their causal range idle for <= 3 tiles.
 #include <type_traits>
 
-#include "attn_v2.h"
-#include "dvq_common.h"
+#include "attn_common.h"
 
 namespace {
-
-constexpr float LOG2E = 1.4426950408889634f;
-
-struct AttnParams {
-    const bf16_t *q, *k, *v, *o, *dout;      // [B*T][C] row-major, C = nh * HS
-    const bf16_t *qt, *kt, *vt, *dot;        // [B][C][T] channel-major copies
-    bf16_t *out, *dq, *dk, *dv;
-    float* lse;                              // [B][nh][T]: log-sum-exp of the scaled, masked scores (natural log)
-    float* dsum;                             // [B][nh][T]: rowsum(dO * O)
-    int T, nh, C;
-    int causal;                              // 1: stage-2 causal attention; 0: full attention (AttnBlock of the DQ-VAE: one head of size
-                                             //    C, every query sees every key; T % 32 == 0: attention2.hip only)
-    float scale;                             // 1 / sqrt(hs)
-    float inv_keep;                          // 1 / (1 - p)
-    unsigned thr, rm, ra;                    // dropout: keep iff dvq_hash32(idx * rm + ra) >= thr (thr == 0: no dropout)
-    unsigned long long* mask;                // optional keep-decision words, [B * nh][nqt][nkt][16] (see drop_tile): written by the
-                                             //    forward, read by the backward kernels instead of hashing every element again
-};
-
-// Dropout decisions of one 32 x 32 score tile as 16 lane masks.  The forward (and dQ) kernels hold the tile as lane = (query l31,
-// half), register r = key (r & 3) + 8 (r >> 2) + 4 half; word r of a tile is the wave-wide ballot of "keep" for register r, i.e.
-// bit (l31 + 32 half) of word r = keep(query l31, key crow(r, half)).  dQ has the same lane / register layout: word r, read with
-// scalar loads, IS its select mask for register r (v_cndmask with an SGPR pair: no VALU work per element besides the select).
-// dK / dV hold the tile transposed (lane = key, registers = queries): lane (key kl, half h') needs keep(query crow(r', h'), kl)
-// = bit crow(r', h') of the 32-bit half-word (kl >> 2 & 1) of word (kl & 3) + 4 (kl >> 3): ONE 4-byte load per lane and tile, then
-// constant bit positions after a shift by 4 h'.  The hash costs 3 quarter-rate integer multiplies + 7 ALU operations per element
-// (~19 issue slots against 4 for the exponential): taken once per element in the forward instead of four times per step, the three
-// backward kernels drop from ~31 to ~13 VALU slots per score element (they were VALU-bound 2.5 : 1 against their MFMAs).
-__device__ __forceinline__ int64_t drop_tile(int bh, int nt, int qt, int kt) { return (((int64_t)bh * nt + qt) * nt + kt) * 16; }
-
-union Frag {
-    uint4 u;
-    bf16x8 v;
-    uint2 h[2];
-};
 
 // LDS tile geometry: row-major tiles [32 rows][HS channels] (K, V, Q, dO) and channel-major tiles [HS channels][32 rows]
 // (V^T, K^T, Q^T, dO^T); row strides padded by 16 bytes
@@ -125,60 +90,18 @@ __device__ __forceinline__ bf16x8 frag_c(const char* tile, int l31, int half, in
     return f.v;
 }
 
-__device__ __forceinline__ bf16x8 ldfrag(const bf16_t* p, bool ok) {
-    Frag f;
-    f.u = ok ? *reinterpret_cast<const uint4*>(p) : make_uint4(0, 0, 0, 0);
-    return f.v;
-}
-
-__device__ __forceinline__ bf16x8 pack8(const f32x16& a, int s) {
-    Frag f;
-    f.u.x = pack_bf16x2(a[8 * s + 0], a[8 * s + 1]);
-    f.u.y = pack_bf16x2(a[8 * s + 2], a[8 * s + 3]);
-    f.u.z = pack_bf16x2(a[8 * s + 4], a[8 * s + 5]);
-    f.u.w = pack_bf16x2(a[8 * s + 6], a[8 * s + 7]);
-    return f.v;
-}
-
-__device__ __forceinline__ f32x16 zero16() {
-    f32x16 z;
-#pragma unroll
-    for (int r = 0; r < 16; ++r) z[r] = 0.f;
-    return z;
-}
-
-#define MFMA(a, b, c) __builtin_amdgcn_mfma_f32_32x32x16_bf16((a), (b), (c), 0, 0, 0)
-
-// accumulator register r of half `half` -> row offset inside the 32-row tile
-__device__ __forceinline__ int crow(int r, int half) { return (r & 3) + 8 * (r >> 2) + 4 * half; }
-
-// [ch][row] accumulators (NM 32-channel tiles) -> row-major [row][HS channels] bf16: lane = row, 4 consecutive channels
-// per register quad (8-byte stores)
-template <int NM>
-__device__ __forceinline__ void store_ct(bf16_t* dst /* row base + head offset */, const f32x16 (&acc)[NM], int half, float mul) {
-#pragma unroll
-    for (int mt = 0; mt < NM; ++mt)
-#pragma unroll
-        for (int g = 0; g < 4; ++g) {
-            uint2 w;
-            w.x = pack_bf16x2(acc[mt][4 * g + 0] * mul, acc[mt][4 * g + 1] * mul);
-            w.y = pack_bf16x2(acc[mt][4 * g + 2] * mul, acc[mt][4 * g + 3] * mul);
-            *reinterpret_cast<uint2*>(dst + 32 * mt + 8 * g + 4 * half) = w;
-        }
-}
-
 // ------------------------------------------------------------------------------------------------------------------
 // forward: one wave per 32 queries; the workgroup walks the key tiles 0 .. (its last query tile)
 // ------------------------------------------------------------------------------------------------------------------
 // (two workgroups per CU: without the explicit bound the compiler spreads into AGPRs and settles for one wave per SIMD)
 template <int HS>
-__global__ __launch_bounds__(256, 2) void attn_fwd_kernel(AttnParams p) {
+__global__ __launch_bounds__(256, 2) void attn_fwd_kernel(AttnArgsCm p) {
     using G = Geo<HS>;
     constexpr int NS = HS / 16, NM = HS / 32, STAGE = G::RTILE + G::CTILE;
     extern __shared__ __attribute__((aligned(16))) char smem[];
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     const int l31 = lane & 31, half = lane >> 5;
-    const int T = p.T, C = p.C;
+    const int T = p.T, C = p.nh * HS;
     const int bh = blockIdx.y, b = bh / p.nh, h = bh - b * p.nh;
     const int nqt = (T + 31) / 32;
     const int qt_max = nqt - 1 - blockIdx.x * 4;                 // late (long) query tiles first; wave 0 owns the last one
@@ -207,22 +130,21 @@ __global__ __launch_bounds__(256, 2) void attn_fwd_kernel(AttnParams p) {
     swrite_rows<HS>(smem, tid, rk);
     swrite_cols<HS>(smem + G::RTILE, tid, rv);
     __syncthreads();
-    const int kt_last = p.causal ? qt_max : nqt - 1;            // full attention: every query tile walks all key tiles
-    for (int kt = 0; kt <= kt_last; ++kt) {
+    for (int kt = 0; kt <= qt_max; ++kt) {
         const char* kl = smem + (kt & 1) * STAGE;
         const char* vl = kl + G::RTILE;
-        const bool more = kt < kt_last;
+        const bool more = kt < qt_max;
         if (more) {
             gload_rows<HS>(kbase, rowbase, 32 * (kt + 1), T, C, tid, rk);
             gload_cols<HS>(vtbase, 32 * (kt + 1), T, tid, rv);
         }
-        if (active && (!p.causal || kt <= qt)) {
+        if (active && kt <= qt) {
             const int k0 = kt * 32;
             f32x16 s = zero16();
 #pragma unroll
             for (int st = 0; st < NS; ++st) s = MFMA(frag_r<HS>(kl, l31, half, st), qf[st], s);
             float mx = m_run;
-            if (p.causal && kt == qt) {                          // diagonal tile: causal mask (also hides keys >= T)
+            if (kt == qt) {                                       // diagonal tile: causal mask (also hides keys >= T)
 #pragma unroll
                 for (int r = 0; r < 16; ++r) {
                     const int key = k0 + crow(r, half);
@@ -292,13 +214,13 @@ __global__ __launch_bounds__(256, 2) void attn_fwd_kernel(AttnParams p) {
 // backward, dQ: one wave per 32 queries (same walk as the forward); LDS stage = K, V (row-major) and K^T tiles
 // ------------------------------------------------------------------------------------------------------------------
 template <int HS, bool MASKED = false>
-__global__ __launch_bounds__(256, 2) void attn_bwd_dq_kernel(AttnParams p) {
+__global__ __launch_bounds__(256, 2) void attn_bwd_dq_kernel(AttnArgsCm p) {
     using G = Geo<HS>;
     constexpr int NS = HS / 16, NM = HS / 32, STAGE = 2 * G::RTILE + G::CTILE;
     extern __shared__ __attribute__((aligned(16))) char smem[];
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     const int l31 = lane & 31, half = lane >> 5;
-    const int T = p.T, C = p.C;
+    const int T = p.T, C = p.nh * HS;
     const int bh = blockIdx.y, b = bh / p.nh, h = bh - b * p.nh;
     const int nqt = (T + 31) / 32;
     const int qt_max = nqt - 1 - blockIdx.x * 4;
@@ -355,18 +277,17 @@ __global__ __launch_bounds__(256, 2) void attn_bwd_dq_kernel(AttnParams p) {
     swrite_rows<HS>(smem + G::RTILE, tid, rv);
     swrite_cols<HS>(smem + 2 * G::RTILE, tid, rt);
     __syncthreads();
-    const int kt_last = p.causal ? qt_max : nqt - 1;
-    for (int kt = 0; kt <= kt_last; ++kt) {
+    for (int kt = 0; kt <= qt_max; ++kt) {
         const char* kl = smem + (kt & 1) * STAGE;
         const char* vl = kl + G::RTILE;
         const char* tl = kl + 2 * G::RTILE;
-        const bool more = kt < kt_last;
+        const bool more = kt < qt_max;
         if (more) {
             gload_rows<HS>(kbase, rowbase, 32 * (kt + 1), T, C, tid, rk);
             gload_rows<HS>(vbase, rowbase, 32 * (kt + 1), T, C, tid, rv);
             gload_cols<HS>(ktbase, 32 * (kt + 1), T, tid, rt);
         }
-        if (active && (!p.causal || kt <= qt)) {
+        if (active && kt <= qt) {
             const int k0 = kt * 32;
             unsigned long long mk[16];                           // the tile's 16 select masks: scalar loads, issued ahead of the first GEMMs
             if constexpr (MASKED) {
@@ -380,7 +301,6 @@ __global__ __launch_bounds__(256, 2) void attn_bwd_dq_kernel(AttnParams p) {
                 s = MFMA(frag_r<HS>(kl, l31, half, st), qf[st], s);
                 dp = MFMA(frag_r<HS>(vl, l31, half, st), dof[st], dp);
             }
-            const bool diag = p.causal && kt == qt;
             auto elementwise = [&](auto diag_c) {
                 constexpr bool DIAG = decltype(diag_c)::value, MASK = MASKED;
 #pragma unroll
@@ -397,7 +317,7 @@ __global__ __launch_bounds__(256, 2) void attn_bwd_dq_kernel(AttnParams p) {
                     s[r] = pr * (g - dq_);                        // d loss / d (scaled score)
                 }
             };
-            if (diag) elementwise(std::true_type{});
+            if (kt == qt) elementwise(std::true_type{});
             else elementwise(std::false_type{});
 #pragma unroll
             for (int s2 = 0; s2 < 2; ++s2) {
@@ -423,14 +343,14 @@ __global__ __launch_bounds__(256, 2) void attn_bwd_dq_kernel(AttnParams p) {
 // ------------------------------------------------------------------------------------------------------------------
 // MODE 0: dK and dV together (the one launch head size 64 makes); 1: dV only; 2: dK only.
 template <int HS, int MODE = 0, bool MASKED = false>
-__global__ __launch_bounds__(256, 2) void attn_bwd_dkv_kernel(AttnParams p) {
+__global__ __launch_bounds__(256, 2) void attn_bwd_dkv_kernel(AttnArgsCm p) {
     constexpr bool DO_DV = MODE != 2, DO_DK = MODE != 1;
     using G = Geo<HS>;
     constexpr int NS = HS / 16, NM = HS / 32, STAGE = 2 * G::RTILE + 2 * G::CTILE;
     extern __shared__ __attribute__((aligned(16))) char smem[];
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     const int l31 = lane & 31, half = lane >> 5;
-    const int T = p.T, C = p.C;
+    const int T = p.T, C = p.nh * HS;
     const int bh = blockIdx.y, b = bh / p.nh, h = bh - b * p.nh;
     const int nt = (T + 31) / 32;
     const int kt_min = blockIdx.x * 4;                            // early (long) key tiles first
@@ -460,11 +380,10 @@ __global__ __launch_bounds__(256, 2) void attn_bwd_dkv_kernel(AttnParams p) {
     const float* lsep = p.lse + (int64_t)bh * T;
     const float* dsp = p.dsum + (int64_t)bh * T;
     uint4 rq[G::NCH], rd[G::NCH], rqt[G::NCH], rdt[G::NCH];
-    const int qt_first = p.causal ? kt_min : 0;                   // full attention: every key tile walks all query tiles
-    gload_rows<HS>(qbase, rowbase, 32 * qt_first, T, C, tid, rq);
-    if constexpr (DO_DK) gload_rows<HS>(dobase, rowbase, 32 * qt_first, T, C, tid, rd);
-    if constexpr (DO_DK) gload_cols<HS>(qtbase, 32 * qt_first, T, tid, rqt);
-    if constexpr (DO_DV) gload_cols<HS>(dotbase, 32 * qt_first, T, tid, rdt);
+    gload_rows<HS>(qbase, rowbase, 32 * kt_min, T, C, tid, rq);
+    if constexpr (DO_DK) gload_rows<HS>(dobase, rowbase, 32 * kt_min, T, C, tid, rd);
+    if constexpr (DO_DK) gload_cols<HS>(qtbase, 32 * kt_min, T, tid, rqt);
+    if constexpr (DO_DV) gload_cols<HS>(dotbase, 32 * kt_min, T, tid, rdt);
     swrite_rows<HS>(smem, tid, rq);
     if constexpr (DO_DK) swrite_rows<HS>(smem + G::RTILE, tid, rd);
     if constexpr (DO_DK) swrite_cols<HS>(smem + 2 * G::RTILE, tid, rqt);
@@ -473,12 +392,12 @@ __global__ __launch_bounds__(256, 2) void attn_bwd_dkv_kernel(AttnParams p) {
     constexpr bool masked = MASKED;
     // keep bits of this lane's key over a tile's 32 queries (see drop_tile): one 4-byte load per tile, fetched one tile ahead
     const unsigned* mlane = reinterpret_cast<const unsigned*>(p.mask) + 2 * ((l31 & 3) + 4 * (l31 >> 3)) + ((l31 >> 2) & 1);
-    auto mask_word = [&](int qt_) { return masked && active && (!p.causal || qt_ >= kt) ? mlane[2 * drop_tile(bh, nt, qt_, kt)] : 0u; };
-    unsigned mnext = mask_word(qt_first);
-    for (int qt = qt_first; qt < nt; ++qt) {
+    auto mask_word = [&](int qt_) { return masked && active && qt_ >= kt ? mlane[2 * drop_tile(bh, nt, qt_, kt)] : 0u; };
+    unsigned mnext = mask_word(kt_min);
+    for (int qt = kt_min; qt < nt; ++qt) {
         const unsigned mword = mnext >> (4 * half);              // query 8 g + 4 half + i of the tile is bit 8 g + i
         if (qt + 1 < nt) mnext = mask_word(qt + 1);
-        const char* ql = smem + ((qt - qt_first) & 1) * STAGE;
+        const char* ql = smem + ((qt - kt_min) & 1) * STAGE;
         const char* dl = ql + G::RTILE;
         const char* qtl = ql + 2 * G::RTILE;
         const char* dtl = qtl + G::CTILE;
@@ -489,7 +408,7 @@ __global__ __launch_bounds__(256, 2) void attn_bwd_dkv_kernel(AttnParams p) {
             if constexpr (DO_DK) gload_cols<HS>(qtbase, 32 * (qt + 1), T, tid, rqt);
             if constexpr (DO_DV) gload_cols<HS>(dotbase, 32 * (qt + 1), T, tid, rdt);
         }
-        if (active && (!p.causal || qt >= kt)) {
+        if (active && qt >= kt) {
             const int q0 = qt * 32;
             f32x16 s = zero16(), dp = zero16();
 #pragma unroll
@@ -499,7 +418,7 @@ __global__ __launch_bounds__(256, 2) void attn_bwd_dkv_kernel(AttnParams p) {
             }
             // element-wise pass and second GEMMs in two halves (registers 8 s2 .. 8 s2 + 7 = two groups of 4 consecutive
             // queries each): only 8 probabilities / 8 score gradients and 8 per-query statistics are live at a time
-            const bool diag = p.causal && qt == kt;
+            const bool diag = qt == kt;
             const bool edge = diag || q0 + 32 > T;               // tiles that need per-element validity tests
             auto second = [&](auto edge_c) {
                 constexpr bool EDGE = decltype(edge_c)::value, MASK = MASKED;
@@ -556,7 +475,7 @@ __global__ __launch_bounds__(256, 2) void attn_bwd_dkv_kernel(AttnParams p) {
             else second(std::false_type{});
         }
         if (more) {
-            char* nl = smem + ((qt + 1 - qt_first) & 1) * STAGE;
+            char* nl = smem + ((qt + 1 - kt_min) & 1) * STAGE;
             swrite_rows<HS>(nl, tid, rq);
             if constexpr (DO_DK) swrite_rows<HS>(nl + G::RTILE, tid, rd);
             if constexpr (DO_DK) swrite_cols<HS>(nl + 2 * G::RTILE, tid, rqt);
@@ -571,7 +490,7 @@ __global__ __launch_bounds__(256, 2) void attn_bwd_dkv_kernel(AttnParams p) {
 }
 
 template <int HS>
-int launch_fwd(const AttnParams& p, dim3 grid, hipStream_t stream) {
+int launch_fwd(const AttnArgsCm& p, dim3 grid, hipStream_t stream) {
     using G = Geo<HS>;
     const int lds = 2 * (G::RTILE + G::CTILE);
     dvq_ensure_dynamic_lds((const void*)attn_fwd_kernel<HS>, lds);
@@ -580,7 +499,7 @@ int launch_fwd(const AttnParams& p, dim3 grid, hipStream_t stream) {
 }
 
 template <int HS, bool MASKED>
-int launch_bwd_m(const AttnParams& p, dim3 grid, hipStream_t stream) {
+int launch_bwd_m(const AttnArgsCm& p, dim3 grid, hipStream_t stream) {
     using G = Geo<HS>;
     const int lds_kv = 2 * (2 * G::RTILE + 2 * G::CTILE), lds_q = 2 * (2 * G::RTILE + G::CTILE);
     dvq_ensure_dynamic_lds((const void*)attn_bwd_dq_kernel<HS, MASKED>, lds_q);
@@ -590,15 +509,15 @@ int launch_bwd_m(const AttnParams& p, dim3 grid, hipStream_t stream) {
     return 0;
 }
 template <int HS>
-int launch_bwd(const AttnParams& p, dim3 grid, hipStream_t stream) {
+int launch_bwd(const AttnArgsCm& p, dim3 grid, hipStream_t stream) {
     if (p.thr != 0 && p.mask != nullptr) return launch_bwd_m<HS, true>(p, grid, stream);
     return launch_bwd_m<HS, false>(p, grid, stream);
 }
 
 // geometry the fused kernels take, stated once: fill_params (every entry point) and the exported predicates dvq_attn_causal_ok /
-// dvq_attn_full_ok ask it.  nullptr = accepted, else the refusal's format (one %s: the entry point).  Full attention (!causal) has no
-// dropout path: attention2.hip launches nothing for it.
-const char* attn_refusal(int dtype, int64_t B, int64_t T, int n_head, int head_dim, float p_drop, int causal) {
+// dvq_attn_full_ok ask it.  nullptr = accepted, else the refusal's format (one %s: the entry point).  ld: row pitch of q, k, v and
+// their gradients.  Full attention (!causal) has no dropout path: attention2.hip launches nothing for it.
+const char* attn_refusal(int dtype, int64_t B, int64_t T, int n_head, int head_dim, int64_t ld, float p_drop, int causal) {
     if (!(dtype == DVQ_BF16 && (causal ? head_dim == 64 || head_dim == 128 : head_dim == 256)))
         return "%s: bf16 with head size 64 or 128 (causal) / 256 (full attention) only (use the GEMM path otherwise)";
     if (!(causal || T % 32 == 0)) return "%s: full attention needs T %% 32 == 0";
@@ -606,17 +525,21 @@ const char* attn_refusal(int dtype, int64_t B, int64_t T, int n_head, int head_d
         return "%s: bad geometry (T %% 8 == 0, B * n_head <= 65535)";
     if (!((double)B * n_head * (double)T * (double)T < 4294967296.0))
         return "%s: B * n_head * T * T must stay below 2^32 (dropout element index)";
+    if (ld != (int64_t)n_head * head_dim && head_dim != 128)
+        return "%s: a row pitch other than n_head * head_dim needs head size 128 (the kernels of attention2.hip)";
+    if (!(ld >= (int64_t)n_head * head_dim && ld % 8 == 0 && (double)T * (double)ld * 2.0 < 4294967296.0))
+        return "%s: bad pitch (at least n_head * head_dim, a multiple of 8, T * pitch * 2 below 2^32)";
     return nullptr;
 }
 
-int fill_params(AttnParams& p, const char* who, int dtype, int64_t B, int64_t T, int n_head, int head_dim, float scale, float p_drop,
+int fill_params(AttnArgs& p, const char* who, int dtype, int64_t B, int64_t T, int n_head, int head_dim, int64_t ld, float scale, float p_drop,
                 uint64_t seed, int causal = 1) {
-    if (const char* why = attn_refusal(dtype, B, T, n_head, head_dim, p_drop, causal)) {
+    if (const char* why = attn_refusal(dtype, B, T, n_head, head_dim, ld, p_drop, causal)) {
         dvq_set_error(why, who);
         return DVQ_ESHAPE;
     }
     p.causal = causal;
-    p.T = (int)T; p.nh = n_head; p.C = n_head * head_dim;
+    p.B = (int)B; p.T = (int)T; p.nh = n_head; p.ldq = (int)ld;
     p.scale = scale;
     p.inv_keep = 1.f / (1.f - p_drop);
     p.thr = (unsigned)((double)p_drop * 4294967296.0);
@@ -624,33 +547,22 @@ int fill_params(AttnParams& p, const char* who, int dtype, int64_t B, int64_t T,
     return DVQ_OK;
 }
 
-// head sizes 128 and 256 run on the round-6 kernels (attention2.hip: LDS-DMA ring, transpose reads instead of channel-major copies)
-Attn2Args v2_args(const AttnParams& p, int64_t B) {
-    Attn2Args a{};
-    a.q = p.q; a.k = p.k; a.v = p.v; a.o = p.o; a.dout = p.dout;
-    a.out = p.out; a.dq = p.dq; a.dk = p.dk; a.dv = p.dv;
-    a.lse = p.lse; a.dsum = p.dsum;
-    a.B = (int)B; a.T = p.T; a.nh = p.nh;
-    a.scale = p.scale; a.inv_keep = p.inv_keep; a.thr = p.thr; a.rm = p.rm; a.ra = p.ra;
-    a.mask = p.mask;
-    a.causal = p.causal;
-    a.ldq = p.C;
-    return a;
-}
+int64_t dsum_bytes(int64_t B, int64_t T, int n_head) { return ((B * n_head * T * 4 + 255) / 256) * 256; }
 
 }  // namespace
 
 extern "C" {
 
 int dvq_attn_causal_ok(int dtype, int64_t B, int64_t T, int n_head, int head_dim) {
-    return attn_refusal(dtype, B, T, n_head, head_dim, 0.f, 1) == nullptr;
+    return attn_refusal(dtype, B, T, n_head, head_dim, (int64_t)n_head * head_dim, 0.f, 1) == nullptr;
 }
-int dvq_attn_full_ok(int dtype, int64_t B, int64_t T, int C) { return attn_refusal(dtype, B, T, 1, C, 0.f, 0) == nullptr; }
+int dvq_attn_full_ok(int dtype, int64_t B, int64_t T, int C) { return attn_refusal(dtype, B, T, 1, C, C, 0.f, 0) == nullptr; }
 
+// head size 64: the channel-major copies (v^T forward; q^T, k^T, dO^T backward) and, behind them, dsum.  Head sizes 128 and 256
+// (attention2.hip) read their operands in place: nothing forward, dsum alone backward.
 int64_t dvq_attn_causal_scratch_bytes(int64_t B, int64_t T, int n_head, int head_dim, int backward) {
-    const int64_t elems = B * T * n_head * head_dim;
-    if (!backward) return elems * 2;
-    return 3 * elems * 2 + ((B * n_head * T * 4 + 255) / 256) * 256;
+    const int64_t copy = head_dim == 64 ? B * T * n_head * head_dim * 2 : 0;
+    return backward ? 3 * copy + dsum_bytes(B, T, n_head) : copy;
 }
 
 int64_t dvq_attn_causal_mask_bytes(int64_t B, int64_t T, int n_head) {
@@ -658,44 +570,24 @@ int64_t dvq_attn_causal_mask_bytes(int64_t B, int64_t T, int n_head) {
     return B * n_head * nt * nt * 16 * 8;
 }
 
-static int attn_causal_fwd_impl(const void* q, const void* k, const void* v, int64_t ldqkv, int dtype, int64_t B, int64_t T, int n_head,
-                                int head_dim, float scale, float p_drop, uint64_t seed, void* out, float* lse, void* scratch,
-                                void* drop_mask, dvq_stream_t stream);
-
-int dvq_attn_causal_fwd(const void* q, const void* k, const void* v, int dtype, int64_t B, int64_t T, int n_head, int head_dim,
-                        float scale, float p_drop, uint64_t seed, void* out, float* lse, void* scratch, void* drop_mask,
+int dvq_attn_causal_fwd(const void* q, const void* k, const void* v, int64_t ldqkv, int dtype, int64_t B, int64_t T, int n_head,
+                        int head_dim, float scale, float p_drop, uint64_t seed, void* out, float* lse, void* scratch, void* drop_mask,
                         dvq_stream_t stream) {
-    return attn_causal_fwd_impl(q, k, v, (int64_t)n_head * head_dim, dtype, B, T, n_head, head_dim, scale, p_drop, seed, out, lse, scratch,
-                                drop_mask, stream);
-}
-
-int dvq_attn_causal_fwd_ld(const void* q, const void* k, const void* v, int64_t ldqkv, int dtype, int64_t B, int64_t T, int n_head,
-                           int head_dim, float scale, float p_drop, uint64_t seed, void* out, float* lse, void* drop_mask,
-                           dvq_stream_t stream) {
-    DVQ_REQUIRE(head_dim == 128, DVQ_ESHAPE, "dvq_attn_causal_fwd_ld: a row pitch needs the head-size-128 kernels of attention2.hip");
-    DVQ_REQUIRE(ldqkv >= (int64_t)n_head * head_dim && ldqkv % 8 == 0 && (double)T * (double)ldqkv * 2.0 < 4294967296.0, DVQ_ESHAPE,
-                "dvq_attn_causal_fwd_ld: bad pitch");
-    return attn_causal_fwd_impl(q, k, v, ldqkv, dtype, B, T, n_head, head_dim, scale, p_drop, seed, out, lse, out /* unused */, drop_mask, stream);
-}
-
-static int attn_causal_fwd_impl(const void* q, const void* k, const void* v, int64_t ldqkv, int dtype, int64_t B, int64_t T, int n_head,
-                                int head_dim, float scale, float p_drop, uint64_t seed, void* out, float* lse, void* scratch,
-                                void* drop_mask, dvq_stream_t stream) {
-    DVQ_REQUIRE(q && k && v && out && lse && scratch, DVQ_EINVAL, "dvq_attn_causal_fwd: null pointer");
-    AttnParams p{};
-    int rc = fill_params(p, "dvq_attn_causal_fwd", dtype, B, T, n_head, head_dim, scale, p_drop, seed);
+    DVQ_REQUIRE(q && k && v && out && lse, DVQ_EINVAL, "dvq_attn_causal_fwd: null pointer");
+    AttnArgsCm p{};
+    int rc = fill_params(p, "dvq_attn_causal_fwd", dtype, B, T, n_head, head_dim, ldqkv, scale, p_drop, seed);
     if (rc != DVQ_OK) return rc;
-    p.q = (const bf16_t*)q; p.k = (const bf16_t*)k; p.v = (const bf16_t*)v; p.vt = (const bf16_t*)scratch;
+    DVQ_REQUIRE(scratch || dvq_attn_causal_scratch_bytes(B, T, n_head, head_dim, 0) == 0, DVQ_EINVAL, "dvq_attn_causal_fwd: null scratch");
+    p.q = (const bf16_t*)q; p.k = (const bf16_t*)k; p.v = (const bf16_t*)v;
     p.out = (bf16_t*)out; p.lse = lse;
     p.mask = (unsigned long long*)drop_mask;
     if (head_dim == 128) {
-        Attn2Args a = v2_args(p, B);
-        a.ldq = (int)ldqkv;
-        dvq_attn2_fwd(a, (hipStream_t)stream);
+        dvq_attn2_fwd(p, (hipStream_t)stream);
         DVQ_CHECK_LAUNCH("attn_causal_fwd");
         return DVQ_OK;
     }
-    rc = dvq_transpose(v, dtype, B, T, p.C, scratch, stream);                        // head size 64: v^T [B][C][T]
+    p.vt = (const bf16_t*)scratch;
+    rc = dvq_transpose(v, dtype, B, T, n_head * head_dim, scratch, stream);          // head size 64: v^T [B][C][T]
     if (rc != DVQ_OK) return rc;
     const int nqt = (int)((T + 31) / 32);
     launch_fwd<64>(p, dim3((unsigned)((nqt + 3) / 4), (unsigned)(B * n_head)), (hipStream_t)stream);
@@ -703,54 +595,32 @@ static int attn_causal_fwd_impl(const void* q, const void* k, const void* v, int
     return DVQ_OK;
 }
 
-static int attn_causal_bwd_impl(const void* q, const void* k, const void* v, int64_t ldqkv, const void* out, const void* dout, const float* lse,
-                                int dtype, int64_t B, int64_t T, int n_head, int head_dim, float scale, float p_drop, uint64_t seed, void* dq,
-                                void* dk, void* dv, void* scratch, const void* drop_mask, dvq_stream_t stream);
-
-int dvq_attn_causal_bwd(const void* q, const void* k, const void* v, const void* out, const void* dout, const float* lse, int dtype,
-                        int64_t B, int64_t T, int n_head, int head_dim, float scale, float p_drop, uint64_t seed, void* dq, void* dk,
-                        void* dv, void* scratch, const void* drop_mask, dvq_stream_t stream) {
-    return attn_causal_bwd_impl(q, k, v, (int64_t)n_head * head_dim, out, dout, lse, dtype, B, T, n_head, head_dim, scale, p_drop, seed, dq, dk,
-                                dv, scratch, drop_mask, stream);
-}
-
-int dvq_attn_causal_bwd_ld(const void* q, const void* k, const void* v, int64_t ldqkv, const void* out, const void* dout, const float* lse,
-                           int dtype, int64_t B, int64_t T, int n_head, int head_dim, float scale, float p_drop, uint64_t seed, void* dq,
-                           void* dk, void* dv, void* scratch, const void* drop_mask, dvq_stream_t stream) {
-    DVQ_REQUIRE(head_dim == 128, DVQ_ESHAPE, "dvq_attn_causal_bwd_ld: a row pitch needs the head-size-128 kernels of attention2.hip");
-    DVQ_REQUIRE(ldqkv >= (int64_t)n_head * head_dim && ldqkv % 8 == 0 && (double)T * (double)ldqkv * 2.0 < 4294967296.0, DVQ_ESHAPE,
-                "dvq_attn_causal_bwd_ld: bad pitch");
-    return attn_causal_bwd_impl(q, k, v, ldqkv, out, dout, lse, dtype, B, T, n_head, head_dim, scale, p_drop, seed, dq, dk, dv, scratch, drop_mask,
-                                stream);
-}
-
-static int attn_causal_bwd_impl(const void* q, const void* k, const void* v, int64_t ldqkv, const void* out, const void* dout, const float* lse,
-                                int dtype, int64_t B, int64_t T, int n_head, int head_dim, float scale, float p_drop, uint64_t seed, void* dq,
-                                void* dk, void* dv, void* scratch, const void* drop_mask, dvq_stream_t stream) {
+int dvq_attn_causal_bwd(const void* q, const void* k, const void* v, int64_t ldqkv, const void* out, const void* dout, const float* lse,
+                        int dtype, int64_t B, int64_t T, int n_head, int head_dim, float scale, float p_drop, uint64_t seed, void* dq,
+                        void* dk, void* dv, void* scratch, const void* drop_mask, dvq_stream_t stream) {
     DVQ_REQUIRE(q && k && v && out && dout && lse && dq && dk && dv && scratch, DVQ_EINVAL, "dvq_attn_causal_bwd: null pointer");
-    AttnParams p{};
-    int rc = fill_params(p, "dvq_attn_causal_bwd", dtype, B, T, n_head, head_dim, scale, p_drop, seed);
+    AttnArgsCm p{};
+    int rc = fill_params(p, "dvq_attn_causal_bwd", dtype, B, T, n_head, head_dim, ldqkv, scale, p_drop, seed);
     if (rc != DVQ_OK) return rc;
-    const int64_t elems = B * T * p.C;
-    bf16_t* qt = (bf16_t*)scratch;
-    bf16_t* kt = qt + elems;
-    bf16_t* dot = kt + elems;
-    float* dsum = reinterpret_cast<float*>(dot + elems);
     p.q = (const bf16_t*)q; p.k = (const bf16_t*)k; p.v = (const bf16_t*)v; p.o = (const bf16_t*)out; p.dout = (const bf16_t*)dout;
-    p.qt = qt; p.kt = kt; p.dot = dot;
     p.dq = (bf16_t*)dq; p.dk = (bf16_t*)dk; p.dv = (bf16_t*)dv;
-    p.lse = const_cast<float*>(lse); p.dsum = dsum;
+    p.lse = const_cast<float*>(lse);
     p.mask = (unsigned long long*)const_cast<void*>(drop_mask);
     if (head_dim == 128) {
-        Attn2Args a = v2_args(p, B);
-        a.ldq = (int)ldqkv;
-        dvq_attn2_bwd(a, (hipStream_t)stream);
+        p.dsum = (float*)scratch;
+        dvq_attn2_bwd(p, (hipStream_t)stream);
         DVQ_CHECK_LAUNCH("attn_causal_bwd");
         return DVQ_OK;
     }
-    if ((rc = dvq_transpose(q, dtype, B, T, p.C, qt, stream)) != DVQ_OK) return rc;
-    if ((rc = dvq_transpose(k, dtype, B, T, p.C, kt, stream)) != DVQ_OK) return rc;
-    if ((rc = dvq_transpose(dout, dtype, B, T, p.C, dot, stream)) != DVQ_OK) return rc;
+    const int64_t C = n_head * head_dim, elems = B * T * C;                          // head size 64: q^T, k^T, dO^T [B][C][T], then dsum
+    bf16_t* qt = (bf16_t*)scratch;
+    bf16_t* kt = qt + elems;
+    bf16_t* dot = kt + elems;
+    p.qt = qt; p.kt = kt; p.dot = dot;
+    p.dsum = reinterpret_cast<float*>(dot + elems);
+    if ((rc = dvq_transpose(q, dtype, B, T, C, qt, stream)) != DVQ_OK) return rc;
+    if ((rc = dvq_transpose(k, dtype, B, T, C, kt, stream)) != DVQ_OK) return rc;
+    if ((rc = dvq_transpose(dout, dtype, B, T, C, dot, stream)) != DVQ_OK) return rc;
     const int nt = (int)((T + 31) / 32);
     launch_bwd<64>(p, dim3((unsigned)((nt + 3) / 4), (unsigned)(B * n_head)), (hipStream_t)stream);
     DVQ_CHECK_LAUNCH("attn_causal_bwd");
@@ -758,21 +628,17 @@ static int attn_causal_bwd_impl(const void* q, const void* k, const void* v, int
 }
 
 /* ---- single-head FULL (non-causal) attention of the DQ-VAE's AttnBlock (modules/diffusionmodules/model.py:168-192): one head of
- * size C = 256 (fill_params refuses any other), every query sees every key, no dropout; scores never reach HBM.  The scratch sizes
- * are those of the causal entry points: callers size their buffers by them. ---- */
-int64_t dvq_attn_full_scratch_bytes(int64_t B, int64_t T, int C, int backward) {
-    return dvq_attn_causal_scratch_bytes(B, T, 1, C, backward);
-}
-
+ * size C = 256 (attn_refusal takes no other), every query sees every key, no dropout; scores never reach HBM.  Scratch:
+ * dvq_attn_causal_scratch_bytes with n_head = 1 (nothing forward, dsum backward). ---- */
 int dvq_attn_full_fwd(const void* q, const void* k, const void* v, int dtype, int64_t B, int64_t T, int C, float scale, void* out,
-                      float* lse, void* scratch, dvq_stream_t stream) {
-    DVQ_REQUIRE(q && k && v && out && lse && scratch, DVQ_EINVAL, "dvq_attn_full_fwd: null pointer");
-    AttnParams p{};
-    int rc = fill_params(p, "dvq_attn_full_fwd", dtype, B, T, 1, C, scale, 0.f, 0, 0);
+                      float* lse, void* /* scratch: none at this head size */, dvq_stream_t stream) {
+    DVQ_REQUIRE(q && k && v && out && lse, DVQ_EINVAL, "dvq_attn_full_fwd: null pointer");
+    AttnArgs p{};
+    int rc = fill_params(p, "dvq_attn_full_fwd", dtype, B, T, 1, C, C, scale, 0.f, 0, 0);
     if (rc != DVQ_OK) return rc;
     p.q = (const bf16_t*)q; p.k = (const bf16_t*)k; p.v = (const bf16_t*)v;
     p.out = (bf16_t*)out; p.lse = lse;
-    dvq_attn2_fwd(v2_args(p, B), (hipStream_t)stream);
+    dvq_attn2_fwd(p, (hipStream_t)stream);
     DVQ_CHECK_LAUNCH("attn_full_fwd");
     return DVQ_OK;
 }
@@ -780,14 +646,14 @@ int dvq_attn_full_fwd(const void* q, const void* k, const void* v, int dtype, in
 int dvq_attn_full_bwd(const void* q, const void* k, const void* v, const void* out, const void* dout, const float* lse, int dtype,
                       int64_t B, int64_t T, int C, float scale, void* dq, void* dk, void* dv, void* scratch, dvq_stream_t stream) {
     DVQ_REQUIRE(q && k && v && out && dout && lse && dq && dk && dv && scratch, DVQ_EINVAL, "dvq_attn_full_bwd: null pointer");
-    AttnParams p{};
-    int rc = fill_params(p, "dvq_attn_full_bwd", dtype, B, T, 1, C, scale, 0.f, 0, 0);
+    AttnArgs p{};
+    int rc = fill_params(p, "dvq_attn_full_bwd", dtype, B, T, 1, C, C, scale, 0.f, 0, 0);
     if (rc != DVQ_OK) return rc;
     p.q = (const bf16_t*)q; p.k = (const bf16_t*)k; p.v = (const bf16_t*)v; p.o = (const bf16_t*)out; p.dout = (const bf16_t*)dout;
     p.dq = (bf16_t*)dq; p.dk = (bf16_t*)dk; p.dv = (bf16_t*)dv;
     p.lse = const_cast<float*>(lse);
-    p.dsum = reinterpret_cast<float*>((bf16_t*)scratch + 3 * B * T * p.C);           // where the causal layout keeps it
-    dvq_attn2_bwd(v2_args(p, B), (hipStream_t)stream);
+    p.dsum = (float*)scratch;
+    dvq_attn2_bwd(p, (hipStream_t)stream);
     DVQ_CHECK_LAUNCH("attn_full_bwd");
     return DVQ_OK;
 }

@@ -26,21 +26,12 @@
 // dK, dV:       S[query][key] = Q K^T    (lane = key; registers = queries = contraction index of dV^T += dO^T P, dK^T += Q^T dS)
 #include <type_traits>
 
-#include "attn_v2.h"
+#include "attn_common.h"
 
 namespace {
 
-constexpr float LOG2E = 1.4426950408889634f;
 typedef int i32x4 __attribute__((ext_vector_type(4)));
 typedef __attribute__((address_space(3))) bf16x4 lds_bf16x4;
-
-#define MFMA(a, b, c) __builtin_amdgcn_mfma_f32_32x32x16_bf16((a), (b), (c), 0, 0, 0)
-
-union Frag {
-    uint4 u;
-    bf16x8 v;
-    uint2 h[2];
-};
 
 // head-size dependent geometry: LDS rows of HS bf16 channels, 64-row operand tiles, 1-KiB DMA pieces
 template <int HS>
@@ -54,32 +45,6 @@ struct Cfg {
     static constexpr int NPW = 64 / RPP / 4;        // pieces per wave and tile
     static constexpr int WPC = HS <= 128 ? 2 : 1;   // workgroups per CU (registers: 2 x 256 or 1 x 512 per SIMD lane)
 };
-
-// accumulator register r of half `half` -> row inside the 32-row tile; ccol: the part that does not depend on the lane
-__device__ __forceinline__ constexpr int ccol(int r) { return (r & 3) + 8 * (r >> 2); }
-__device__ __forceinline__ int crow(int r, int half) { return ccol(r) + 4 * half; }
-
-__device__ __forceinline__ f32x16 zero16() {
-    f32x16 z;
-#pragma unroll
-    for (int r = 0; r < 16; ++r) z[r] = 0.f;
-    return z;
-}
-
-__device__ __forceinline__ bf16x8 pack8(const f32x16& a, int s) {
-    Frag f;
-    f.u.x = pack_bf16x2(a[8 * s + 0], a[8 * s + 1]);
-    f.u.y = pack_bf16x2(a[8 * s + 2], a[8 * s + 3]);
-    f.u.z = pack_bf16x2(a[8 * s + 4], a[8 * s + 5]);
-    f.u.w = pack_bf16x2(a[8 * s + 6], a[8 * s + 7]);
-    return f.v;
-}
-
-__device__ __forceinline__ bf16x8 ldfrag(const bf16_t* p, bool ok) {
-    Frag f;
-    f.u = ok ? *reinterpret_cast<const uint4*>(p) : make_uint4(0, 0, 0, 0);
-    return f.v;
-}
 
 // reductions over the two 32-lane halves (lanes l and l + 32 hold the same query / key): v_permlane32_swap_b32 exchanges the upper half of
 // its first operand with the lower half of its second -- fed the same value twice it returns {low half everywhere, high half everywhere}
@@ -193,25 +158,8 @@ __device__ __forceinline__ void decode_block(int id, int BH, int nx, int order, 
     }
 }
 
-__device__ __forceinline__ int64_t drop_tile(int bh, int nt, int qt, int kt) { return (((int64_t)bh * nt + qt) * nt + kt) * 16; }
-
-// [ch][row] accumulators (NM tiles of 32 channels) -> row-major [row][HS channels] bf16: lane = row, 4 consecutive channels per
-// register quad (8-byte stores)
-template <int NM>
-__device__ __forceinline__ void store_ct(bf16_t* dst /* row base + head offset */, const f32x16 (&acc)[NM], int half, float mul) {
-#pragma unroll
-    for (int mt = 0; mt < NM; ++mt)
-#pragma unroll
-        for (int g = 0; g < 4; ++g) {
-            uint2 w;
-            w.x = pack_bf16x2(acc[mt][4 * g + 0] * mul, acc[mt][4 * g + 1] * mul);
-            w.y = pack_bf16x2(acc[mt][4 * g + 2] * mul, acc[mt][4 * g + 3] * mul);
-            *reinterpret_cast<uint2*>(dst + 32 * mt + 8 * g + 4 * half) = w;
-        }
-}
-
-// The same through a wave-private LDS slab (32 rows x HS channels, chunk c of row r at c ^ (r & 15)): 8-byte column writes, then whole
-// rows leave as 16-byte stores -- 16 lanes cover one 256-byte row segment instead of every lane touching 16 (32) different rows with
+// store_ct (attn_common.h) through a wave-private LDS slab (32 rows x HS channels, chunk c of row r at c ^ (r & 15)): 8-byte column
+// writes, then whole rows leave as 16-byte stores -- 16 lanes cover one 256-byte row segment instead of every lane touching 16 (32) different rows with
 // 8-byte stores.  `slab` must be LDS no wave of the workgroup still reads (the ring stage the last tile did NOT use); only this wave
 // touches it, so an LDS wait is all the synchronisation it needs.  nvalid: rows of the tile inside the sequence.
 template <int HS>
@@ -250,7 +198,7 @@ __device__ __forceinline__ void store_ct_lds(char* slab, bf16_t* dst_row0 /* row
 // forward ran 0.102 (0.276 with dropout) instead of 0.066 (0.086) ms at the p6c18 geometry, 0.379 instead of 0.148 ms at head size 256.
 // ------------------------------------------------------------------------------------------------------------------
 template <int HS, bool CAUSAL, bool DROP, bool WMASK>
-__global__ __launch_bounds__(256, Cfg<HS>::WPC) void attn2_fwd_kernel(Attn2Args p) {
+__global__ __launch_bounds__(256, Cfg<HS>::WPC) void attn2_fwd_kernel(AttnArgs p) {
 #if defined(__HIP_DEVICE_COMPILE__)
     using G = Cfg<HS>;
     constexpr int NS = G::NS, NM = G::NM, TILEB = G::TILEB;
@@ -416,7 +364,7 @@ __global__ __launch_bounds__(256, Cfg<HS>::WPC) void attn2_fwd_kernel(Attn2Args 
 // LDS: 2 stages x (K tile | V tile).
 // ------------------------------------------------------------------------------------------------------------------
 template <int HS, bool CAUSAL, bool DROP, bool MASKED>
-__global__ __launch_bounds__(256, Cfg<HS>::WPC) void attn2_bwd_dq_kernel(Attn2Args p) {
+__global__ __launch_bounds__(256, Cfg<HS>::WPC) void attn2_bwd_dq_kernel(AttnArgs p) {
 #if defined(__HIP_DEVICE_COMPILE__)
     using G = Cfg<HS>;
     constexpr int NS = G::NS, NM = G::NM, TILEB = G::TILEB;
@@ -561,7 +509,7 @@ __global__ __launch_bounds__(256, Cfg<HS>::WPC) void attn2_bwd_dq_kernel(Attn2Ar
 // diagonal needs a per-element test.
 // ------------------------------------------------------------------------------------------------------------------
 template <int HS, bool CAUSAL, int MODE, bool DROP, bool MASKED>
-__global__ __launch_bounds__(256, Cfg<HS>::WPC) void attn2_bwd_dkv_kernel(Attn2Args p) {
+__global__ __launch_bounds__(256, Cfg<HS>::WPC) void attn2_bwd_dkv_kernel(AttnArgs p) {
 #if defined(__HIP_DEVICE_COMPILE__)
     constexpr bool DO_DV = MODE == 1, DO_DK = MODE == 2;
     using G = Cfg<HS>;
@@ -613,7 +561,7 @@ __global__ __launch_bounds__(256, Cfg<HS>::WPC) void attn2_bwd_dkv_kernel(Attn2A
     // dropout: hash input of query 0 of (batch, head) bh for this lane's key; a query row adds T * rm
     const unsigned xkey = ((unsigned)((int64_t)bh * T * T) + (unsigned)krow + 4u * half * (unsigned)T) * p.rm + p.ra;
     const unsigned trm = (unsigned)T * p.rm;
-    // keep bits of this lane's key over a tile's 32 queries (attention.hip: drop_tile): one 4-byte load per tile
+    // keep bits of this lane's key over a tile's 32 queries (attn_common.h: drop_tile): one 4-byte load per tile
     const unsigned* mlane = reinterpret_cast<const unsigned*>(p.mask) + 2 * ((l31 & 3) + 4 * (l31 >> 3)) + ((l31 >> 2) & 1);
 
     // the keep words of a 64-query tile's two 32-query halves, fetched one tile ahead (a 4-byte load per lane and half from a 14-MB
@@ -702,7 +650,7 @@ static int order_env() {
 }
 
 template <typename K>
-void launch(K kernel, Attn2Args a, int lds, hipStream_t stream) {
+void launch(K kernel, AttnArgs a, int lds, hipStream_t stream) {
     a.order = (a.B * a.nh) % 8 == 0 ? order_env() : 0;
     const int nt = (a.T + 31) / 32;
     const dim3 grid((unsigned)(((nt + 3) / 4) * a.B * a.nh));
@@ -711,7 +659,7 @@ void launch(K kernel, Attn2Args a, int lds, hipStream_t stream) {
 }
 
 template <int HS, bool CAUSAL>
-void fwd_hs(const Attn2Args& a, hipStream_t stream) {
+void fwd_hs(const AttnArgs& a, hipStream_t stream) {
     const int lds = 4 * Cfg<HS>::TILEB;
     if (a.thr == 0) launch(attn2_fwd_kernel<HS, CAUSAL, false, false>, a, lds, stream);
     else if constexpr (CAUSAL) {
@@ -721,7 +669,7 @@ void fwd_hs(const Attn2Args& a, hipStream_t stream) {
 }
 
 template <int HS, bool CAUSAL, bool DROP, bool MASKED>
-void bwd_variant(const Attn2Args& a, hipStream_t stream) {
+void bwd_variant(const AttnArgs& a, hipStream_t stream) {
     const int lds_q = 4 * Cfg<HS>::TILEB, lds_kv = 2 * (2 * Cfg<HS>::TILEB + 512);
     launch(attn2_bwd_dq_kernel<HS, CAUSAL, DROP, MASKED>, a, lds_q, stream);                // first: it also produces dsum for the dK kernel
     launch(attn2_bwd_dkv_kernel<HS, CAUSAL, 1, DROP, MASKED>, a, lds_kv, stream);
@@ -731,13 +679,13 @@ void bwd_variant(const Attn2Args& a, hipStream_t stream) {
 }  // namespace
 
 // causal: head size 128 (dropout optional); full attention: head size 256, no dropout (attention.hip checks the geometry)
-int dvq_attn2_fwd(const Attn2Args& a, hipStream_t stream) {
+int dvq_attn2_fwd(const AttnArgs& a, hipStream_t stream) {
     if (a.causal) fwd_hs<128, true>(a, stream);
     else fwd_hs<256, false>(a, stream);
     return DVQ_OK;
 }
 
-int dvq_attn2_bwd(const Attn2Args& a, hipStream_t stream) {
+int dvq_attn2_bwd(const AttnArgs& a, hipStream_t stream) {
     if (!a.causal) bwd_variant<256, false, false, false>(a, stream);
     else if (a.thr == 0) bwd_variant<128, true, false, false>(a, stream);
     else if (a.mask != nullptr) bwd_variant<128, true, true, true>(a, stream);

@@ -1079,73 +1079,60 @@ def attn_causal_ok(x, n_head, b, t):
 
 
 def _attn_scratch(q, b, t, n_head, backward):
+    """scratch of an attention call, None where the kernels that run need none (forward of head sizes 128 / 256)"""
     nbytes = lib().dvq_attn_causal_scratch_bytes(b, t, n_head, q.shape[-1] // n_head, int(backward))
-    return torch.empty(nbytes, dtype=torch.uint8, device=q.device)
+    return torch.empty(nbytes, dtype=torch.uint8, device=q.device) if nbytes else None
+
+
+def _attn_pitch(a, b, c):
+    """row pitch shared by q, k, v (or dq, dk, dv): contiguous [M, C] tensors, or column blocks of one [M, 3 C] tensor"""
+    s = a.stride()
+    if len(s) == 2 and s[1] == 1 and b.stride() == s and c.stride() == s and a.shape == b.shape == c.shape:
+        return s[0]
+    if a.is_contiguous() and b.is_contiguous() and c.is_contiguous():
+        return a.shape[-1]
+    raise _lib.DvqError("attention operands must be contiguous, or 2-d column blocks that share one row pitch")
 
 
 def attn_causal_drop_mask(q, b, t, n_head):
-    """buffer for the forward's dropout keep decisions (1 bit per score of the causal tiles; csrc/attention.hip: drop_tile)"""
+    """buffer for the forward's dropout keep decisions (1 bit per score of the causal tiles; csrc/attn_common.h: drop_tile)"""
     return torch.empty(lib().dvq_attn_causal_mask_bytes(b, t, n_head) // 8, dtype=torch.int64, device=q.device)
 
 
 def attn_causal_fwd(q, k, v, b, t, n_head, scale, p_drop=0.0, seed=0, drop_mask=None):
-    """q, k, v [B*T, C] -> (out [B*T, C], lse fp32 [B, n_head, T]); drop_mask (attn_causal_drop_mask): receives the keep decisions"""
-    out = torch.empty_like(q)
+    """q, k, v [B*T, C], contiguous or column blocks of ONE projection output [B*T, 3 C] (no copies: the kernels take the row pitch; head
+    size 128) -> (out [B*T, C], lse fp32 [B, n_head, T]); drop_mask (attn_causal_drop_mask): receives the keep decisions"""
+    ld = _attn_pitch(q, k, v)
+    out = torch.empty(q.shape, dtype=q.dtype, device=q.device)
     lse = torch.empty(b, n_head, t, dtype=torch.float32, device=q.device)
     scratch = _attn_scratch(q, b, t, n_head, False)
     c = q.shape[-1]
     _timed("attn_causal_fwd", 2 * b * t * t * c, 4 * q.numel() * q.element_size(), lambda: check(
-        lib().dvq_attn_causal_fwd(_p(q), _p(k), _p(v), dt(q), b, t, n_head, c // n_head, float(scale), float(p_drop),
+        lib().dvq_attn_causal_fwd(_praw(q), _praw(k), _praw(v), ld, dt(q), b, t, n_head, c // n_head, float(scale), float(p_drop),
                                   int(seed) & 0xFFFFFFFFFFFFFFFF, _p(out), _p(lse), _p(scratch), _p(drop_mask), _s()),
         "dvq_attn_causal_fwd"))
     return out, lse
 
 
-def attn_causal_bwd(q, k, v, out, dout, lse, b, t, n_head, scale, p_drop=0.0, seed=0, drop_mask=None):
-    """drop_mask: the buffer the forward filled with the same (p_drop, seed); None: the decisions are hashed again"""
-    dq, dk, dv = torch.empty_like(q), torch.empty_like(q), torch.empty_like(q)
+def attn_causal_bwd(q, k, v, out, dout, lse, b, t, n_head, scale, p_drop=0.0, seed=0, drop_mask=None, grads=None):
+    """drop_mask: the buffer the forward filled with the same (p_drop, seed); None: the decisions are hashed again.  grads: (dq, dk, dv)
+    to write, laid out like q, k, v (column blocks of one [B*T, 3 C] matrix that one input-gradient GEMM consumes); None: new tensors"""
+    ld = _attn_pitch(q, k, v)
+    if grads is None:
+        if ld != q.shape[-1]:
+            raise _lib.DvqError("attn_causal_bwd: q, k, v with a row pitch need grads laid out like them")
+        grads = tuple(torch.empty_like(q) for _ in range(3))
+    if _attn_pitch(*grads) != ld or grads[0].shape != q.shape:
+        raise _lib.DvqError("attn_causal_bwd: grads must share the shape and row pitch of q, k, v")
+    dq, dk, dv = grads
     scratch = _attn_scratch(q, b, t, n_head, True)
     c = q.shape[-1]
     _timed("attn_causal_bwd", 5 * b * t * t * c, 8 * q.numel() * q.element_size(), lambda: check(
-        lib().dvq_attn_causal_bwd(_p(q), _p(k), _p(v), _p(out), _p(dout), _p(lse), dt(q), b, t, n_head, c // n_head, float(scale),
-                                  float(p_drop), int(seed) & 0xFFFFFFFFFFFFFFFF, _p(dq), _p(dk), _p(dv), _p(scratch), _p(drop_mask), _s()),
+        lib().dvq_attn_causal_bwd(_praw(q), _praw(k), _praw(v), ld, _p(out), _p(dout), _p(lse), dt(q), b, t, n_head, c // n_head,
+                                  float(scale), float(p_drop), int(seed) & 0xFFFFFFFFFFFFFFFF, _praw(dq), _praw(dk), _praw(dv),
+                                  _p(scratch), _p(drop_mask), _s()),
         "dvq_attn_causal_bwd"))
     return dq, dk, dv
-
-
-def attn_causal_fwd_fused(qkv, cols, b, t, n_head, scale, p_drop=0.0, seed=0, drop_mask=None):
-    """q, k, v as column blocks of ONE projection output qkv [B*T, 3 C] (cols = their first columns, order (q, k, v)): no copies, the
-    kernels take the row pitch (dvq_attn_causal_fwd_ld; head size 128) -> (out [B*T, C], lse)"""
-    m, ld = qkv.shape
-    c = ld // 3
-    assert qkv.is_contiguous() and ld == 3 * c and c == n_head * 128
-    flat = qkv.view(-1)
-    q, k, v = (flat[o:] for o in cols)                 # (pointer offsets: the kernels walk rows with the pitch ld)
-    out = torch.empty(m, c, dtype=qkv.dtype, device=qkv.device)
-    lse = torch.empty(b, n_head, t, dtype=torch.float32, device=qkv.device)
-    _timed("attn_causal_fwd", 2 * b * t * t * c, 4 * m * c * qkv.element_size(), lambda: check(
-        lib().dvq_attn_causal_fwd_ld(_p(q), _p(k), _p(v), ld, dt(qkv), b, t, n_head, c // n_head, float(scale), float(p_drop),
-                                     int(seed) & 0xFFFFFFFFFFFFFFFF, _p(out), _p(lse), _p(drop_mask), _s()),
-        "dvq_attn_causal_fwd_ld"))
-    return out, lse
-
-
-def attn_causal_bwd_fused(qkv, cols, out, dout, lse, b, t, n_head, scale, p_drop=0.0, seed=0, drop_mask=None):
-    """-> dqkv [B*T, 3 C]: the three gradients as column blocks in the layout of qkv (one input-gradient GEMM consumes them)"""
-    m, ld = qkv.shape
-    c = ld // 3
-    flat = qkv.view(-1)
-    q, k, v = (flat[o:] for o in cols)
-    dqkv = torch.empty_like(qkv)
-    dflat = dqkv.view(-1)
-    dq, dk, dv = (dflat[o:] for o in cols)
-    scratch = _attn_scratch(out, b, t, n_head, True)
-    _timed("attn_causal_bwd", 5 * b * t * t * c, 8 * m * c * qkv.element_size(), lambda: check(
-        lib().dvq_attn_causal_bwd_ld(_p(q), _p(k), _p(v), ld, _p(out), _p(dout), _p(lse), dt(qkv), b, t, n_head, c // n_head, float(scale),
-                                     float(p_drop), int(seed) & 0xFFFFFFFFFFFFFFFF, _p(dq), _p(dk), _p(dv), _p(scratch), _p(drop_mask),
-                                     _s()),
-        "dvq_attn_causal_bwd_ld"))
-    return dqkv
 
 
 def attn_full_ok(q, t):
@@ -1159,7 +1146,7 @@ def attn_full_fwd(q, k, v, b, t, scale):
     c = q.shape[-1]
     out = torch.empty_like(q)
     lse = torch.empty(b, t, dtype=torch.float32, device=q.device)
-    scratch = torch.empty(lib().dvq_attn_full_scratch_bytes(b, t, c, 0), dtype=torch.uint8, device=q.device)
+    scratch = _attn_scratch(q, b, t, 1, False)
     _timed("attn_full_fwd", 4 * b * t * t * c, 4 * q.numel() * q.element_size(), lambda: check(
         lib().dvq_attn_full_fwd(_p(q), _p(k), _p(v), dt(q), b, t, c, float(scale), _p(out), _p(lse), _p(scratch), _s()),
         "dvq_attn_full_fwd"))
@@ -1169,7 +1156,7 @@ def attn_full_fwd(q, k, v, b, t, scale):
 def attn_full_bwd(q, k, v, out, dout, lse, b, t, scale):
     c = q.shape[-1]
     dq, dk, dv = torch.empty_like(q), torch.empty_like(q), torch.empty_like(q)
-    scratch = torch.empty(lib().dvq_attn_full_scratch_bytes(b, t, c, 1), dtype=torch.uint8, device=q.device)
+    scratch = _attn_scratch(q, b, t, 1, True)
     _timed("attn_full_bwd", 10 * b * t * t * c, 8 * q.numel() * q.element_size(), lambda: check(
         lib().dvq_attn_full_bwd(_p(q), _p(k), _p(v), _p(out), _p(dout), _p(lse), dt(q), b, t, c, float(scale), _p(dq), _p(dk), _p(dv),
                                 _p(scratch), _s()), "dvq_attn_full_bwd"))

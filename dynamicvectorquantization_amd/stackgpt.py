@@ -140,16 +140,16 @@ class CausalSelfAttention(nn.Module):
             m = x2d.shape[0]
             pk = self._qkv_pack()
             qkv = K.gemm_nt(x2d, pk["w"], m, 3 * c, c, c, c, 3 * c, bias=pk["b"], bias_mode=1).view(m, 3 * c)
-            cols = (c, 0, 2 * c)                                 # first columns of q, k, v in [k | q | v]
+            k, q, v = qkv[:, :c], qkv[:, c:2 * c], qkv[:, 2 * c:]  # column blocks [k | q | v]
             p_drop = self.attn_drop.p if self.training else 0.0
             seed = _next_seed() if p_drop > 0.0 else 0
             dm = None
             if tape is not None and p_drop > 0.0:
                 dm = K.attn_causal_drop_mask(x2d, b, t, nh)
-            y, lse = K.attn_causal_fwd_fused(qkv, cols, b, t, nh, 1.0 / math.sqrt(hs), p_drop, seed, drop_mask=dm)
+            y, lse = K.attn_causal_fwd(q, k, v, b, t, nh, 1.0 / math.sqrt(hs), p_drop, seed, drop_mask=dm)
             out = self.proj.fwd(y, _child(tape, "proj"))
             if tape is not None:
-                tape.s.update(qkv=qkv, cols=cols, fused=(p_drop, seed), y=y, lse=lse, drop_mask=dm, x=x2d, b=b, t=t)
+                tape.s.update(qkv=qkv, fused=(p_drop, seed), y=y, lse=lse, drop_mask=dm, x=x2d, b=b, t=t)
             if resid is not None:
                 return _drop_add(resid, out, self.resid_drop.p, self.training, tape, "rdrop")
             return _drop(out, self.resid_drop.p, self.training, tape, "rdrop")
@@ -238,15 +238,17 @@ class CausalSelfAttention(nn.Module):
         """backward of the fused-projection forward: attention backward into [dk | dq | dv] ([M, 3 C]), ONE input-gradient GEMM over
         K = 3 C, the three weight / bias gradients from column blocks of that matrix (side stream, like Linear.bwd)"""
         s_ = tape.s
-        qkv, cols, x2d, b, t = s_["qkv"], s_["cols"], s_["x"], s_["b"], s_["t"]
+        qkv, x2d, b, t = s_["qkv"], s_["x"], s_["b"], s_["t"]
         m, c3 = qkv.shape
         c = c3 // 3
         nh, hs = self.n_head, c // self.n_head
         dout = dout_dropped if dout_dropped is not None else _drop_bwd(dout, tape, "rdrop")
         dy = self.proj.bwd(dout, tape.child("proj"))
         p_drop, seed = s_["fused"]
-        dqkv = K.attn_causal_bwd_fused(qkv, cols, s_["y"], dy, s_["lse"], b, t, nh, 1.0 / math.sqrt(hs), p_drop, seed,
-                                       drop_mask=s_.get("drop_mask"))
+        dqkv = torch.empty_like(qkv)                             # [dk | dq | dv], the layout of qkv
+        (k, q, v), (dk, dq, dv) = (tuple(m_[:, i * c:(i + 1) * c] for i in range(3)) for m_ in (qkv, dqkv))
+        K.attn_causal_bwd(q, k, v, s_["y"], dy, s_["lse"], b, t, nh, 1.0 / math.sqrt(hs), p_drop, seed, drop_mask=s_.get("drop_mask"),
+                          grads=(dq, dk, dv))
         pk = self._qkv_pack()
         dflat = dqkv.view(-1)
 

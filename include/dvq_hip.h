@@ -46,7 +46,9 @@ const char* dvq_last_error(void);
  * written in csrc ("conv3x3_halo_kernel", "conv_nt_pipe_kernel", ...; no template arguments, no fold / reduce / transpose helpers), noted
  * at the dispatch branch that launches it.  "" when nothing was noted (those entry points clear it first).  For timing labels. */
 const char* dvq_last_kernel(void);
-int dvq_version(void);     /* 121: dvq_halo_trace_read is gone (the timing experiments and the persistent 3x3 kernel left the sources: one library);
+int dvq_version(void);     /* 122: dvq_attn_causal_fwd / _bwd take the row pitch ldqkv (dvq_attn_causal_fwd_ld / _bwd_ld are gone); dvq_attn_causal_scratch_bytes
+                            * is what the kernels that run need (0 forward at head sizes 128 / 256: NULL scratch); dvq_attn_full_scratch_bytes is gone;
+                            * 121: dvq_halo_trace_read is gone (the timing experiments and the persistent 3x3 kernel left the sources: one library);
                             * 120: dvq_conv3x3_subpixel_ok, dvq_conv_desc.upsample == 2, bit 9 of the weight packs' dtype (nearest x2 + 3x3 convolutions
                             * as four 2x2 sub-pixel convolutions, forward and input gradient);
                             * 119: dvq_scalar_push (+ dvq_scalar_push_state_bytes), dvq_codebook_health (training metric logs);
@@ -540,41 +542,36 @@ int dvq_sample_guided(const void* logits, int dtype, int64_t B, int64_t V, int64
                       dvq_stream_t stream);
 /* Fused causal multi-head self-attention (bf16, head_dim 64 or 128) -- CausalSelfAttention.forward, stackgpt.py:41-69:
  *   out = attn_drop(softmax(causal_mask(q k^T * scale))) v      per (batch, head), scores never materialised.
- * q, k, v, out, dout, dq, dk, dv: [B*T][n_head*head_dim] row-major (head h = columns h*head_dim ..); T % 8 == 0;
+ * q, k, v, dq, dk, dv: [B*T] rows of n_head*head_dim columns (head h = columns h*head_dim ..), ldqkv elements between consecutive rows.
+ * ldqkv == n_head*head_dim: contiguous.  Head size 128 also takes a larger pitch (a multiple of 8, T * ldqkv * 2 < 2^32), e.g.
+ * 3 * n_head * head_dim when the three are column blocks of one fused [B*T][3 C] projection output (stackgpt.py:46-48 computes them as
+ * three Linear layers over the same input: one GEMM here) and the three gradients are written as column blocks of one [B*T][3 C]
+ * matrix that feeds ONE input-gradient GEMM.  out, dout: [B*T][n_head*head_dim], always contiguous.  T % 8 == 0.
  * lse: fp32 [B][n_head][T] (forward output, backward input); p_drop / seed: attention dropout (element index of the
  * [B][n_head][T][T] probability tensor, same generator as dvq_dropout; p_drop == 0: none).
- * scratch: dvq_attn_causal_scratch_bytes(B, T, n_head, head_dim, backward) bytes of device memory (channel-major operand copies).
+ * scratch: dvq_attn_causal_scratch_bytes(B, T, n_head, head_dim, backward) bytes of device memory -- what the kernels that run need:
+ * head size 64 its channel-major operand copies (one forward, three backward) and rowsum(dO * O) behind them; head sizes 128 and 256
+ * nothing forward and rowsum(dO * O) alone backward (B * n_head * T floats, rounded up to 256 bytes).  NULL exactly when that is 0.
  * drop_mask (may be NULL): dvq_attn_causal_mask_bytes(B, T, n_head) bytes; the forward stores its keep decisions there, one bit per
  * (query, key) of every causal 32 x 32 tile, and a backward given the same buffer reads them instead of hashing every element again
  * in each of its three kernels (identical results: test_fused_attention_drop_mask_equals_rehash).  NULL: decisions recomputed.
- * DVQ_ESHAPE when dtype / head_dim are not bf16 / 64 or 128: callers use the per-head GEMM path then.
- * dvq_attn_causal_ok: 1 when the entry points below take this geometry (the check they make themselves), else 0. */
+ * DVQ_ESHAPE when dtype / head_dim are not bf16 / 64 or 128 (callers use the per-head GEMM path then) or the pitch is not taken.
+ * dvq_attn_causal_ok: 1 when the entry points below take this geometry with contiguous rows (the check they make themselves), else 0. */
 int dvq_attn_causal_ok(int dtype, int64_t B, int64_t T, int n_head, int head_dim);
 int64_t dvq_attn_causal_scratch_bytes(int64_t B, int64_t T, int n_head, int head_dim, int backward);
 int64_t dvq_attn_causal_mask_bytes(int64_t B, int64_t T, int n_head);
-int dvq_attn_causal_fwd(const void* q, const void* k, const void* v, int dtype, int64_t B, int64_t T, int n_head, int head_dim,
-                        float scale, float p_drop, uint64_t seed, void* out, float* lse, void* scratch, void* drop_mask,
+int dvq_attn_causal_fwd(const void* q, const void* k, const void* v, int64_t ldqkv, int dtype, int64_t B, int64_t T, int n_head,
+                        int head_dim, float scale, float p_drop, uint64_t seed, void* out, float* lse, void* scratch, void* drop_mask,
                         dvq_stream_t stream);
-int dvq_attn_causal_bwd(const void* q, const void* k, const void* v, const void* out, const void* dout, const float* lse, int dtype,
-                        int64_t B, int64_t T, int n_head, int head_dim, float scale, float p_drop, uint64_t seed, void* dq, void* dk,
-                        void* dv, void* scratch, const void* drop_mask, dvq_stream_t stream);
-/* The same with a ROW PITCH for q, k, v (and dq, dk, dv): ldqkv elements between consecutive rows, e.g. 3 * n_head * head_dim when the
- * three are column blocks of one fused [B*T][3 C] projection output (stackgpt.py:46-48 computes them as three Linear layers over the
- * same input: one GEMM here) and the three gradients are written as column blocks of one [B*T][3 C] matrix that feeds ONE input-
- * gradient GEMM.  out / dout keep pitch C.  Head size 128 only (csrc/attention2.hip); the backward's scratch holds rowsum(dO * O):
- * dvq_attn_causal_scratch_bytes(.., backward = 1) bytes.  DVQ_ESHAPE otherwise. */
-int dvq_attn_causal_fwd_ld(const void* q, const void* k, const void* v, int64_t ldqkv, int dtype, int64_t B, int64_t T, int n_head,
-                           int head_dim, float scale, float p_drop, uint64_t seed, void* out, float* lse, void* drop_mask,
-                           dvq_stream_t stream);
-int dvq_attn_causal_bwd_ld(const void* q, const void* k, const void* v, int64_t ldqkv, const void* out, const void* dout, const float* lse,
-                           int dtype, int64_t B, int64_t T, int n_head, int head_dim, float scale, float p_drop, uint64_t seed, void* dq,
-                           void* dk, void* dv, void* scratch, const void* drop_mask, dvq_stream_t stream);
+int dvq_attn_causal_bwd(const void* q, const void* k, const void* v, int64_t ldqkv, const void* out, const void* dout, const float* lse,
+                        int dtype, int64_t B, int64_t T, int n_head, int head_dim, float scale, float p_drop, uint64_t seed, void* dq,
+                        void* dk, void* dv, void* scratch, const void* drop_mask, dvq_stream_t stream);
 /* Single-head FULL (non-causal) self-attention of the DQ-VAE's AttnBlock (modules/diffusionmodules/model.py:168-192:
- * w = softmax_j(q^T k * C^-1/2), h = v w^T) for C = 256 (bf16, T %% 32 == 0): the same flash kernels as above with one head of
- * size C, no mask, no dropout; q, k, v, out [B*T][C]; lse fp32 [B][T].  The [B,T,T] score tensor never reaches HBM.  Other
- * shapes (C = 512) return DVQ_ESHAPE: the caller keeps the GEMM + softmax path for them -- dvq_attn_full_ok tells (1 / 0). */
+ * w = softmax_j(q^T k * C^-1/2), h = v w^T) for C = 256 (bf16, T %% 32 == 0): the same flash kernels as causal head size 128 with one
+ * head of size C, no mask, no dropout; q, k, v, out [B*T][C]; lse fp32 [B][T].  The [B,T,T] score tensor never reaches HBM.  Other
+ * shapes (C = 512) return DVQ_ESHAPE: the caller keeps the GEMM + softmax path for them -- dvq_attn_full_ok tells (1 / 0).
+ * scratch: dvq_attn_causal_scratch_bytes(B, T, 1, C, backward) bytes (forward: 0, NULL). */
 int dvq_attn_full_ok(int dtype, int64_t B, int64_t T, int C);
-int64_t dvq_attn_full_scratch_bytes(int64_t B, int64_t T, int C, int backward);
 int dvq_attn_full_fwd(const void* q, const void* k, const void* v, int dtype, int64_t B, int64_t T, int C, float scale, void* out,
                       float* lse, void* scratch, dvq_stream_t stream);
 int dvq_attn_full_bwd(const void* q, const void* k, const void* v, const void* out, const void* dout, const float* lse, int dtype,

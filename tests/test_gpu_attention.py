@@ -250,3 +250,71 @@ def test_fused_qkv_projection_equals_three_linears(dev, monkeypatch, p_drop):
             for p_ in attn.parameters():
                 p_.add_(0.05 * torch.randn_like(p_))
         rt.bump_weights_epoch()
+
+
+def _qkv_blocks(m, c):
+    """(q, k, v) as column blocks [k | q | v] of one [M, 3 C] matrix, the layout of the fused projection"""
+    return m[:, c:2 * c], m[:, :c], m[:, 2 * c:]
+
+
+@pytest.mark.parametrize("p_drop", [0.0, 0.1])
+def test_fused_attention_row_pitch_equals_contiguous(dev, p_drop):
+    """head size 128 with q, k, v (and dq, dk, dv) as column blocks of one [M, 3 C] matrix against contiguous copies of the same
+    values: the same kernels, the same arithmetic in the same order, only the addresses differ -- bit for bit.  T = 72: a partial last
+    32-row tile and a partial 64-row operand tile"""
+    from dynamicvectorquantization_amd import kernels as K
+    b, t, nh, hs = 2, 72, 2, 128
+    c, scale, seed = nh * hs, 1.0 / math.sqrt(hs), 0x5EED0 + 72
+    g = torch.Generator(device="cpu").manual_seed(72)
+    qkv = torch.randn(b * t, 3 * c, generator=g).to(dev, torch.bfloat16)
+    do = torch.randn(b * t, c, generator=g).to(dev, torch.bfloat16)
+    res = []
+    for pitched in (True, False):
+        q, k, v = _qkv_blocks(qkv, c)
+        grads = None
+        if pitched:
+            assert q.stride() == (3 * c, 1) and not q.is_contiguous()
+            grads = _qkv_blocks(torch.full_like(qkv, float("nan")), c)
+        else:
+            q, k, v = q.contiguous(), k.contiguous(), v.contiguous()
+        dm = K.attn_causal_drop_mask(do, b, t, nh) if p_drop > 0 else None
+        out, lse = K.attn_causal_fwd(q, k, v, b, t, nh, scale, p_drop, seed, drop_mask=dm)
+        dq, dk, dv = K.attn_causal_bwd(q, k, v, out, do, lse, b, t, nh, scale, p_drop, seed, drop_mask=dm, grads=grads)
+        assert out.is_contiguous() and dq.stride(0) == (3 * c if pitched else c)
+        res.append((out, lse, dq.contiguous(), dk.contiguous(), dv.contiguous()))
+    torch.cuda.synchronize()
+    for name, a, r in zip(("out", "lse", "dq", "dk", "dv"), *res):
+        assert torch.equal(a, r), name
+
+
+def test_fused_attention_refuses_a_pitch_before_any_launch(dev):
+    """host-side geometry refusals of the row pitch: head size 64 takes contiguous rows only; a pitch must be a multiple of 8"""
+    from dynamicvectorquantization_amd import _lib, kernels as K
+    b, t = 1, 32
+    m64 = torch.zeros(b * t, 3 * 64, dtype=torch.bfloat16, device=dev)
+    q, k, v = _qkv_blocks(m64, 64)
+    with pytest.raises(_lib.DvqError):
+        K.attn_causal_fwd(q, k, v, b, t, 1, 0.125)
+    assert b"row pitch" in _lib.load().dvq_last_error() and b"head size 128" in _lib.load().dvq_last_error()
+    out, lse = torch.zeros(b * t, 64, dtype=torch.bfloat16, device=dev), torch.zeros(b, 1, t, device=dev)
+    with pytest.raises(_lib.DvqError):
+        K.attn_causal_bwd(q, k, v, out, out, lse, b, t, 1, 0.125, grads=_qkv_blocks(torch.zeros_like(m64), 64))
+    assert b"row pitch" in _lib.load().dvq_last_error()
+    m128 = torch.zeros(b * t, 3 * 128 + 4, dtype=torch.bfloat16, device=dev)             # pitch 388: not a multiple of 8
+    q, k, v = (m128[:, i * 128:(i + 1) * 128] for i in range(3))
+    with pytest.raises(_lib.DvqError):
+        K.attn_causal_fwd(q, k, v, b, t, 1, 128 ** -0.5)
+    assert b"pitch" in _lib.load().dvq_last_error()
+
+
+@pytest.mark.parametrize("hs,nh", [(128, 2), (256, 1)])
+def test_attention_forward_scratch_is_none_at_head_sizes_128_and_256(dev, hs, nh):
+    """the second-generation kernels read their operands in place: no forward scratch is allocated (the parity tests of this file run
+    through that path); the backward keeps rowsum(dO * O) only; head size 64 keeps its channel-major copies"""
+    from dynamicvectorquantization_amd import kernels as K
+    b, t = 2, 64
+    q = torch.empty(b * t, nh * hs, dtype=torch.bfloat16, device=dev)
+    assert K._attn_scratch(q, b, t, nh, False) is None
+    assert K._attn_scratch(q, b, t, nh, True).numel() == (b * nh * t * 4 + 255) // 256 * 256
+    q64 = torch.empty(b * t, 64, dtype=torch.bfloat16, device=dev)
+    assert K._attn_scratch(q64, b, t, 1, False).numel() == q64.numel() * 2

@@ -393,6 +393,20 @@ def test_attn_full_ok_table():
     ])
 
 
+def test_attn_causal_scratch_bytes_table():
+    """dvq_attn_causal_scratch_bytes(B, T, n_head, head_dim, backward): what the kernels that run need -- head size 64 its channel-major
+    copies (+ rowsum(dO * O) backward), head sizes 128 / 256 nothing forward and rowsum(dO * O), rounded up to 256 bytes, backward"""
+    lib_fn = __import__("dynamicvectorquantization_amd._lib", fromlist=["load"]).load().dvq_attn_causal_scratch_bytes
+    cases = [
+        ((2, 64, 4, 64, 0), 2 * 64 * 256 * 2), ((2, 64, 4, 64, 1), 3 * 2 * 64 * 256 * 2 + 2048),
+        ((2, 64, 4, 128, 0), 0), ((2, 64, 4, 128, 1), 2048),
+        ((1, 8, 1, 128, 1), 256),                                                                           # the round-up
+        ((2, 32, 1, 256, 0), 0), ((2, 32, 1, 256, 1), 256),
+    ]
+    bad = [(args, want, lib_fn(*args)) for args, want in cases if lib_fn(*args) != want]
+    assert not bad, f"dvq_attn_causal_scratch_bytes: (args, expected, got) = {bad}"
+
+
 def test_decode_stack_ok_table():
     """dvq_decode_stack_ok(B, C, n_head, F, Tmax): both sides of every bound of dvq_decode_stack's shape check (csrc/decode.hip)"""
     _table("dvq_decode_stack_ok", [
@@ -497,7 +511,7 @@ def test_one_library_without_probe_code():
     lib = _lib.load()
     assert not hasattr(lib, "dvq_halo_trace_read")
     assert not hasattr(lib, "dvq_conv3x3_halo2_try")
-    assert lib.dvq_version() == 121
+    assert lib.dvq_version() == 122
 
 
 # the environment names the Python package reads that are paths or build inputs, not switches: read where they are used
