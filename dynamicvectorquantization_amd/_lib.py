@@ -224,6 +224,10 @@ SIGNATURES = {
     "dvq_scalar_push_state_bytes": (sz, [i64]),
     "dvq_scalar_push": (i32, [C.POINTER(ScalarRecord), i32, i32, i32, vp, vp]),
     "dvq_codebook_health": (i32, [vp, i32, i64, i64, vp, vp, vp, vp]),
+    "dvq_codec_tables": (i32, [vp, i32, i64, i64, i64, vp, i64, i64, i64, vp, i64, i64, i64, vp, vp, vp]),
+    "dvq_codec_record": (i32, [vp, i32, i64, i64, i64, vp, i64, i64, i64, vp, i64, i64, i64, vp, vp, vp, i64, i64, vp, vp, vp]),
+    "dvq_codec_encode": (i32, [vp, i64, i64, i64, vp, vp, vp, i64, vp, vp, vp]),
+    "dvq_codec_decode_step": (i32, [vp, i32, i64, i64, i64, vp, i64, i64, i64, vp, i64, i64, i64, vp, vp, vp, i64, vp, vp, vp]),
 }
 
 

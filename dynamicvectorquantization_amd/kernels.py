@@ -1457,6 +1457,94 @@ def sample_guided(logits2d, guidance, temperature, pad_code, state, forbid_idx=N
     return out
 
 
+# ---------------------------------------------------------------------------------------------
+# lossless token codec (csrc/codec.hip, docs/design/27-token-codec.md)
+# ---------------------------------------------------------------------------------------------
+CODEC_PREC, CODEC_M, CODEC_L = 16, 1 << 16, 1 << 31
+CODEC_ERRORS = {1: "a token the model's rule forbids (frequency 0)", 2: "a read past the end of a word stream",
+                4: "a live row with no allowed symbol", 8: "no symbol under the coder's state"}
+
+
+def _codec_rule(logits2d, pad_code, forbid_idx, forbid_from, forbid_codes, keep_code, late_forbid_code, finished):
+    """the leading arguments (logits + constraint rule) that the four dvq_codec_* row kernels share, and what they keep alive"""
+    b, v = logits2d.shape
+    fi, n_forbid, ld, ff, codes, fin = _sample_args(logits2d, forbid_idx, forbid_from, forbid_codes, finished)
+    assert (fi is None or (fi.dtype == torch.int64 and fi.shape[0] >= b)) and (fin is None or fin.numel() >= b)
+    return (_praw(logits2d), dt(logits2d), b, v, logits2d.stride(0), _p(fi), n_forbid, ld, ff, codes, int(keep_code),
+            int(late_forbid_code), int(pad_code), _p(fin)), (fi, fin, codes)
+
+
+def codec_tables(logits2d, pad_code, forbid_idx=None, forbid_from=None, forbid_codes=(), keep_code=-1, late_forbid_code=-1,
+                 finished=None):
+    """the codec's integer frequency table of every row of logits2d [B, V] (V <= 2048) under a constraint rule (the rule arguments of
+    sample_constrained): int32 [B, V], sum 65536 per row (dvq_codec_tables; for tests and inspection)"""
+    b, v = logits2d.shape
+    out = torch.empty(b, v, dtype=torch.int32, device=logits2d.device)
+    args, keep = _codec_rule(logits2d, pad_code, forbid_idx, forbid_from, forbid_codes, keep_code, late_forbid_code, finished)
+    check(lib().dvq_codec_tables(*args, _p(out), _s()), "dvq_codec_tables")
+    return out
+
+
+def codec_record(logits2d, target, records, step, err, pad_code, forbid_idx=None, forbid_from=None, forbid_codes=(), keep_code=-1,
+                 late_forbid_code=-1, finished=None):
+    """records[:, step] (int32 [B, T]) = cum | f << 16 of target (int64 [B] or [B, 1]) under the row's table, 0 where the step codes
+    nothing; err int32 [B] collects error bits (CODEC_ERRORS).  -> int64 [B, 1], the token to feed onwards (dvq_codec_record)"""
+    b = logits2d.shape[0]
+    out = torch.empty(b, 1, dtype=torch.int64, device=logits2d.device)
+    tg = target.reshape(-1).contiguous()
+    assert tg.dtype == torch.int64 and tg.numel() == b and records.dtype == torch.int32 and records.shape[0] == b
+    assert records.stride(1) == 1
+    assert err.dtype == torch.int32 and err.numel() == b and err.is_contiguous() and 0 <= step < records.shape[1]
+    args, keep = _codec_rule(logits2d, pad_code, forbid_idx, forbid_from, forbid_codes, keep_code, late_forbid_code, finished)
+    check(lib().dvq_codec_record(*args, _p(tg), _p(records), records.stride(0), int(step), _p(out), _p(err), _s()), "dvq_codec_record")
+    return out
+
+
+def codec_encode(records, steps, counts=None, kinds=None, want_bits=False):
+    """rANS-code the first `steps` records of every row of records int32 [B, T] (counts int64 [B]: fewer for some rows), last to first.
+    -> (words int32 [B, steps + 2], nwords int64 [B], bits fp64 [B, 3] or None): row b's stream is words[b, steps + 2 - nwords[b]:];
+    bits = sum of log2(M / f) over the coded steps by kinds[step] (uint8 [steps], values 0 .. 2)"""
+    b = records.shape[0]
+    assert records.dtype == torch.int32 and records.stride(1) == 1 and 0 <= steps <= records.shape[1]
+    dev = records.device
+    cap = steps + 2
+    words = torch.zeros(b, cap, dtype=torch.int32, device=dev)
+    nwords = torch.empty(b, dtype=torch.int64, device=dev)
+    bits = torch.empty(b, 3, dtype=torch.float64, device=dev) if want_bits else None
+    if counts is not None:
+        counts = counts.reshape(-1).to(torch.int64).contiguous()
+        assert counts.numel() == b
+    if kinds is not None:
+        kinds = kinds.reshape(-1).to(torch.uint8).contiguous()
+        assert kinds.numel() >= steps
+    check(lib().dvq_codec_encode(_p(records), b, steps, records.stride(0), _p(counts), _p(kinds), _p(words), cap, _p(nwords), _p(bits),
+                                 _s()), "dvq_codec_encode")
+    return words, nwords, bits
+
+
+def codec_decode_state(words, base, count):
+    """the decoder's per-row state int64 [B, 4] = {rANS state, cursor, first word, word count} for streams laid out in `words` (int32,
+    flat) at base[b] .. base[b] + count[b] (int64 [B]; every count >= 2 and every stream inside `words`: the caller has checked)"""
+    w = words.reshape(-1)
+    base, count = base.reshape(-1).to(torch.int64), count.reshape(-1).to(torch.int64)
+    lo = w[base].to(torch.int64) & 0xFFFFFFFF
+    hi = w[base + 1].to(torch.int64) & 0xFFFFFFFF
+    return torch.stack([lo | (hi << 32), torch.full_like(base, 2), base, count], dim=1).contiguous()
+
+
+def codec_decode_step(logits2d, state, words, err, pad_code, forbid_idx=None, forbid_from=None, forbid_codes=(), keep_code=-1,
+                      late_forbid_code=-1, finished=None):
+    """one token per row from the rows' rANS states (codec_decode_state) under the rows' tables; the states advance and refill from
+    `words` with the cursor bounds-checked (dvq_codec_decode_step).  -> int64 [B, 1]"""
+    b = logits2d.shape[0]
+    out = torch.empty(b, 1, dtype=torch.int64, device=logits2d.device)
+    assert state.dtype == torch.int64 and state.shape == (b, 4) and state.is_contiguous()
+    assert words.dtype == torch.int32 and words.is_contiguous() and err.dtype == torch.int32 and err.numel() == b and err.is_contiguous()
+    args, keep = _codec_rule(logits2d, pad_code, forbid_idx, forbid_from, forbid_codes, keep_code, late_forbid_code, finished)
+    check(lib().dvq_codec_decode_step(*args, _p(state), _p(words), words.numel(), _p(out), _p(err), _s()), "dvq_codec_decode_step")
+    return out
+
+
 def label_dropout(labels, p, null_label, seed):
     """int64 [B] class labels -> labels with each replaced by null_label with probability p (dvq_label_dropout: dvq_dropout's hash of
     (seed, element index), so a seed reproduces the decisions)"""

@@ -314,6 +314,30 @@ class Dualformer(_SamplerMixinBase, nn.Module):
         """score() from stored codes (`tokens` = the permuter's dict of a token batch, c = what get_tc returns)"""
         return self._score_streams(tokens, c)
 
+    # ---- lossless token codec (codec.py, docs/design/27-token-codec.md)
+    def compress(self, x, c=None, batch_group=8, return_bits=False):
+        """rANS-code the images x with this model as the entropy model -> bytes; return_bits=True: (bytes, ideal bits fp64 [B, 3] by
+        stream: coarse position, coarse content, fine content).  c: class labels (class-conditional model).  The images of a group
+        of `batch_group` are coded together and decode together."""
+        from . import codec
+        return codec.compress(self, x, c, batch_group, return_bits)
+
+    def compress_tokens(self, tokens, c=None, batch_group=8, return_bits=False):
+        """compress() from stored codes (`tokens` = the permuter's dict of a token batch)"""
+        from . import codec
+        return codec.compress_tokens(self, tokens, c, batch_group, return_bits)
+
+    def decompress(self, blob, force=False):
+        """-> (indices [N, fine_hw, fine_hw], grain_indices [N, coarse_hw, coarse_hw]) of the images in `blob`, exactly what encode_to_z
+        gave compress.  Raises codec.CodecError for a damaged blob or one of another checkpoint / compute dtype (force=True tries)."""
+        from . import codec
+        return codec.decompress(self, blob, force)
+
+    def decompress_images(self, blob, force=False):
+        """decompress() through decode_to_img -> images [N, 3, H, W]"""
+        from . import codec
+        return codec.decompress_images(self, blob, force)
+
     def get_tc(self, batch):
         """(tokens, conditioning) of a token batch.  The unconditional start tokens only need the batch size and the device
         (PositionAwareSOSProvider.encode reads nothing else of its argument), so a stream stands in for the image that is not there"""
@@ -417,6 +441,26 @@ def _mask_rows(logits, finished, forbid, keep_code, pad_code):
     only_pad = neg.clone()
     only_pad[:, pad_code] = logits[:, pad_code]
     return torch.where(finished.bool().view(-1, 1), only_pad, out)
+
+
+class _SampleSource:
+    """where `_sample_cached` gets its next token from -- here: the constrained draw (`_draw_rule`).  A source has token(logits2d,
+    rule) -> int64 [B, 1] with rule = (kind, sampled positions or None, done flags), check() called once after the loop,
+    max_coarse_steps (None: the coarse stream runs until every row drew <eos>) and decode_state (set by the loop).  The token codec
+    brings the other two: codec.RecordSource and codec.DecodeSource."""
+    max_coarse_steps = None
+    decode_state = None
+
+    def __init__(self, model, temperature, sample, top_k, top_p, top_k_pos, top_p_pos, cfg):
+        self.model, self.temperature, self.sample, self.cfg = model, temperature, sample, cfg
+        self.content, self.position = (top_k, top_p), (top_k_pos, top_p_pos)
+
+    def token(self, logits2d, rule):
+        k, p = self.content if rule[0] == "content" else self.position
+        return self.model._draw_rule(logits2d, self.temperature, self.sample, k, p, rule, self.cfg)
+
+    def check(self):
+        pass
 
 
 class _SamplerMixin:
@@ -542,12 +586,15 @@ class _SamplerMixin:
 
     @torch.no_grad()
     def _sample_cached(self, c_coarse, c_fine, c_pos_coarse, c_pos_fine, c_seg_coarse, c_seg_fine, temperature, sample, top_k, top_p,
-                       top_k_pos, top_p_pos, fix_fine_position, cfg=None):
+                       top_k_pos, top_p_pos, fix_fine_position, cfg=None, source=None):
         """the same sampler with K/V caches: every step feeds ONE new row to each transformer instead of recomputing the whole
         prefix (the reference's O(T^2) schedule).  The content transformer's coarse rows are re-filled once when the fine
         stream starts, because the reference pairs them with different update positions in the two phases
-        (stackgpt.py:263 vs :331: shifted coarse positions while sampling coarse, unshifted ones afterwards)."""
+        (stackgpt.py:263 vs :331: shifted coarse positions while sampling coarse, unshifted ones afterwards).
+        `source` says where the next token comes from: None = the constrained draw (_SampleSource); the token codec passes
+        codec.RecordSource (the image's own tokens, their probabilities recorded) or codec.DecodeSource (a bitstream)."""
         from .stackgpt import DecodeState
+        src = source if source is not None else _SampleSource(self, temperature, sample, top_k, top_p, top_k_pos, top_p_pos, cfg)
         tr = self.transformer
         cpe, fpe = tr.content_coarse_pos_emb.weight, tr.content_fine_pos_emb.weight
         seg = self.activate_segment
@@ -569,16 +616,21 @@ class _SamplerMixin:
                 pool.pop(k_)
             st = pool[key] = DecodeState(tr, b, rows)
         st.reset()
+        src.decode_state = st
         zeros1 = torch.zeros(b, 1, dtype=torch.long, device=dev)
         # ---- coarse stream
         done = torch.zeros(b, 1, device=dev)
+        coarse_steps = 0
         while not torch.all(done.bool()):
+            if src.max_coarse_steps is not None and coarse_steps >= src.max_coarse_steps:      # (a bitstream never sets the length)
+                break
+            coarse_steps += 1
             pl = st.position_rows(x_c[:, -1:], x_pc[:, -1:], cpe, None, x_sc[:, -1:] if seg else None)
-            ix_pos = self._draw_rule(pl, temperature, sample, top_k_pos, top_p_pos, ("coarse_pos", x_pc, done), cfg)
+            ix_pos = src.token(pl, ("coarse_pos", x_pc, done))
             x_pc = torch.cat((x_pc, ix_pos), dim=1)
             done = done + (ix_pos == self.coarse_position_eos_code)
             cl = st.content_rows(ix_pos, cpe)
-            ix = self._draw_rule(cl, temperature, sample, top_k, top_p, ("content", None, done), cfg)
+            ix = src.token(cl, ("content", None, done))
             if seg:
                 x_sc = torch.cat([x_sc, zeros1], dim=1)
             x_c = torch.cat((x_c, ix), dim=1)
@@ -612,7 +664,7 @@ class _SamplerMixin:
                 ix_pos = plan[:, j].unsqueeze(-1)
                 j += 1
             else:
-                ix_pos = self._draw_rule(pl, temperature, sample, top_k_pos, top_p_pos, ("fine_pos", taken, done), cfg)
+                ix_pos = src.token(pl, ("fine_pos", taken, done))
                 taken = torch.cat([taken, ix_pos], dim=1)
             x_pf = torch.cat((x_pf, ix_pos), dim=1)
             done = done + (ix_pos == self.fine_position_eos_code)
@@ -627,11 +679,12 @@ class _SamplerMixin:
             if cl is None:                                   # no fine <sos>: the first fine content comes from the last coarse row
                 st.reset_content()
                 cl = st.content_rows(x_pc[:, :n_coarse], cpe)
-            ix = self._draw_rule(cl, temperature, sample, top_k, top_p, ("content", None, done), cfg)
+            ix = src.token(cl, ("content", None, done))
             x_f = torch.cat((x_f, ix), dim=1)
             if seg:
                 x_sf = torch.cat([x_sf, zeros1 + 1], dim=1)
         st.check()                   # the persistent token-step kernel reports a barrier time-out here: never return garbage tokens
+        src.check()                  # the codec's device error words, read once per run
         x_c, x_pc = x_c[:, c_coarse.shape[1]:], x_pc[:, c_pos_coarse.shape[1]:]
         if self.activate_sos_for_fine_sequence:
             x_f, x_pf = x_f[:, c_fine.shape[1]:], x_pf[:, c_fine.shape[1]:]

@@ -917,6 +917,42 @@ int dvq_image_grid_shape(int64_t N, int64_t H, int64_t W, int64_t nrow, int64_t 
 int dvq_image_grid_u8(const float* x, int64_t N, int64_t C, int64_t H, int64_t W, int64_t nrow, int64_t padding, int clamp, uint8_t* out,
                       size_t out_bytes, void* ws, size_t ws_bytes, dvq_stream_t stream);
 
+/* Lossless token codec (csrc/codec.hip, docs/design/27-token-codec.md): rANS driven by the DQ-Transformer's next-token distributions.
+ * The frequency table of a logits row [V <= 2048] of `dtype` (row pitch ldl) under a constraint rule -- the rule arguments of
+ * dvq_sample_constrained: forbid_idx int64 [B][forbid_ld] (n_forbid used), forbid_from (< 0: none), forbid_codes4 (host int64 [4], -1:
+ * unused), keep_code, late_forbid_code, pad_code, finished fp32 [B] or NULL -- is
+ *   A = the columns the rule leaves to a live row and whose logit is finite (a finished row: {pad_code}), n = |A|, M = 65536;
+ *   n == 1: f = M on that column;  n == 0: f = 0 everywhere;
+ *   n >= 2: e_c = expf(x_c - max_A x), S = sum_A e_c in fp32 (lane l of 64 adds columns l, l + 64, ... in ascending order, then a fixed
+ *           xor tree), f_c = 1 + floor(e_c / S * (M - n)) on A, 0 elsewhere, and M - sum f is added to the lowest-index arg-max of A.
+ * The coder is rANS: 64-bit state, lower bound 2^31, 32-bit words, 16-bit frequencies, one state and one word stream per row.
+ * err uint32 [B] is sticky (bits are only ever set): 1 = a target with f = 0 (or outside [0, V)), 2 = a read past the end of a stream
+ * (it yields a zero word), 4 = a live row with an empty allowed set, 8 = internal (no column under the state).
+ * dvq_codec_tables: table uint32 [B][V] = f.  For tests and inspection.
+ * dvq_codec_record: records[row * rec_ld + step] = cum | f << 16 of target[row] (int64 [B]), or 0 when the step codes nothing (finished
+ *   row, n == 1, or an error); token int64 [B] = the target for a live row (pad_code when it lies outside [0, V)), pad_code for a finished one.
+ * dvq_codec_encode: records uint32 [B][rec_ld], the first min(counts[row], T) steps of a row are coded (counts int64 [B] or NULL: T), last
+ *   to first; row b's words end at words + (b + 1) * cap (uint32 [B][cap], cap >= T + 2), nwords int64 [B] = how many: the stream is
+ *   words[(b + 1) * cap - nwords[b] ...], its first two words the final state (low half first).  bits fp64 [B][3] or NULL: sum of
+ *   16 - log2 f over the coded steps with kinds[step] = 0, 1, 2 (uint8 [T]; NULL: all 0; >= 3: not counted), in a fixed order.
+ * dvq_codec_decode_step: state int64 [B][4] = {rANS state, cursor, index of the row's first word in `words`, words in its stream}
+ *   (the caller starts with state = word 0 | word 1 << 32, cursor = 2); token int64 [B] = the column c with cum_c <= state mod M <
+ *   cum_c + f_c (pad_code for a finished row, the one allowed column when n == 1); the state advances and refills at most one word
+ *   from words[base + cursor] iff cursor < count and base + cursor < total_words -- otherwise a zero word and error bit 2. */
+int dvq_codec_tables(const void* logits, int dtype, int64_t B, int64_t V, int64_t ldl, const int64_t* forbid_idx, int64_t n_forbid,
+                     int64_t forbid_ld, int64_t forbid_from, const int64_t* forbid_codes4, int64_t keep_code, int64_t late_forbid_code,
+                     int64_t pad_code, const float* finished, uint32_t* table, dvq_stream_t stream);
+int dvq_codec_record(const void* logits, int dtype, int64_t B, int64_t V, int64_t ldl, const int64_t* forbid_idx, int64_t n_forbid,
+                     int64_t forbid_ld, int64_t forbid_from, const int64_t* forbid_codes4, int64_t keep_code, int64_t late_forbid_code,
+                     int64_t pad_code, const float* finished, const int64_t* target, uint32_t* records, int64_t rec_ld, int64_t step,
+                     int64_t* token, uint32_t* err, dvq_stream_t stream);
+int dvq_codec_encode(const uint32_t* records, int64_t B, int64_t T, int64_t rec_ld, const int64_t* counts, const uint8_t* kinds,
+                     uint32_t* words, int64_t cap, int64_t* nwords, double* bits, dvq_stream_t stream);
+int dvq_codec_decode_step(const void* logits, int dtype, int64_t B, int64_t V, int64_t ldl, const int64_t* forbid_idx, int64_t n_forbid,
+                          int64_t forbid_ld, int64_t forbid_from, const int64_t* forbid_codes4, int64_t keep_code,
+                          int64_t late_forbid_code, int64_t pad_code, const float* finished, int64_t* state, const uint32_t* words,
+                          int64_t total_words, int64_t* token, uint32_t* err, dvq_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif
