@@ -467,14 +467,40 @@ class GradBuckets:
         return (lo or 0), (hi or 0)
 
 
-def reference_learning_rate(model_cfg, world, batch_size):
-    """train.py:248-257 of the reference: lr = ngpu * batch_size * base_learning_rate when the config gives a base rate, else
-    the absolute `learning_rate`"""
+def reference_learning_rate(model_cfg, world, batch_size, accumulate_grad_batches=1):
+    """train.py:248-257 of the reference: lr = accumulate_grad_batches * ngpu * batch_size * base_learning_rate when the config gives
+    a base rate (the reference pins the first factor to 1, and so does every caller here until the Trainer accumulates), else the
+    absolute `learning_rate`"""
     if "base_learning_rate" in model_cfg:
-        return world * batch_size * model_cfg["base_learning_rate"]
+        return accumulate_grad_batches * world * batch_size * model_cfg["base_learning_rate"]
     if "learning_rate" in model_cfg:
         return model_cfg["learning_rate"]
     raise NotImplementedError("Please set learning rate!")
+
+
+# ---- accumulation windows (docs/design/28-gradient-accumulation.md): the host arithmetic HipAdam.set_window is fed from -------------------
+def window_flags(pos, batch_in_epoch, k, batches_per_epoch=None):
+    """(first, last) of a micro-batch under Lightning 1.5's accumulation: `pos` micro-batches of its window have run before it, it is
+    batch `batch_in_epoch` of its epoch.  A window closes after k micro-batches or with the epoch's last batch, whichever comes
+    first; batches_per_epoch None: epochs never cut a window.  From an epoch's start pos == batch_in_epoch % k, i.e. the window
+    closes when (batch_in_epoch + 1) % k == 0."""
+    last = pos + 1 >= k or (batches_per_epoch is not None and batch_in_epoch + 1 >= batches_per_epoch)
+    return pos == 0, last
+
+
+def window_schedule(n_batches, k, batches_per_epoch=None):
+    """[(first, last)] of batches 0 .. n_batches - 1 of a run that starts at an epoch's start"""
+    out, pos = [], 0
+    for b in range(n_batches):
+        first, last = window_flags(pos, b % batches_per_epoch if batches_per_epoch else b, k, batches_per_epoch)
+        out.append((first, last))
+        pos = 0 if last else pos + 1
+    return out
+
+
+def optimizer_steps_per_epoch(batches_per_epoch, k):
+    """ceil(batches / k): the short last window of an epoch is an optimizer step too"""
+    return -(-int(batches_per_epoch) // int(k))
 
 
 def _replicated_tensors(model):
