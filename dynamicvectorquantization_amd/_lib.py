@@ -181,6 +181,8 @@ SIGNATURES = {
     "dvq_jpeg_entropy_decode": (i32, [vp, sz, vp, i64, vp]),
     "dvq_jpeg_desc_bytes": (sz, []),
     "dvq_jpeg_batch_decode": (i32, [vp, vp, i64, vp, vp, vp]),
+    "dvq_png_desc_bytes": (sz, []),
+    "dvq_png_batch_unfilter": (i32, [vp, vp, i64, vp, vp]),
     "dvq_adamw_dev": (i32, [vp, vp, vp, vp, i64, vp, vp]),
     "dvq_grad_sqnorm_workspace_bytes": (sz, [i64]),
     "dvq_grad_sqnorm": (i32, [vp, i64, f32, i32, vp, sz, vp, vp]),

@@ -20,6 +20,7 @@ _P = "dynamicvectorquantization_amd."
 
 # reference dotted path -> (module in this package, attribute)
 TARGET_ALIASES = {
+    "data.faceshq.FFHQ": (_P + "data", "FFHQ"),
     "models.stage1_dynamic.dqvae_dual_entropy.DualGrainVQModel": (_P + "dqvae", "DualGrainVQModel"),
     "models.stage1_dynamic.dqvae_dual_entropy.Entropy": (_P + "dqvae", "Entropy"),
     "models.stage1_dynamic.dqvae_dual_feat.DualGrainVQModel": (_P + "dqvae", "DualGrainFeatVQModel"),

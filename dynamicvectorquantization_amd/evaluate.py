@@ -381,11 +381,12 @@ def folder_dataset(root: str, limit: int | None = None):
 
 
 def image_batches(batch_size: int, size: int, device, images: str | None = None, synthetic: int = 0, limit: int | None = None,
-                  seed: int = 2021, num_workers: int = 8, device_decode: bool = False):
+                  seed: int = 2021, num_workers: int = 8, device_decode: bool = False, device_png: bool = False):
     """NCHW fp32 [b,3,size,size] device batches in [-1, 1], streamed (never the whole set in host memory):
     synthetic > 0: synth.half_flat_images per batch; images = *.npy: memory-mapped [N,3,H,W] fp32, read per batch; images = folder:
     decoded on host threads, transformed on the GPU (data.GpuBatchLoader, the eval transform: Resize + CenterCrop); device_decode: its
-    JPEG files through the device decoder (docs/design/23-device-jpeg.md) -- the same pixels, less host work per image"""
+    JPEG files through the device decoder (docs/design/23-device-jpeg.md) -- the same pixels, less host work per image; device_png: its
+    PNG files likewise (docs/design/29-device-png.md)"""
     import numpy as np
 
     from . import data, synth
@@ -402,7 +403,7 @@ def image_batches(batch_size: int, size: int, device, images: str | None = None,
             yield torch.from_numpy(np.array(a[i:min(i + batch_size, n)], dtype=np.float32)).to(device)     # a writable copy of the slice
     elif images is not None:
         loader = data.GpuBatchLoader(folder_dataset(images, limit), batch_size, device, size=size, shuffle=False,
-                                     num_workers=num_workers, drop_last=False, device_decode=device_decode)
+                                     num_workers=num_workers, drop_last=False, device_decode=device_decode, device_png=device_png)
         for b in loader:
             yield b["image"]
     else:
@@ -442,6 +443,9 @@ def add_eval_args(ap) -> None:
     ap.add_argument("--device_jpeg", action="store_true",
                     help="image folders: decode JPEG files on the GPU after a Huffman pass on host threads (same pixels as PIL; other "
                          "files are decoded by PIL as before)")
+    ap.add_argument("--device_png", action="store_true",
+                    help="image folders: un-filter PNG files on the GPU after inflating them on host threads (same pixels as PIL; palette, "
+                         "16-bit and interlaced files are decoded by PIL as before)")
 
 
 def image_source(opt, ap) -> str | None:

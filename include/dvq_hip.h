@@ -795,6 +795,17 @@ int dvq_jpeg_entropy_decode(const uint8_t* data, size_t n, int16_t* coef, int64_
 size_t dvq_jpeg_desc_bytes(void);
 int dvq_jpeg_batch_decode(const int16_t* coef, const void* desc, int64_t B, uint8_t* planes_tmp, uint8_t* rgb_out, dvq_stream_t stream);
 
+/* ---- device PNG decode (docs/design/29-device-png.md): the host parses the chunks, checks the CRCs and inflates the IDAT stream
+ * (data.decode_png_host, pure Python over zlib); the device reverses the PNG filters (None, Sub, Up, Average, Paeth) of a whole batch of
+ * differently sized images in one launch (csrc/png.hip), pixel for pixel what PIL decodes.
+ * scan: the batch's FILTERED scanlines back to back (device), per image h rows of 1 filter byte (0..4, checked by the host) and w * bpp
+ * bytes; desc: B records of dvq_png_desc_bytes() bytes in device memory (layout: PngDesc in csrc/png.hip, mirrored by data._PngDesc)
+ * with per image scan_off, rgb_off, w, h and bpp (1 grey, 2 grey + alpha, 3 RGB, 4 RGBA; 8 bits per sample).  Output per image: packed
+ * uint8 [h][w][3] at rgb_off of rgb_out, grey written to all three channels, alpha dropped; no byte outside the images' slots is
+ * written.  rgb_out is what dvq_image_batch_transform reads as `src`, and the buffer dvq_jpeg_batch_decode fills. */
+size_t dvq_png_desc_bytes(void);
+int dvq_png_batch_unfilter(const uint8_t* scan, const void* desc, int64_t B, uint8_t* rgb_out, dvq_stream_t stream);
+
 /* ---- reconstruction evaluation (no reference kernel: its codebook-usage tool collects codes on the host,
  * scripts/tools/codebook_usage_dqvae.py:52-69; SSIM as Wang et al. 2004) -----------------------------------------------------------
  * dvq_recon_metrics: x (target), y (reconstruction) NCHW fp32 [B][3][H][W] in [-1, 1]; per image fp64 outputs

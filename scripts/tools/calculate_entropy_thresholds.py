@@ -33,6 +33,9 @@ def get_parser():
                          "decoder, the eval transform Resize + CenterCrop in its kernels) instead of calibrate.load_images (PIL on the "
                          "host).  The folder is read as the loader reads it: <folder>/<class dir>/<image>, or the image files of "
                          "<folder> itself; deeper nesting is not walked")
+    ap.add_argument("--device_png", action="store_true",
+                    help="--images <folder>: like --device_jpeg (the input pipeline instead of calibrate.load_images), with PNG files "
+                         "un-filtered on the GPU (docs/design/29-device-png.md)")
     ap.add_argument("--out", type=str, default=None, help="default: scripts/tools/thresholds/entropy_thresholds_<type>_<split>_patch-<p>.json")
     return ap
 
@@ -43,12 +46,12 @@ def main():
     from dynamicvectorquantization_amd import calibrate, synth
     if opt.synthetic > 0:
         images = synth.half_flat_images(opt.synthetic, opt.image_size, patch=opt.patch_size, seed=2021)
-    elif opt.images and opt.device_jpeg and not opt.images.endswith(".npy"):
+    elif opt.images and (opt.device_jpeg or opt.device_png) and not opt.images.endswith(".npy"):
         import numpy as np
 
         from dynamicvectorquantization_amd import evaluate
         images = np.concatenate([b.cpu().numpy() for b in evaluate.image_batches(64, opt.image_size, "cuda", opt.images, limit=opt.limit,
-                                                                                  device_decode=True)])
+                                                                                  device_decode=opt.device_jpeg, device_png=opt.device_png)])
     elif opt.images:
         images = calibrate.load_images(opt.images, opt.image_size, opt.limit)
     else:

@@ -31,7 +31,7 @@ def main():
     k = codebook_of(model.quantize)[1]
     if opt.codebook_size is not None and opt.codebook_size != k:
         print(f"warning: --codebook_size {opt.codebook_size} differs from the model's {k} codes", file=sys.stderr)
-    s = E.evaluate_reconstruction(model, E.image_batches(opt.batch_size, size, "cuda", source, opt.synthetic, opt.limit, device_decode=opt.device_jpeg), lpips=False)
+    s = E.evaluate_reconstruction(model, E.image_batches(opt.batch_size, size, "cuda", source, opt.synthetic, opt.limit, device_decode=opt.device_jpeg, device_png=opt.device_png), lpips=False)
     print(s["codes_used"])
     print("usage: ", 1 - s["codes_used"] / (opt.codebook_size or k))
 

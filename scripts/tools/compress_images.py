@@ -78,7 +78,7 @@ def gather_tokens(opt, ap, model, size):
             labels = torch.from_numpy(E.read_labels(opt.labels))
         n = 0
         for x in E.image_batches(opt.group * max(1, opt.batch_size // opt.group), size, "cuda", E.image_source(opt, ap), opt.synthetic,
-                                 opt.limit, device_decode=opt.device_jpeg):
+                                 opt.limit, device_decode=opt.device_jpeg, device_png=opt.device_png):
             for g0 in range(0, x.shape[0], opt.group):          # tokenised group by group, as Dualformer.compress does
                 zs.append(model.encode_to_z(x[g0:g0 + opt.group])[1])
             n += int(x.shape[0])

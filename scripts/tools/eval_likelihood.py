@@ -87,7 +87,7 @@ def main():
         loader = T.TokenBatchLoader(ds, opt.batch_size, "cuda", model.permuter, shuffle=False, drop_last=False, view=opt.view)
         batches = token_batches(loader, opt.limit, model.cond_stage_key if model.cond_stage_key != model.first_stage_key else None, ap)
     else:
-        batches = E.image_batches(opt.batch_size, size, "cuda", source, opt.synthetic, opt.limit, device_decode=opt.device_jpeg)
+        batches = E.image_batches(opt.batch_size, size, "cuda", source, opt.synthetic, opt.limit, device_decode=opt.device_jpeg, device_png=opt.device_png)
     if not opt.tokens and model.cond_stage_key != model.first_stage_key:
         if labels is None:
             ap.error(f"{opt.yaml_path} is class-conditional: give --labels")

@@ -47,7 +47,7 @@ def main():
                 Image.fromarray(img, "RGB").save(os.path.join(opt.dump_dir, f"{n_done[0]:06d}.png"))
                 n_done[0] += 1
 
-    s = E.evaluate_reconstruction(model, E.image_batches(opt.batch_size, size, "cuda", source, opt.synthetic, opt.limit, device_decode=opt.device_jpeg),
+    s = E.evaluate_reconstruction(model, E.image_batches(opt.batch_size, size, "cuda", source, opt.synthetic, opt.limit, device_decode=opt.device_jpeg, device_png=opt.device_png),
                                   quantize_u8=opt.quantize_u8, on_batch=on_batch)
     line = json.dumps(s)
     if opt.json:

@@ -87,9 +87,10 @@ def tensor_view_batches(batches, views, lo, hi):
         i += b
 
 
-def decoded_view_batches(ds, views, lo, hi, batch_size, size, device, seed, workers, device_decode=False):
+def decoded_view_batches(ds, views, lo, hi, batch_size, size, device, seed, workers, device_decode=False, device_png=False):
     """decoded images (a folder, the YAML's dataset): data.plan_batch per view with the view's crops / flips, the transforms on the GPU.
-    device_decode: JPEG files are decoded on the GPU too, once per batch (data.decode_batch_gpu); every view reads that buffer"""
+    device_decode: JPEG files are decoded on the GPU too, once per batch (data.decode_batch_gpu); every view reads that buffer.
+    device_png: the same for PNG files (docs/design/29-device-png.md)"""
     from concurrent.futures import ThreadPoolExecutor
 
     import numpy as np
@@ -98,10 +99,10 @@ def decoded_view_batches(ds, views, lo, hi, batch_size, size, device, seed, work
     with ThreadPoolExecutor(max(1, workers)) as pool:
         for i in range(lo, hi, batch_size):
             idx = list(range(i, min(hi, i + batch_size)))
-            ex = list(pool.map((lambda j: ds.example(j, True)) if device_decode else ds.__getitem__, idx))
+            ex = list(pool.map((lambda j: ds.example(j, device_decode, device_png)) if device_decode or device_png else ds.__getitem__, idx))
             dec = None
-            if any("jpeg" in e for e in ex):
-                dec = data.decode_batch_gpu([e["jpeg"] if "jpeg" in e else e["image_u8"] for e in ex], device)
+            if any("jpeg" in e or "png" in e for e in ex):
+                dec = data.decode_batch_gpu([data.example_record(e) for e in ex], device)
             sizes = dec["sizes"] if dec else [(int(e["image_u8"].shape[1]), int(e["image_u8"].shape[0])) for e in ex]
             out = []
             for v, name in enumerate(views):
@@ -169,9 +170,9 @@ def main():
     if ds is None:
         if any(v.startswith("random:") for v in views):
             ap.error("--views random:N draws crops of decoded images: give a folder (--images DIR) or --split")
-        batches = tensor_view_batches(E.image_batches(opt.batch_size, size, dev, source, opt.synthetic, n, device_decode=opt.device_jpeg), views, lo, hi)
+        batches = tensor_view_batches(E.image_batches(opt.batch_size, size, dev, source, opt.synthetic, n, device_decode=opt.device_jpeg, device_png=opt.device_png), views, lo, hi)
     else:
-        batches = decoded_view_batches(ds, views, lo, hi, opt.batch_size, size, dev, opt.seed, opt.num_workers, opt.device_jpeg)
+        batches = decoded_view_batches(ds, views, lo, hi, opt.batch_size, size, dev, opt.seed, opt.num_workers, opt.device_jpeg, opt.device_png)
     writer = T.TokenShardWriter(opt.out, hw1, hw2, codebook_of(model.quantize)[1], views, shard_size=opt.shard_size,
                                 compute_dtype=E.dtype_name(), fingerprint=T.first_stage_fingerprint(model), dataset=described, part=part)
     stats = T.tokenize_batches(model, batches, writer)

@@ -65,6 +65,9 @@ def get_parser():
     p.add_argument("--device_jpeg", action="store_true",
                    help="with --real_data: JPEG files go through the device decoder (Huffman pass on host threads, inverse DCT, upsampling "
                         "and colour in HIP kernels; same pixels as PIL); other files are decoded by PIL as before")
+    p.add_argument("--device_png", action="store_true",
+                   help="with --real_data: PNG files are inflated on host threads and un-filtered in a HIP kernel (same pixels as PIL; "
+                        "palette, 16-bit and interlaced files are decoded by PIL as before)")
     p.add_argument("--token_data", type=str, default="",
                    help="stage 2 only: train from this token set (scripts/tools/tokenize_dataset.py) instead of images -- no first-stage "
                         "forward, no image decoding")
@@ -217,6 +220,10 @@ def run(rank, world, opt, unknown):
             config.data.params["device_decode"] = True      # docs/design/23-device-jpeg.md
             if rank == 0:
                 print("[train.py] device JPEG decode: Huffman pass on host threads, the rest on the GPU")
+        if opt.device_png:
+            config.data.params["device_png"] = True         # docs/design/29-device-png.md
+            if rank == 0:
+                print("[train.py] device PNG decode: inflate on host threads, un-filtering on the GPU")
         dm = cfg.instantiate_from_config(config.data)
         loader = dm.train_dataloader()
         loader.rng = __import__("numpy").random.default_rng(opt.seed + 977 * rank)
@@ -343,6 +350,8 @@ def main():
         raise SystemExit("-b/--base <config.yaml> is required")
     if opt.device_jpeg and not opt.real_data:
         raise SystemExit("--device_jpeg needs --real_data")
+    if opt.device_png and not opt.real_data:
+        raise SystemExit("--device_png needs --real_data")
     import torch
     if "WORLD_SIZE" in os.environ:          # launched by torchrun
         return run(int(os.environ["RANK"]), int(os.environ["WORLD_SIZE"]), opt, unknown)
