@@ -44,6 +44,13 @@ class ScalarRecord(C.Structure):
     _fields_ = [("addr", C.c_uint64 * 64), ("code", C.c_uint8 * 64)]
 
 
+class TokenRule(C.Structure):
+    """dvq_token_rule of include/dvq_hip.h (forbid_idx and finished are device pointers); MAXV: its DVQ_TOKEN_RULE_MAXV"""
+    _fields_ = [("forbid_idx", vp), ("n_forbid", i64), ("forbid_ld", i64), ("forbid_from", i64), ("forbid_codes4", i64 * 4),
+                ("keep_code", i64), ("late_forbid_code", i64), ("pad_code", i64), ("finished", vp)]
+    MAXV = 2048
+
+
 class JpegInfo(C.Structure):
     """dvq_jpeg_info_t of include/dvq_hip.h"""
     _fields_ = [("width", i32), ("height", i32), ("components", i32), ("restart_interval", i32), ("h_samp", i32 * 4), ("v_samp", i32 * 4),
@@ -198,8 +205,8 @@ SIGNATURES = {
     "dvq_set_f32x8": (i32, [vp, f32, f32, f32, f32, f32, f32, f32, f32, vp]),
     "dvq_sample_rows": (i32, [vp, i64, i64, vp, vp]),
     "dvq_add_uniform": (i32, [vp, i64, f32, vp, vp]),
-    "dvq_sample_constrained": (i32, [vp, i32, i64, i64, i64, f32, vp, i64, i64, i64, vp, i64, i64, i64, vp, i32, f32, i32, vp, vp, vp]),
-    "dvq_sample_guided": (i32, [vp, i32, i64, i64, i64, f32, f32, vp, i64, i64, i64, vp, i64, i64, i64, vp, i32, f32, i32, vp, vp, vp]),
+    "dvq_sample_constrained": (i32, [vp, i32, i64, i64, i64, f32, C.POINTER(TokenRule), i32, f32, i32, vp, vp, vp]),
+    "dvq_sample_guided": (i32, [vp, i32, i64, i64, i64, f32, f32, C.POINTER(TokenRule), i32, f32, i32, vp, vp, vp]),
     "dvq_label_dropout": (i32, [vp, i64, f32, i64, C.c_uint64, vp, vp]),
     "dvq_recon_metrics_workspace_bytes": (sz, [i64, i64, i64]),
     "dvq_recon_metrics": (i32, [vp, vp, i64, i64, i64, i32, vp, vp, vp, vp, sz, vp]),
@@ -226,10 +233,10 @@ SIGNATURES = {
     "dvq_scalar_push_state_bytes": (sz, [i64]),
     "dvq_scalar_push": (i32, [C.POINTER(ScalarRecord), i32, i32, i32, vp, vp]),
     "dvq_codebook_health": (i32, [vp, i32, i64, i64, vp, vp, vp, vp]),
-    "dvq_codec_tables": (i32, [vp, i32, i64, i64, i64, vp, i64, i64, i64, vp, i64, i64, i64, vp, vp, vp]),
-    "dvq_codec_record": (i32, [vp, i32, i64, i64, i64, vp, i64, i64, i64, vp, i64, i64, i64, vp, vp, vp, i64, i64, vp, vp, vp]),
+    "dvq_codec_tables": (i32, [vp, i32, i64, i64, i64, C.POINTER(TokenRule), vp, vp]),
+    "dvq_codec_record": (i32, [vp, i32, i64, i64, i64, C.POINTER(TokenRule), vp, vp, i64, i64, vp, vp, vp]),
     "dvq_codec_encode": (i32, [vp, i64, i64, i64, vp, vp, vp, i64, vp, vp, vp]),
-    "dvq_codec_decode_step": (i32, [vp, i32, i64, i64, i64, vp, i64, i64, i64, vp, i64, i64, i64, vp, vp, vp, i64, vp, vp, vp]),
+    "dvq_codec_decode_step": (i32, [vp, i32, i64, i64, i64, C.POINTER(TokenRule), vp, vp, i64, vp, vp, vp]),
 }
 
 

@@ -230,16 +230,14 @@ class _CodecSource:
         self.decode_state = None                                       # the DecodeState the loop ran on (set by _sample_cached)
 
     def _rule(self, logits2d, rule):
-        import torch
+        from . import kernels as K
+        from .stage2 import rule_kwargs
         kind, sampled, done = rule
-        if not (logits2d.is_cuda and logits2d.shape[1] <= 2048 and logits2d.dtype in (torch.float32, torch.bfloat16)):
-            raise CodecError("the codec needs device logits of at most 2048 columns")
+        if not K.token_rule_ok(logits2d):
+            raise CodecError("the codec needs device logits, fp32 or bf16, within the column limit of its kernels (kernels.token_rule_ok)")
         if self.step >= self.max_steps:
             raise CodecError("the token loop ran past its step capacity")
-        kw = dict(self.rules[kind])
-        if kind != "content":
-            kw["forbid_idx"] = sampled
-        return kw, done
+        return rule_kwargs(self.rules[kind], kind, sampled), done
 
     def check(self):
         """the device error words, read once per group"""

@@ -1,18 +1,19 @@
 // Lossless token codec of the DQ-Transformer (gfx950; docs/design/27-token-codec.md).  No counterpart in the reference.
 //
 // A logits row becomes an integer frequency table (codec_table, the ONE function encoder and decoder share):
-//   allowed set A = the columns Dualformer's constraint rule leaves to a live row (the rule of dvq_sample_constrained) whose logit is
-//                   finite; a finished row: {pad_code};  n = |A|
+//   allowed set A = the columns the token rule (dvq_token_rule of include/dvq_hip.h, applied by token_rule.h: the sampler's code) leaves
+//                   unmasked; in a live row the logit must be finite as well;  n = |A|
 //   n == 1:  f = M on that column (nothing is coded);  n == 0: all zero (an error for the callers)
 //   n >= 2:  e_c = expf(x_c - max_A x);  S = sum_A e_c in fp32: lane l adds its columns l, l + 64, ... in ascending order, then the xor
 //            tree of wave_sum;  f_c = 1 + floor(e_c / S * (M - n));  the exact integer remainder M - sum f goes to the lowest-index
-//            arg-max column (it stays >= 1 for n <= 2048: the design note has the argument);  M = 2^16
+//            arg-max column (it stays >= 1 for n <= DVQ_TOKEN_RULE_MAXV: the design note has the argument);  M = 2^16
 // so sum f = M, f >= 1 on A, f = 0 elsewhere; cum_c = exclusive prefix sum in column order.
 // The coder is rANS with a 64-bit state, lower bound L = 2^31, 32-bit words and 16-bit frequencies: a symbol emits at most one word.
 // dvq_codec_record stores (cum, f) of the target per step; dvq_codec_encode walks an image's records backwards and writes its words
 // from the END of its buffer, so dvq_codec_decode_step reads them forwards.
 // One wave per row.  Every output element is written by one lane with a plain store: no atomics.  The error words are one per row.
 #include "dvq_common.h"
+#include "token_rule.h"
 
 #include <math.h>
 
@@ -20,21 +21,15 @@ namespace {
 
 constexpr unsigned CODEC_M = 1u << 16;
 constexpr uint64_t CODEC_L = 1ull << 31;
-constexpr int CODEC_MAXV = 2048;
+constexpr int CODEC_MAXV = DVQ_TOKEN_RULE_MAXV;
 constexpr int CODEC_NI = CODEC_MAXV / 64;        // columns per lane, lane-strided (the softmax) and contiguous (the prefix sums)
 constexpr int CODEC_LDS = CODEC_MAXV + CODEC_MAXV / 32;
 
-struct CodecRule {
+struct CodecParams {
     const void* logits;
     int64_t ldl;
     int V;
-    const int64_t* forbid_idx;
-    int64_t forbid_ld;
-    int n_forbid;
-    int forbid_from;
-    int codes[4];
-    int keep_code, late_forbid_code, pad_code;
-    const float* finished;
+    TokenRule rule;
 };
 
 struct CodecTable {
@@ -48,18 +43,11 @@ struct CodecTable {
 __device__ __forceinline__ int codec_slot(int c) { return c + (c >> 5); }
 
 template <typename T>
-__device__ __forceinline__ CodecTable codec_table(const CodecRule& p, int row, unsigned* __restrict__ sf, unsigned char* __restrict__ flag) {
+__device__ __forceinline__ CodecTable codec_table(const CodecParams& p, int row, unsigned* __restrict__ sf, unsigned char* __restrict__ flag) {
     const int lane = threadIdx.x, V = p.V;
     CodecTable t;
-    t.fin = p.finished != nullptr && p.finished[row] != 0.f;
-    for (int c = lane; c < V; c += 64) flag[c] = 0;
-    __syncthreads();
-    if (!t.fin && p.forbid_idx != nullptr)
-        for (int j = lane; j < p.n_forbid; j += 64) {
-            const int64_t c = p.forbid_idx[(int64_t)row * p.forbid_ld + j];
-            if (c >= 0 && c < V) flag[c] = 1;
-        }
-    __syncthreads();
+    t.fin = token_rule_finished(p.rule, row);
+    token_rule_mark(p.rule, t.fin, row, V, flag, V, lane, 64);
     const T* lg = reinterpret_cast<const T*>(p.logits) + (int64_t)row * p.ldl;
     float x[CODEC_NI];
     float m = -INFINITY;
@@ -73,13 +61,10 @@ __device__ __forceinline__ CodecTable codec_table(const CodecRule& p, int row, u
             bool ok;
             float v = 0.f;
             if (t.fin) {
-                ok = c == p.pad_code;
-            } else {
+                ok = !token_rule_masked(p.rule, true, flag, c);
+            } else {                                                         // A of a live row: not masked AND a finite logit
                 v = ElemIO<T>::load(lg + c);
-                bool masked = flag[c] != 0 || c >= p.forbid_from || c == p.codes[0] || c == p.codes[1] || c == p.codes[2] || c == p.codes[3];
-                if (c == p.keep_code) masked = false;
-                if (c == p.late_forbid_code) masked = true;
-                ok = !masked && v > -INFINITY && v < INFINITY;              // (NaN fails both comparisons)
+                ok = !token_rule_masked(p.rule, false, flag, c) && v > -INFINITY && v < INFINITY;       // (NaN fails both comparisons)
             }
             if (ok) {
                 x[i] = v;
@@ -142,7 +127,7 @@ __device__ __forceinline__ CodecTable codec_table(const CodecRule& p, int row, u
 enum { CODEC_ERR_TARGET = 1, CODEC_ERR_UNDERRUN = 2, CODEC_ERR_EMPTY = 4, CODEC_ERR_SEARCH = 8 };
 
 template <typename T>
-__global__ __launch_bounds__(64) void codec_tables_kernel(CodecRule p, uint32_t* __restrict__ out) {
+__global__ __launch_bounds__(64) void codec_tables_kernel(CodecParams p, uint32_t* __restrict__ out) {
     __shared__ unsigned sf[CODEC_LDS];
     __shared__ unsigned char flag[CODEC_MAXV];
     const int row = blockIdx.x;
@@ -152,7 +137,7 @@ __global__ __launch_bounds__(64) void codec_tables_kernel(CodecRule p, uint32_t*
 
 // a record: cum | f << 16 (f in [1, 65535]); 0 = nothing coded at this step
 template <typename T>
-__global__ __launch_bounds__(64) void codec_record_kernel(CodecRule p, const int64_t* __restrict__ target, uint32_t* __restrict__ records,
+__global__ __launch_bounds__(64) void codec_record_kernel(CodecParams p, const int64_t* __restrict__ target, uint32_t* __restrict__ records,
                                                           int64_t rec_ld, int64_t step, int64_t* __restrict__ token,
                                                           uint32_t* __restrict__ err) {
     __shared__ unsigned sf[CODEC_LDS];
@@ -178,20 +163,20 @@ __global__ __launch_bounds__(64) void codec_record_kernel(CodecRule p, const int
     }
     if (lane == 0) {
         records[(int64_t)row * rec_ld + step] = rec;
-        token[row] = t.fin || !in_range ? (int64_t)p.pad_code : tg;
+        token[row] = t.fin || !in_range ? (int64_t)p.rule.pad_code : tg;
         if (e) err[row] |= e;
     }
 }
 
 // per-row decoder state, int64 [B][4]: {rANS state, cursor, first word of the row's stream in `words`, number of words of the stream}
 template <typename T>
-__global__ __launch_bounds__(64) void codec_decode_kernel(CodecRule p, int64_t* __restrict__ state, const uint32_t* __restrict__ words,
+__global__ __launch_bounds__(64) void codec_decode_kernel(CodecParams p, int64_t* __restrict__ state, const uint32_t* __restrict__ words,
                                                           int64_t total_words, int64_t* __restrict__ token, uint32_t* __restrict__ err) {
     __shared__ unsigned sf[CODEC_LDS];
     __shared__ unsigned char flag[CODEC_MAXV];
     const int row = blockIdx.x, lane = threadIdx.x;
     const CodecTable t = codec_table<T>(p, row, sf, flag);
-    int64_t tok = p.pad_code;
+    int64_t tok = p.rule.pad_code;
     uint32_t e = 0;
     if (!t.fin) {
         if (t.n == 0) {
@@ -303,44 +288,30 @@ __global__ __launch_bounds__(64) void codec_encode_kernel(const uint32_t* __rest
     }
 }
 
-bool codec_rule(CodecRule& p, const void* logits, int dtype, int64_t B, int64_t V, int64_t ldl, const int64_t* forbid_idx, int64_t n_forbid,
-                int64_t forbid_ld, int64_t forbid_from, const int64_t* forbid_codes4, int64_t keep_code, int64_t late_forbid_code,
-                int64_t pad_code, const float* finished) {
-    if (!(logits && B > 0 && B < (int64_t)1 << 30 && V > 0 && V <= CODEC_MAXV && ldl >= V && (dtype == DVQ_F32 || dtype == DVQ_BF16) &&
-          (forbid_idx == nullptr || (n_forbid >= 0 && n_forbid < (int64_t)1 << 30 && forbid_ld >= n_forbid)) && pad_code >= 0 && pad_code < V))
-        return false;
+// the logits arguments and the rule that the three row kernels share; false on a bad one
+bool codec_params(CodecParams& p, const void* logits, int dtype, int64_t B, int64_t V, int64_t ldl, const dvq_token_rule* rule) {
+    if (!(logits && ldl >= V && (dtype == DVQ_F32 || dtype == DVQ_BF16) && token_rule_fill(p.rule, rule, B, V))) return false;
     p.logits = logits; p.ldl = ldl; p.V = (int)V;
-    p.forbid_idx = forbid_idx; p.forbid_ld = forbid_ld; p.n_forbid = forbid_idx ? (int)n_forbid : 0;
-    p.forbid_from = (int)(forbid_from < 0 || forbid_from > V ? V : forbid_from);
-    for (int i = 0; i < 4; ++i) p.codes[i] = forbid_codes4 ? (int)forbid_codes4[i] : -1;
-    p.keep_code = (int)keep_code; p.late_forbid_code = (int)late_forbid_code; p.pad_code = (int)pad_code;
-    p.finished = finished;
     return true;
 }
 
 }  // namespace
 
-int dvq_codec_tables(const void* logits, int dtype, int64_t B, int64_t V, int64_t ldl, const int64_t* forbid_idx, int64_t n_forbid,
-                     int64_t forbid_ld, int64_t forbid_from, const int64_t* forbid_codes4, int64_t keep_code, int64_t late_forbid_code,
-                     int64_t pad_code, const float* finished, uint32_t* table, dvq_stream_t stream) {
-    CodecRule p{};
-    DVQ_REQUIRE(table && codec_rule(p, logits, dtype, B, V, ldl, forbid_idx, n_forbid, forbid_ld, forbid_from, forbid_codes4, keep_code,
-                                    late_forbid_code, pad_code, finished),
-                DVQ_EINVAL, "dvq_codec_tables: bad arguments (V <= 2048)");
+int dvq_codec_tables(const void* logits, int dtype, int64_t B, int64_t V, int64_t ldl, const dvq_token_rule* rule, uint32_t* table,
+                     dvq_stream_t stream) {
+    CodecParams p{};
+    DVQ_REQUIRE(table && codec_params(p, logits, dtype, B, V, ldl, rule), DVQ_EINVAL, "dvq_codec_tables: bad arguments (V <= %d)",
+                CODEC_MAXV);
     DVQ_DISPATCH_DTYPE(dtype, TT, codec_tables_kernel<TT><<<dim3((unsigned)B), dim3(64), 0, (hipStream_t)stream>>>(p, table););
     DVQ_CHECK_LAUNCH("codec_tables");
     return DVQ_OK;
 }
 
-int dvq_codec_record(const void* logits, int dtype, int64_t B, int64_t V, int64_t ldl, const int64_t* forbid_idx, int64_t n_forbid,
-                     int64_t forbid_ld, int64_t forbid_from, const int64_t* forbid_codes4, int64_t keep_code, int64_t late_forbid_code,
-                     int64_t pad_code, const float* finished, const int64_t* target, uint32_t* records, int64_t rec_ld, int64_t step,
-                     int64_t* token, uint32_t* err, dvq_stream_t stream) {
-    CodecRule p{};
-    DVQ_REQUIRE(target && records && token && err && step >= 0 && step < rec_ld &&
-                    codec_rule(p, logits, dtype, B, V, ldl, forbid_idx, n_forbid, forbid_ld, forbid_from, forbid_codes4, keep_code,
-                               late_forbid_code, pad_code, finished),
-                DVQ_EINVAL, "dvq_codec_record: bad arguments (V <= 2048, 0 <= step < rec_ld)");
+int dvq_codec_record(const void* logits, int dtype, int64_t B, int64_t V, int64_t ldl, const dvq_token_rule* rule, const int64_t* target,
+                     uint32_t* records, int64_t rec_ld, int64_t step, int64_t* token, uint32_t* err, dvq_stream_t stream) {
+    CodecParams p{};
+    DVQ_REQUIRE(target && records && token && err && step >= 0 && step < rec_ld && codec_params(p, logits, dtype, B, V, ldl, rule),
+                DVQ_EINVAL, "dvq_codec_record: bad arguments (V <= %d, 0 <= step < rec_ld)", CODEC_MAXV);
     DVQ_DISPATCH_DTYPE(dtype, TT, codec_record_kernel<TT><<<dim3((unsigned)B), dim3(64), 0, (hipStream_t)stream>>>(p, target, records, rec_ld,
                                                                                                                   step, token, err););
     DVQ_CHECK_LAUNCH("codec_record");
@@ -356,15 +327,11 @@ int dvq_codec_encode(const uint32_t* records, int64_t B, int64_t T, int64_t rec_
     return DVQ_OK;
 }
 
-int dvq_codec_decode_step(const void* logits, int dtype, int64_t B, int64_t V, int64_t ldl, const int64_t* forbid_idx, int64_t n_forbid,
-                          int64_t forbid_ld, int64_t forbid_from, const int64_t* forbid_codes4, int64_t keep_code,
-                          int64_t late_forbid_code, int64_t pad_code, const float* finished, int64_t* state, const uint32_t* words,
-                          int64_t total_words, int64_t* token, uint32_t* err, dvq_stream_t stream) {
-    CodecRule p{};
-    DVQ_REQUIRE(state && token && err && total_words >= 0 && (words || total_words == 0) &&
-                    codec_rule(p, logits, dtype, B, V, ldl, forbid_idx, n_forbid, forbid_ld, forbid_from, forbid_codes4, keep_code,
-                               late_forbid_code, pad_code, finished),
-                DVQ_EINVAL, "dvq_codec_decode_step: bad arguments (V <= 2048)");
+int dvq_codec_decode_step(const void* logits, int dtype, int64_t B, int64_t V, int64_t ldl, const dvq_token_rule* rule, int64_t* state,
+                          const uint32_t* words, int64_t total_words, int64_t* token, uint32_t* err, dvq_stream_t stream) {
+    CodecParams p{};
+    DVQ_REQUIRE(state && token && err && total_words >= 0 && (words || total_words == 0) && codec_params(p, logits, dtype, B, V, ldl, rule),
+                DVQ_EINVAL, "dvq_codec_decode_step: bad arguments (V <= %d)", CODEC_MAXV);
     DVQ_DISPATCH_DTYPE(dtype, TT, codec_decode_kernel<TT><<<dim3((unsigned)B), dim3(64), 0, (hipStream_t)stream>>>(p, state, words, total_words,
                                                                                                                   token, err););
     DVQ_CHECK_LAUNCH("codec_decode_step");

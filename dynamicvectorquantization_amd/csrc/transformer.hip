@@ -7,6 +7,7 @@
 //   dropout (counter-based hash RNG)        nn.Dropout                      stackgpt.py:31-32,82,146
 // The GEMMs (q/k/v/proj/MLP/heads, QK^T, PV and their backward) run on the kernels of igemm_nt.hip / igemm_tn.hip.
 #include "dvq_common.h"
+#include "token_rule.h"
 #include <type_traits>
 
 namespace {
@@ -941,16 +942,14 @@ extern "C" int dvq_rows_dev(void* x, void* hidden, int dtype, int64_t B, int64_t
 //   dqtransformer_uncond_entropy.py:522-561 (avoid_repeat_or_enforce_pad_for_{coarse,fine}_position, avoid_special_or_enforce_pad_
 //   for_content), models/stage2/utils.py:22-40 (top_k_logits, top_p_logits), :328 / :350 (softmax + multinomial, or top-1)
 // as one launch instead of ~12 ATen kernels (scatter / masked fills / topk / sort / cumsum / softmax / multinomial) per draw.
-// One workgroup per row.  The row (V <= 2048 logits / temperature, constraint mask applied) is sorted in LDS by (value descending,
+// One workgroup per row.  The row (V <= DVQ_TOKEN_RULE_MAXV logits / temperature, the token rule applied) is sorted in LDS by (value descending,
 // index ascending) with a bitonic network; in that order
 //   top-k    keeps every value >= the k-th one (ties kept, like `out[out < v[..., [-1]]] = -inf`),
 //   softmax  is exp(v - v_max) / sum over the kept entries,
 //   top-p    removes entry i (i >= 1) when the inclusive cumulative probability of entries 0 .. i-1 is already >= p, renormalises,
 //   the draw is the inverse CDF at u * (kept mass), u uniform from a counter-based generator whose state lives in device memory
 //            (capturable in a hipGraph; advanced by a one-thread kernel after the draw), or entry 0 when sample == 0.
-// Constraint rule of a LIVE row (finished[row] == 0): column c is masked when c >= forbid_from, c is one of forbid_codes[4], or c is
-// listed in forbid_idx[row][0 .. n_forbid); then keep_code gets its logit back; then late_forbid_code is masked.  A FINISHED row keeps
-// pad_code only.
+// The constraint rule is dvq_token_rule (include/dvq_hip.h), applied by token_rule.h -- the code the token codec masks with.
 // =================================================================================================
 namespace {
 
@@ -959,13 +958,7 @@ struct SampleParams {
     int64_t ldl;
     int V, N;                       // columns; sort size (power of two >= V)
     float inv_temperature;
-    const int64_t* forbid_idx;
-    int64_t forbid_ld;
-    int n_forbid;
-    int forbid_from;
-    int codes[4];
-    int keep_code, late_forbid_code, pad_code;
-    const float* finished;
+    TokenRule rule;
     int top_k;
     float top_p;
     int sample;
@@ -993,15 +986,8 @@ __global__ __launch_bounds__(1024) void sample_constrained_kernel(SampleParams p
     // N / 2 threads (256 .. 1024): one compare-exchange per thread and sort step
     const int tid = threadIdx.x, row = blockIdx.x, lane = tid & 63, wave = tid >> 6, nth = blockDim.x, nw = nth >> 6;
     const int V = p.V, N = p.N;
-    const bool fin = p.finished != nullptr && p.finished[row] != 0.f;
-    for (int c = tid; c < N; c += nth) flag[c] = 0;
-    __syncthreads();
-    if (!fin && p.forbid_idx != nullptr)
-        for (int j = tid; j < p.n_forbid; j += nth) {
-            const int64_t c = p.forbid_idx[(int64_t)row * p.forbid_ld + j];
-            if (c >= 0 && c < V) flag[c] = 1;
-        }
-    __syncthreads();
+    const bool fin = token_rule_finished(p.rule, row);
+    token_rule_mark(p.rule, fin, row, V, flag, N, tid, nth);
     const T* lg = reinterpret_cast<const T*>(p.logits) + (int64_t)row * p.ldl;
     for (int c = tid; c < N; c += nth) {
         float v = -INFINITY;
@@ -1013,15 +999,7 @@ __global__ __launch_bounds__(1024) void sample_constrained_kernel(SampleParams p
             } else {
                 x = ElemIO<T>::load(lg + c) * p.inv_temperature;
             }
-            bool masked;
-            if (fin) {
-                masked = c != p.pad_code;
-            } else {
-                masked = flag[c] != 0 || c >= p.forbid_from || c == p.codes[0] || c == p.codes[1] || c == p.codes[2] || c == p.codes[3];
-                if (c == p.keep_code) masked = false;
-                if (c == p.late_forbid_code) masked = true;
-            }
-            v = masked ? -INFINITY : x;
+            v = token_rule_masked(p.rule, fin, flag, c) ? -INFINITY : x;
         }
         sv[c] = v;
         si[c] = c;
@@ -1155,24 +1133,23 @@ __global__ void sample_bump_kernel(uint64_t* state) {
     if (threadIdx.x == 0) state[1] += 1;
 }
 
-// the shared host side of dvq_sample_constrained / dvq_sample_guided: B rows (GUIDED: B pairs over 2 B logits rows)
+// the shared host side of dvq_sample_constrained / dvq_sample_guided: B rows (GUIDED: B pairs over 2 B logits rows).  The rule's
+// own conditions (and the ranges of B and V) are token_rule_fill's; the rest are checked here, under the entry point's name
 template <bool GUIDED>
 int sample_constrained_launch(const void* logits, int dtype, int64_t B, int64_t V, int64_t ldl, float temperature, float guidance,
-                              const int64_t* forbid_idx, int64_t n_forbid, int64_t forbid_ld, int64_t forbid_from,
-                              const int64_t* forbid_codes4, int64_t keep_code, int64_t late_forbid_code, int64_t pad_code,
-                              const float* finished, int top_k, float top_p, int sample, uint64_t* state, int64_t* out,
+                              const dvq_token_rule* rule, int top_k, float top_p, int sample, uint64_t* state, int64_t* out,
                               dvq_stream_t stream) {
     SampleParams p{};
+    DVQ_REQUIRE(logits && out && ldl >= V && temperature > 0.f && (!sample || state != nullptr) && top_k >= 0 && std::isfinite(guidance) &&
+                    token_rule_fill(p.rule, rule, B, V),
+                DVQ_EINVAL, "%s: bad arguments (V <= %d%s)", GUIDED ? "dvq_sample_guided" : "dvq_sample_constrained", DVQ_TOKEN_RULE_MAXV,
+                GUIDED ? ", finite guidance" : "");
     p.logits = logits; p.ldl = ldl; p.V = (int)V;
     int n = 256;
     while (n < V) n <<= 1;
     p.N = n;
     p.inv_temperature = 1.f / temperature;
-    p.forbid_idx = forbid_idx; p.forbid_ld = forbid_ld; p.n_forbid = forbid_idx ? (int)n_forbid : 0;
-    p.forbid_from = (int)(forbid_from < 0 || forbid_from > V ? V : forbid_from);
-    for (int i = 0; i < 4; ++i) p.codes[i] = forbid_codes4 ? (int)forbid_codes4[i] : -1;
-    p.keep_code = (int)keep_code; p.late_forbid_code = (int)late_forbid_code; p.pad_code = (int)pad_code;
-    p.finished = finished; p.top_k = top_k; p.top_p = top_p; p.sample = sample; p.guidance = guidance; p.state = state; p.out = out;
+    p.top_k = top_k; p.top_p = top_p; p.sample = sample; p.guidance = guidance; p.state = state; p.out = out;
     const int lds = n * (4 + 4 + 4 + 1);
     const unsigned nthreads = (unsigned)(n / 2 < 256 ? 256 : n / 2 > 1024 ? 1024 : n / 2);
     DVQ_DISPATCH_DTYPE(dtype, TT, sample_constrained_kernel<TT, GUIDED><<<dim3((unsigned)B), dim3(nthreads), lds, (hipStream_t)stream>>>(p););
@@ -1187,28 +1164,13 @@ int sample_constrained_launch(const void* logits, int dtype, int64_t B, int64_t 
 }  // namespace
 
 extern "C" int dvq_sample_constrained(const void* logits, int dtype, int64_t B, int64_t V, int64_t ldl, float temperature,
-                                      const int64_t* forbid_idx, int64_t n_forbid, int64_t forbid_ld, int64_t forbid_from,
-                                      const int64_t* forbid_codes4, int64_t keep_code, int64_t late_forbid_code, int64_t pad_code,
-                                      const float* finished, int top_k, float top_p, int sample, uint64_t* state, int64_t* out,
+                                      const dvq_token_rule* rule, int top_k, float top_p, int sample, uint64_t* state, int64_t* out,
                                       dvq_stream_t stream) {
-    DVQ_REQUIRE(logits && out && B > 0 && V > 0 && V <= 2048 && ldl >= V && temperature > 0.f && (!sample || state != nullptr) &&
-                    (forbid_idx == nullptr || (n_forbid >= 0 && forbid_ld >= n_forbid)) && pad_code >= 0 && pad_code < V && top_k >= 0,
-                DVQ_EINVAL, "dvq_sample_constrained: bad arguments (V <= 2048)");
-    return sample_constrained_launch<false>(logits, dtype, B, V, ldl, temperature, 0.f, forbid_idx, n_forbid, forbid_ld, forbid_from,
-                                            forbid_codes4, keep_code, late_forbid_code, pad_code, finished, top_k, top_p, sample, state,
-                                            out, stream);
+    return sample_constrained_launch<false>(logits, dtype, B, V, ldl, temperature, 0.f, rule, top_k, top_p, sample, state, out, stream);
 }
 
 extern "C" int dvq_sample_guided(const void* logits, int dtype, int64_t B, int64_t V, int64_t ldl, float guidance, float temperature,
-                                 const int64_t* forbid_idx, int64_t n_forbid, int64_t forbid_ld, int64_t forbid_from,
-                                 const int64_t* forbid_codes4, int64_t keep_code, int64_t late_forbid_code, int64_t pad_code,
-                                 const float* finished, int top_k, float top_p, int sample, uint64_t* state, int64_t* out,
+                                 const dvq_token_rule* rule, int top_k, float top_p, int sample, uint64_t* state, int64_t* out,
                                  dvq_stream_t stream) {
-    DVQ_REQUIRE(logits && out && B > 0 && V > 0 && V <= 2048 && ldl >= V && temperature > 0.f && (!sample || state != nullptr) &&
-                    (forbid_idx == nullptr || (n_forbid >= 0 && forbid_ld >= n_forbid)) && pad_code >= 0 && pad_code < V && top_k >= 0 &&
-                    std::isfinite(guidance),
-                DVQ_EINVAL, "dvq_sample_guided: bad arguments (V <= 2048, finite guidance)");
-    return sample_constrained_launch<true>(logits, dtype, B, V, ldl, temperature, guidance, forbid_idx, n_forbid, forbid_ld, forbid_from,
-                                           forbid_codes4, keep_code, late_forbid_code, pad_code, finished, top_k, top_p, sample, state,
-                                           out, stream);
+    return sample_constrained_launch<true>(logits, dtype, B, V, ldl, temperature, guidance, rule, top_k, top_p, sample, state, out, stream);
 }

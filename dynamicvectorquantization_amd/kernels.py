@@ -1412,48 +1412,57 @@ def attn_decode(q, kcache, vcache, n_head, t, scale):
     return out
 
 
-def _sample_args(logits2d, forbid_idx, forbid_from, forbid_codes, finished):
-    """marshalled constraint arguments of dvq_sample_constrained / dvq_sample_guided"""
-    v = logits2d.shape[1]
-    codes = (C.c_int64 * 4)(*([int(c) for c in forbid_codes] + [-1] * (4 - len(forbid_codes))))
-    fi = None
-    n_forbid = ld = 0
-    if forbid_idx is not None and forbid_idx.shape[1] > 0:
-        fi = forbid_idx if forbid_idx.is_contiguous() else forbid_idx.contiguous()
-        n_forbid, ld = fi.shape[1], fi.stride(0)
-    fin = None
-    if finished is not None:
-        fin = finished.reshape(-1).to(torch.float32).contiguous()
+def token_rule_ok(logits2d) -> bool:
+    """can the kernels that take a token rule (sample_*, codec_*) run on these logits?  [B, V] on the device, fp32 or bf16, unit column
+    stride (a column slice of a padded matrix is fine), at most DVQ_TOKEN_RULE_MAXV columns"""
+    return (logits2d.is_cuda and logits2d.dtype in _DT and logits2d.dim() == 2 and logits2d.stride(1) == 1
+            and logits2d.shape[1] <= _lib.TokenRule.MAXV)
+
+
+def _token_rule(logits2d, pad_code, forbid_idx, forbid_from, forbid_codes, keep_code, late_forbid_code, finished):
+    """dvq_token_rule of include/dvq_hip.h (the rule is described there) for the B rows of logits2d -> (the filled struct, the tensors
+    it points at: alive until the call is issued).  forbid_idx int64 [>= B, L]; finished [>= B]; forbid_from None: no bound"""
+    b = logits2d.shape[0]
     assert logits2d.is_cuda and logits2d.stride(1) == 1, "row-major logits (a column slice of a padded matrix is fine)"
-    return fi, n_forbid, ld, v if forbid_from is None else int(forbid_from), codes, fin
+    fi = forbid_idx.contiguous() if forbid_idx is not None and forbid_idx.shape[1] > 0 else None
+    fin = finished.reshape(-1).to(torch.float32).contiguous() if finished is not None else None
+    assert (fi is None or (fi.dtype == torch.int64 and fi.shape[0] >= b)) and (fin is None or fin.numel() >= b)
+    n_forbid, ld = (fi.shape[1], fi.stride(0)) if fi is not None else (0, 0)
+    codes = (C.c_int64 * 4)(*([int(c) for c in forbid_codes] + [-1] * (4 - len(forbid_codes))))
+    return _lib.TokenRule(_p(fi), n_forbid, ld, -1 if forbid_from is None else int(forbid_from), codes, int(keep_code),
+                          int(late_forbid_code), int(pad_code), _p(fin)), (fi, fin)
+
+
+def _logits_args(logits2d):
+    """(logits, dtype, B, V, ldl): the leading arguments of the entry points that take one row of logits2d per token"""
+    b, v = logits2d.shape
+    return _praw(logits2d), dt(logits2d), b, v, logits2d.stride(0)
 
 
 def sample_constrained(logits2d, temperature, pad_code, state, forbid_idx=None, forbid_from=None, forbid_codes=(), keep_code=-1,
                        late_forbid_code=-1, finished=None, top_k=None, top_p=None, sample=True):
-    """one token per row of logits2d [B, V] (V <= 2048) under Dualformer's constraint rules, top-k / top-p, multinomial or top-1:
-    ONE launch (csrc/transformer.hip: dvq_sample_constrained).  forbid_idx int64 [B, L] lists columns to mask per row; finished fp32
-    [B] (non-zero: the row only keeps pad_code); state = int64 [2] device generator state (key, counter).  -> int64 [B, 1]"""
-    b, v = logits2d.shape
-    out = torch.empty(b, 1, dtype=torch.int64, device=logits2d.device)
-    fi, n_forbid, ld, ff, codes, fin = _sample_args(logits2d, forbid_idx, forbid_from, forbid_codes, finished)
-    check(lib().dvq_sample_constrained(_praw(logits2d), dt(logits2d), b, v, logits2d.stride(0), float(temperature), _p(fi), n_forbid, ld,
-                                       ff, codes, int(keep_code), int(late_forbid_code), int(pad_code), _p(fin), int(top_k or 0),
-                                       float(top_p or 0.0), int(bool(sample)), _p(state), _p(out), _s()), "dvq_sample_constrained")
+    """one token per row of logits2d [B, V] (token_rule_ok) under Dualformer's constraint rule (_token_rule), top-k / top-p, multinomial
+    or top-1: ONE launch (csrc/transformer.hip: dvq_sample_constrained).  state = int64 [2] device generator state (key, counter).
+    -> int64 [B, 1]"""
+    out = torch.empty(logits2d.shape[0], 1, dtype=torch.int64, device=logits2d.device)
+    rule, keep = _token_rule(logits2d, pad_code, forbid_idx, forbid_from, forbid_codes, keep_code, late_forbid_code, finished)
+    check(lib().dvq_sample_constrained(*_logits_args(logits2d), float(temperature), C.byref(rule), int(top_k or 0), float(top_p or 0.0),
+                                       int(bool(sample)), _p(state), _p(out), _s()), "dvq_sample_constrained")
     return out
 
 
 def sample_guided(logits2d, guidance, temperature, pad_code, state, forbid_idx=None, forbid_from=None, forbid_codes=(), keep_code=-1,
                   late_forbid_code=-1, finished=None, top_k=None, top_p=None, sample=True):
     """classifier-free-guided sample_constrained (csrc/transformer.hip: dvq_sample_guided): logits2d [2B, V], rows [0, B) conditional,
-    rows [B, 2B) unconditional; the pipeline runs on fmaf(1 - guidance, u, guidance * c) per pair.  forbid_idx / finished may be the
+    rows [B, 2B) unconditional; the pipeline runs on fmaf(1 - guidance, u, guidance * c) per pair.  forbid_idx / finished are the
     2B-row tensors (rows [0, B) are read).  -> int64 [2B, 1], the pair's token in row i and row i + B"""
     b2, v = logits2d.shape
     assert b2 % 2 == 0, "guided sampling takes [conditional ; unconditional] rows"
     out = torch.empty(b2, 1, dtype=torch.int64, device=logits2d.device)
-    fi, n_forbid, ld, ff, codes, fin = _sample_args(logits2d, forbid_idx, forbid_from, forbid_codes, finished)
+    rule, keep = _token_rule(logits2d, pad_code, forbid_idx, forbid_from, forbid_codes, keep_code, late_forbid_code, finished)
     check(lib().dvq_sample_guided(_praw(logits2d), dt(logits2d), b2 // 2, v, logits2d.stride(0), float(guidance), float(temperature),
-                                  _p(fi), n_forbid, ld, ff, codes, int(keep_code), int(late_forbid_code), int(pad_code), _p(fin),
-                                  int(top_k or 0), float(top_p or 0.0), int(bool(sample)), _p(state), _p(out), _s()), "dvq_sample_guided")
+                                  C.byref(rule), int(top_k or 0), float(top_p or 0.0), int(bool(sample)), _p(state), _p(out), _s()),
+          "dvq_sample_guided")
     return out
 
 
@@ -1465,23 +1474,13 @@ CODEC_ERRORS = {1: "a token the model's rule forbids (frequency 0)", 2: "a read 
                 4: "a live row with no allowed symbol", 8: "no symbol under the coder's state"}
 
 
-def _codec_rule(logits2d, pad_code, forbid_idx, forbid_from, forbid_codes, keep_code, late_forbid_code, finished):
-    """the leading arguments (logits + constraint rule) that the four dvq_codec_* row kernels share, and what they keep alive"""
-    b, v = logits2d.shape
-    fi, n_forbid, ld, ff, codes, fin = _sample_args(logits2d, forbid_idx, forbid_from, forbid_codes, finished)
-    assert (fi is None or (fi.dtype == torch.int64 and fi.shape[0] >= b)) and (fin is None or fin.numel() >= b)
-    return (_praw(logits2d), dt(logits2d), b, v, logits2d.stride(0), _p(fi), n_forbid, ld, ff, codes, int(keep_code),
-            int(late_forbid_code), int(pad_code), _p(fin)), (fi, fin, codes)
-
-
 def codec_tables(logits2d, pad_code, forbid_idx=None, forbid_from=None, forbid_codes=(), keep_code=-1, late_forbid_code=-1,
                  finished=None):
-    """the codec's integer frequency table of every row of logits2d [B, V] (V <= 2048) under a constraint rule (the rule arguments of
-    sample_constrained): int32 [B, V], sum 65536 per row (dvq_codec_tables; for tests and inspection)"""
-    b, v = logits2d.shape
-    out = torch.empty(b, v, dtype=torch.int32, device=logits2d.device)
-    args, keep = _codec_rule(logits2d, pad_code, forbid_idx, forbid_from, forbid_codes, keep_code, late_forbid_code, finished)
-    check(lib().dvq_codec_tables(*args, _p(out), _s()), "dvq_codec_tables")
+    """the codec's integer frequency table of every row of logits2d [B, V] (token_rule_ok) under a constraint rule (the rule arguments
+    of sample_constrained): int32 [B, V], sum 65536 per row (dvq_codec_tables; for tests and inspection)"""
+    out = torch.empty(logits2d.shape, dtype=torch.int32, device=logits2d.device)
+    rule, keep = _token_rule(logits2d, pad_code, forbid_idx, forbid_from, forbid_codes, keep_code, late_forbid_code, finished)
+    check(lib().dvq_codec_tables(*_logits_args(logits2d), C.byref(rule), _p(out), _s()), "dvq_codec_tables")
     return out
 
 
@@ -1495,8 +1494,9 @@ def codec_record(logits2d, target, records, step, err, pad_code, forbid_idx=None
     assert tg.dtype == torch.int64 and tg.numel() == b and records.dtype == torch.int32 and records.shape[0] == b
     assert records.stride(1) == 1
     assert err.dtype == torch.int32 and err.numel() == b and err.is_contiguous() and 0 <= step < records.shape[1]
-    args, keep = _codec_rule(logits2d, pad_code, forbid_idx, forbid_from, forbid_codes, keep_code, late_forbid_code, finished)
-    check(lib().dvq_codec_record(*args, _p(tg), _p(records), records.stride(0), int(step), _p(out), _p(err), _s()), "dvq_codec_record")
+    rule, keep = _token_rule(logits2d, pad_code, forbid_idx, forbid_from, forbid_codes, keep_code, late_forbid_code, finished)
+    check(lib().dvq_codec_record(*_logits_args(logits2d), C.byref(rule), _p(tg), _p(records), records.stride(0), int(step), _p(out),
+                                 _p(err), _s()), "dvq_codec_record")
     return out
 
 
@@ -1540,8 +1540,9 @@ def codec_decode_step(logits2d, state, words, err, pad_code, forbid_idx=None, fo
     out = torch.empty(b, 1, dtype=torch.int64, device=logits2d.device)
     assert state.dtype == torch.int64 and state.shape == (b, 4) and state.is_contiguous()
     assert words.dtype == torch.int32 and words.is_contiguous() and err.dtype == torch.int32 and err.numel() == b and err.is_contiguous()
-    args, keep = _codec_rule(logits2d, pad_code, forbid_idx, forbid_from, forbid_codes, keep_code, late_forbid_code, finished)
-    check(lib().dvq_codec_decode_step(*args, _p(state), _p(words), words.numel(), _p(out), _p(err), _s()), "dvq_codec_decode_step")
+    rule, keep = _token_rule(logits2d, pad_code, forbid_idx, forbid_from, forbid_codes, keep_code, late_forbid_code, finished)
+    check(lib().dvq_codec_decode_step(*_logits_args(logits2d), C.byref(rule), _p(state), _p(words), words.numel(), _p(out), _p(err), _s()),
+          "dvq_codec_decode_step")
     return out
 
 

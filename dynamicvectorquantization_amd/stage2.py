@@ -443,6 +443,12 @@ def _mask_rows(logits, finished, forbid, keep_code, pad_code):
     return torch.where(finished.bool().view(-1, 1), only_pad, out)
 
 
+def rule_kwargs(model_rule, kind, sampled):
+    """the rule keywords of kernels.sample_* / codec_* at one token step: the model's rule for `kind` (`_fused_rule`, or the codec's
+    codec.codec_rule); the two position kinds also forbid the positions drawn so far"""
+    return dict(model_rule) if kind == "content" else dict(model_rule, forbid_idx=sampled)
+
+
 class _SampleSource:
     """where `_sample_cached` gets its next token from -- here: the constrained draw (`_draw_rule`).  A source has token(logits2d,
     rule) -> int64 [B, 1] with rule = (kind, sampled positions or None, done flags), check() called once after the loop,
@@ -519,11 +525,12 @@ class _SamplerMixin:
     def _draw_rule(self, logits2d, temperature, sample, k, p, rule, cfg=None):
         """one token per row under constraint `rule` = (kind, sampled positions or None, done flags): ONE fused launch
         (kernels.sample_constrained: mask rules + top-k / top-p + softmax + multinomial / top-1) when the logits are on the device;
-        CPU logits, other dtypes or a vocabulary beyond the kernel's 2048 columns keep the op-by-op path the golden tests pin.
+        logits the kernel does not take (kernels.token_rule_ok: CPU, other dtypes, too many columns) keep the op-by-op path the golden
+        tests pin.
         cfg = classifier-free-guidance scale or None: the rows are [conditional ; unconditional] pairs, each pair draws from the
         guided logits (kernels.sample_guided) and its token is returned in both of its rows"""
         kind, sampled, done = rule
-        if logits2d.is_cuda and logits2d.shape[1] <= 2048 and logits2d.dtype in (torch.float32, torch.bfloat16):
+        if K.token_rule_ok(logits2d):
             # {seed, counter} of the kernel's counter-based generator, keyed by torch's seed: a later torch.manual_seed() /
             # seed_everything() restarts the stream (same seed -> same samples, like the op-by-op path's torch generator)
             seed = torch.initial_seed() & 0x7FFFFFFFFFFFFFFF
@@ -541,9 +548,7 @@ class _SamplerMixin:
                     st = torch.tensor([seed, 0], dtype=torch.int64, device=logits2d.device)
                     self.__dict__["_sampler_state"] = st
                     self.__dict__["_sampler_seed"] = seed
-            kw = self._fused_rule(kind)
-            if kind != "content":
-                kw["forbid_idx"] = sampled
+            kw = rule_kwargs(self._fused_rule(kind), kind, sampled)
             if cfg is not None:
                 return K.sample_guided(logits2d, cfg, temperature, state=st, finished=done, top_k=k, top_p=p, sample=sample, **kw)
             return K.sample_constrained(logits2d, temperature, state=st, finished=done, top_k=k, top_p=p, sample=sample, **kw)

@@ -46,7 +46,9 @@ const char* dvq_last_error(void);
  * written in csrc ("conv3x3_halo_kernel", "conv_nt_pipe_kernel", ...; no template arguments, no fold / reduce / transpose helpers), noted
  * at the dispatch branch that launches it.  "" when nothing was noted (those entry points clear it first).  For timing labels. */
 const char* dvq_last_kernel(void);
-int dvq_version(void);     /* 122: dvq_attn_causal_fwd / _bwd take the row pitch ldqkv (dvq_attn_causal_fwd_ld / _bwd_ld are gone); dvq_attn_causal_scratch_bytes
+int dvq_version(void);     /* 123: struct dvq_token_rule, DVQ_TOKEN_RULE_MAXV: dvq_sample_constrained, dvq_sample_guided, dvq_codec_tables, dvq_codec_record and
+                            * dvq_codec_decode_step take the constraint rule as one block instead of nine loose arguments;
+                            * 122: dvq_attn_causal_fwd / _bwd take the row pitch ldqkv (dvq_attn_causal_fwd_ld / _bwd_ld are gone); dvq_attn_causal_scratch_bytes
                             * is what the kernels that run need (0 forward at head sizes 128 / 256: NULL scratch); dvq_attn_full_scratch_bytes is gone;
                             * 121: dvq_halo_trace_read is gone (the timing experiments and the persistent 3x3 kernel left the sources: one library);
                             * 120: dvq_conv3x3_subpixel_ok, dvq_conv_desc.upsample == 2, bit 9 of the weight packs' dtype (nearest x2 + 3x3 convolutions
@@ -516,30 +518,38 @@ int dvq_embed_scatter_add(const int64_t* idx, int64_t idx_bstride, const void* d
  * when dlogits != NULL, dlogits = (softmax - onehot) * gscale_dev[0] (0 on ignored rows and on columns >= V; row stride ldl) */
 int dvq_cross_entropy(const void* logits, int dtype, int64_t rows, int64_t V, int64_t ldl, const int64_t* target, int64_t ignore_index,
                       float* loss_sum, float* count, const float* gscale_dev, void* dlogits, dvq_stream_t stream);
+/* The token rule: which columns of a logits row [V] the sampler may draw and the token codec gives a frequency to.  ONE definition
+ * for both (csrc/token_rule.h): the codec decodes only what it coded under the rule the sampler draws under.
+ *   A LIVE row (finished == NULL or finished[row] == 0) masks column c when c is listed in forbid_idx[row][0 .. n_forbid) (entries
+ *   outside [0, V) are ignored), or c >= forbid_from, or c is one of forbid_codes4[0 .. 3]; then keep_code gets its logit back; then
+ *   late_forbid_code is masked -- in this order, so late_forbid_code wins over keep_code.
+ *   A FINISHED row (finished[row] != 0) keeps pad_code only.
+ * -1 is an unused code (forbid_codes4[i], keep_code, late_forbid_code); forbid_from < 0 or > V means V: no bound.  pad_code lies in
+ * [0, V).  forbid_idx (int64 [rows][forbid_ld], row pitch forbid_ld >= n_forbid; NULL: no list) and finished (fp32 [rows]; NULL: every
+ * row is live) are DEVICE pointers; everything else is read on the host during the call and copied by value into the kernel arguments,
+ * so a call recorded by stream capture does not depend on the struct afterwards.  B and n_forbid stay below 2^30. */
+#define DVQ_TOKEN_RULE_MAXV 2048 /* the most columns (V) the entry points that take a dvq_token_rule accept */
+typedef struct dvq_token_rule {
+    const int64_t* forbid_idx;
+    int64_t n_forbid, forbid_ld, forbid_from, forbid_codes4[4], keep_code, late_forbid_code, pad_code;
+    const float* finished;
+} dvq_token_rule;
 /* Fused constrained sampling of one token per row (Dualformer's sampler tail: dqtransformer_uncond_entropy.py:522-561 mask rules,
- * models/stage2/utils.py:22-40 top-k / top-p, :328,350 softmax + multinomial / top-1) in ONE launch.  logits [B][ldl] (V <= 2048
- * columns used), divided by `temperature`.  A LIVE row (finished == NULL or finished[row] == 0) masks column c when c >= forbid_from
- * (pass V for none), c is one of forbid_codes4[0..3] (host array, -1 = unused), or c is listed in forbid_idx[row][0 .. n_forbid)
- * (device, row stride forbid_ld; may be NULL); then keep_code (-1: none) gets its logit back; then late_forbid_code (-1: none) is
- * masked.  A FINISHED row keeps pad_code only.  top_k == 0 / top_p outside (0, 1): filter off.  sample != 0: a draw from the filtered
- * distribution with the device-resident generator `state` (uint64 [2]: key, counter; the counter is advanced by the call --
- * capturable in a hipGraph); sample == 0: the most probable column (lowest index on ties).  out int64 [B]. */
-int dvq_sample_constrained(const void* logits, int dtype, int64_t B, int64_t V, int64_t ldl, float temperature,
-                           const int64_t* forbid_idx, int64_t n_forbid, int64_t forbid_ld, int64_t forbid_from,
-                           const int64_t* forbid_codes4, int64_t keep_code, int64_t late_forbid_code, int64_t pad_code,
-                           const float* finished, int top_k, float top_p, int sample, uint64_t* state, int64_t* out,
-                           dvq_stream_t stream);
+ * models/stage2/utils.py:22-40 top-k / top-p, :328,350 softmax + multinomial / top-1) in ONE launch.  logits [B][ldl] (V <=
+ * DVQ_TOKEN_RULE_MAXV columns used), divided by `temperature`, masked by `rule` (dvq_token_rule above).  top_k == 0 / top_p outside
+ * (0, 1): filter off.  sample != 0: a draw from the filtered distribution with the device-resident generator `state` (uint64 [2]: key,
+ * counter; the counter is advanced by the call -- capturable in a hipGraph); sample == 0: the most probable column (lowest index on
+ * ties).  out int64 [B]. */
+int dvq_sample_constrained(const void* logits, int dtype, int64_t B, int64_t V, int64_t ldl, float temperature, const dvq_token_rule* rule,
+                           int top_k, float top_p, int sample, uint64_t* state, int64_t* out, dvq_stream_t stream);
 /* Classifier-free-guided form of dvq_sample_constrained: B is the number of PAIRS.  logits rows [0, B) are the conditional logits c,
- * rows [B, 2B) the unconditional (null-class) logits u (row pitch ldl, V <= 2048).  Per pair and column, in fp32,
+ * rows [B, 2B) the unconditional (null-class) logits u (row pitch ldl).  Per pair and column, in fp32,
  * g = fmaf(1 - guidance, u, guidance * c) (guidance = 1: exactly c; 0: exactly u); then dvq_sample_constrained's pipeline on g
- * (x 1/temperature, mask rules, top-k, softmax, top-p, draw).  forbid_idx / finished are read for rows [0, B) only (pass the 2B-row
- * arrays); the uniform of pair i is that of row i; the counter advances once per call.  The token is written to out[i] AND out[i + B]
- * (out int64 [2B]): both halves of the batch carry the same history.  guidance must be finite. */
+ * (x 1/temperature, the rule, top-k, softmax, top-p, draw).  rule->forbid_idx / rule->finished are read for rows [0, B) only (pass the
+ * 2B-row arrays); the uniform of pair i is that of row i; the counter advances once per call.  The token is written to out[i] AND
+ * out[i + B] (out int64 [2B]): both halves of the batch carry the same history.  guidance must be finite. */
 int dvq_sample_guided(const void* logits, int dtype, int64_t B, int64_t V, int64_t ldl, float guidance, float temperature,
-                      const int64_t* forbid_idx, int64_t n_forbid, int64_t forbid_ld, int64_t forbid_from,
-                      const int64_t* forbid_codes4, int64_t keep_code, int64_t late_forbid_code, int64_t pad_code,
-                      const float* finished, int top_k, float top_p, int sample, uint64_t* state, int64_t* out,
-                      dvq_stream_t stream);
+                      const dvq_token_rule* rule, int top_k, float top_p, int sample, uint64_t* state, int64_t* out, dvq_stream_t stream);
 /* Fused causal multi-head self-attention (bf16, head_dim 64 or 128) -- CausalSelfAttention.forward, stackgpt.py:41-69:
  *   out = attn_drop(softmax(causal_mask(q k^T * scale))) v      per (batch, head), scores never materialised.
  * q, k, v, dq, dk, dv: [B*T] rows of n_head*head_dim columns (head h = columns h*head_dim ..), ldqkv elements between consecutive rows.
@@ -929,9 +939,8 @@ int dvq_image_grid_u8(const float* x, int64_t N, int64_t C, int64_t H, int64_t W
                       size_t out_bytes, void* ws, size_t ws_bytes, dvq_stream_t stream);
 
 /* Lossless token codec (csrc/codec.hip, docs/design/27-token-codec.md): rANS driven by the DQ-Transformer's next-token distributions.
- * The frequency table of a logits row [V <= 2048] of `dtype` (row pitch ldl) under a constraint rule -- the rule arguments of
- * dvq_sample_constrained: forbid_idx int64 [B][forbid_ld] (n_forbid used), forbid_from (< 0: none), forbid_codes4 (host int64 [4], -1:
- * unused), keep_code, late_forbid_code, pad_code, finished fp32 [B] or NULL -- is
+ * The frequency table of a logits row [V <= DVQ_TOKEN_RULE_MAXV] of `dtype` (row pitch ldl) under `rule` (dvq_token_rule above, the
+ * sampler's) is
  *   A = the columns the rule leaves to a live row and whose logit is finite (a finished row: {pad_code}), n = |A|, M = 65536;
  *   n == 1: f = M on that column;  n == 0: f = 0 everywhere;
  *   n >= 2: e_c = expf(x_c - max_A x), S = sum_A e_c in fp32 (lane l of 64 adds columns l, l + 64, ... in ascending order, then a fixed
@@ -950,19 +959,14 @@ int dvq_image_grid_u8(const float* x, int64_t N, int64_t C, int64_t H, int64_t W
  *   (the caller starts with state = word 0 | word 1 << 32, cursor = 2); token int64 [B] = the column c with cum_c <= state mod M <
  *   cum_c + f_c (pad_code for a finished row, the one allowed column when n == 1); the state advances and refills at most one word
  *   from words[base + cursor] iff cursor < count and base + cursor < total_words -- otherwise a zero word and error bit 2. */
-int dvq_codec_tables(const void* logits, int dtype, int64_t B, int64_t V, int64_t ldl, const int64_t* forbid_idx, int64_t n_forbid,
-                     int64_t forbid_ld, int64_t forbid_from, const int64_t* forbid_codes4, int64_t keep_code, int64_t late_forbid_code,
-                     int64_t pad_code, const float* finished, uint32_t* table, dvq_stream_t stream);
-int dvq_codec_record(const void* logits, int dtype, int64_t B, int64_t V, int64_t ldl, const int64_t* forbid_idx, int64_t n_forbid,
-                     int64_t forbid_ld, int64_t forbid_from, const int64_t* forbid_codes4, int64_t keep_code, int64_t late_forbid_code,
-                     int64_t pad_code, const float* finished, const int64_t* target, uint32_t* records, int64_t rec_ld, int64_t step,
-                     int64_t* token, uint32_t* err, dvq_stream_t stream);
+int dvq_codec_tables(const void* logits, int dtype, int64_t B, int64_t V, int64_t ldl, const dvq_token_rule* rule, uint32_t* table,
+                     dvq_stream_t stream);
+int dvq_codec_record(const void* logits, int dtype, int64_t B, int64_t V, int64_t ldl, const dvq_token_rule* rule, const int64_t* target,
+                     uint32_t* records, int64_t rec_ld, int64_t step, int64_t* token, uint32_t* err, dvq_stream_t stream);
 int dvq_codec_encode(const uint32_t* records, int64_t B, int64_t T, int64_t rec_ld, const int64_t* counts, const uint8_t* kinds,
                      uint32_t* words, int64_t cap, int64_t* nwords, double* bits, dvq_stream_t stream);
-int dvq_codec_decode_step(const void* logits, int dtype, int64_t B, int64_t V, int64_t ldl, const int64_t* forbid_idx, int64_t n_forbid,
-                          int64_t forbid_ld, int64_t forbid_from, const int64_t* forbid_codes4, int64_t keep_code,
-                          int64_t late_forbid_code, int64_t pad_code, const float* finished, int64_t* state, const uint32_t* words,
-                          int64_t total_words, int64_t* token, uint32_t* err, dvq_stream_t stream);
+int dvq_codec_decode_step(const void* logits, int dtype, int64_t B, int64_t V, int64_t ldl, const dvq_token_rule* rule, int64_t* state,
+                          const uint32_t* words, int64_t total_words, int64_t* token, uint32_t* err, dvq_stream_t stream);
 
 #ifdef __cplusplus
 }

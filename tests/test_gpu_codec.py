@@ -218,6 +218,66 @@ def test_tables_against_restatement(dev, v):
             assert int(f[r].sum()) == M and np.array_equal(f[r] > 0, ref > 0)
 
 
+def test_sampler_and_codec_share_one_rule(dev):
+    """the same rule keywords through both kernels, at the codec's lane-stride edges and the sampler's sort-size steps (256 / 512 / 1024
+    threads), fp32 and bf16, B in {1, 5}, dense and strided logits, every rule kind:
+    (a) the greedy draw (temperature 1, no top-k / top-p) is, per row, the lowest-index arg-max of the logits over the columns the
+        codec gives a frequency to -- pad_code on the finished row, the one column of the single-symbol row;
+    (b) dvq_sample_guided at guidance 1 on [logits ; other random logits] with the 2B-row lists and flags returns those tokens in both
+        halves.
+    And a bad rule (pad_code = V, pad_code < 0) or V = 2049 is refused by all five wrappers with a DvqError, nothing written."""
+    from dynamicvectorquantization_amd import kernels as K
+    for v in (2, 64, 65, 256, 257, 1024, 1025, 2048):
+        for di, dtype in enumerate((torch.float32, torch.bfloat16)):
+            for b in (1, 5):
+                for strided in (False, True):
+                    for ki, kind in enumerate(_kinds(v)):
+                        what = (v, dtype, b, strided, kind)
+                        df, logits, sampled, done = _case(dev, b, v, dtype, strided, kind, seed=v * 29 + b * 11 + ki * 3 + di)
+                        f, kw = _tables(logits, df, kind, sampled, done)
+                        allowed = f > 0
+                        x = logits.float().masked_fill(~allowed, float("-inf"))
+                        cols = torch.arange(v, device=dev).expand(b, v)
+                        want = torch.where(x == x.max(dim=1, keepdim=True)[0], cols, torch.full_like(cols, v)).min(dim=1)[0]
+                        assert bool(allowed.any(dim=1).all()), what                                # no row is left empty
+                        tok = K.sample_constrained(logits, 1.0, state=None, finished=done, sample=False, **kw)
+                        assert torch.equal(tok.view(-1), want), what
+                        if b >= 5:
+                            assert int(tok[1]) == kw["pad_code"] and int(allowed[b - 1].sum()) == 1, what
+                        pair = torch.empty(2 * b, v + 5 if strided else v, dtype=dtype, device=dev)[:, :v]
+                        pair[:b] = logits
+                        pair[b:] = (3.0 * torch.randn(b, v, generator=torch.Generator().manual_seed(v + ki))).to(dtype).to(dev)
+                        kw2 = dict(kw, forbid_idx=torch.cat([sampled, sampled])) if "forbid_idx" in kw else kw
+                        got = K.sample_guided(pair, 1.0, 1.0, state=None, finished=torch.cat([done, done]), sample=False, **kw2)
+                        assert torch.equal(got[:b], tok) and torch.equal(got[b:], tok), what
+    _bad_rules_are_refused(dev)
+
+
+def _bad_rules_are_refused(dev):
+    from dynamicvectorquantization_amd import kernels as K
+    from dynamicvectorquantization_amd._lib import DvqError
+    for v, pad in ((64, 64), (64, -1), (2049, 0)):
+        b = 3
+        lg = torch.zeros(b, v, device=dev)
+        tg = torch.zeros(b, dtype=torch.int64, device=dev)
+        rec = torch.full((b, 2), -1, dtype=torch.int32, device=dev)
+        err = torch.zeros(b, dtype=torch.int32, device=dev)
+        words = torch.zeros(b * 3, dtype=torch.int32, device=dev)
+        state = K.codec_decode_state(words, torch.arange(b, device=dev) * 3, torch.full((b,), 3, device=dev))
+        state0 = state.clone()
+        calls = {"sample_constrained": lambda: K.sample_constrained(lg, 1.0, pad, None, sample=False),
+                 "sample_guided": lambda: K.sample_guided(torch.cat([lg, lg]), 1.0, 1.0, pad, None, sample=False),
+                 "codec_tables": lambda: K.codec_tables(lg, pad),
+                 "codec_record": lambda: K.codec_record(lg, tg, rec, 0, err, pad),
+                 "codec_decode_step": lambda: K.codec_decode_step(lg, state, words, err, pad)}
+        for name, call in calls.items():
+            with pytest.raises(DvqError):
+                call()
+                pytest.fail(f"{name} took V = {v}, pad_code = {pad}")
+        torch.cuda.synchronize()
+        assert bool((rec == -1).all()) and int(err.abs().sum()) == 0 and torch.equal(state, state0), (v, pad)
+
+
 @pytest.fixture(scope="module")
 def long_run(dev):
     """record + encode 300 steps of fresh random logits for 5 rows that finish at different steps (one from the start); shared by the

@@ -49,6 +49,21 @@ def test_impl_codes_match_the_header():
     assert accepted == [0, 1, 2, 3, 4, 9] and rt.impl() == 0
 
 
+def test_token_rule_block_matches_the_header():
+    """dvq_token_rule and DVQ_TOKEN_RULE_MAXV of include/dvq_hip.h against _lib's mirrors: same members in the same order, all 8 bytes
+    wide; and no entry point takes the rule as loose arguments any more"""
+    import ctypes as C
+    from dynamicvectorquantization_amd import _lib
+    header = open(os.path.join(REPO, "include", "dvq_hip.h")).read()
+    body = re.search(r"typedef struct dvq_token_rule \{(.*?)\} dvq_token_rule;", header, re.S).group(1)
+    members = [re.sub(r"\[\d+\]", "", n.strip()) for decl in re.findall(r"(?:const )?\w+\*?\s+([^;]+);", body) for n in decl.split(",")]
+    assert members == [n for n, _ in _lib.TokenRule._fields_] and len(members) == 9
+    assert C.sizeof(_lib.TokenRule) == 8 * (len(members) + 3)           # forbid_codes4 is int64 [4]
+    assert int(re.search(r"#define DVQ_TOKEN_RULE_MAXV (\d+)", header).group(1)) == _lib.TokenRule.MAXV
+    protos = header[header.index("} dvq_token_rule;"):]
+    assert "forbid_from," not in protos and "forbid_codes4," not in protos and protos.count("const dvq_token_rule* rule") == 5
+
+
 def test_error_convention_without_gpu():
     from dynamicvectorquantization_amd import _lib
     lib = _lib.load()
@@ -511,7 +526,7 @@ def test_one_library_without_probe_code():
     lib = _lib.load()
     assert not hasattr(lib, "dvq_halo_trace_read")
     assert not hasattr(lib, "dvq_conv3x3_halo2_try")
-    assert lib.dvq_version() == 122
+    assert lib.dvq_version() == 123
 
 
 # the environment names the Python package reads that are paths or build inputs, not switches: read where they are used
