@@ -95,18 +95,13 @@ SIGNATURES = {
     "dvq_gn_bwd_partial_bytes": (sz, [i64, i64, i64]),
     "dvq_gn_bwd_reduce": (i32, [vp, vp, i32, i64, i64, i64, i32, vp, vp, vp, i32, vp, vp, vp, vp, vp]),
     "dvq_gn_bwd_dx": (i32, [vp, vp, i32, i64, i64, i64, i32, vp, vp, vp, i32, vp, vp, vp, vp]),
-    "dvq_conv2d_fwd": (i32, [C.POINTER(ConvDesc), vp, vp, vp, vp, vp, vp, vp, i32, i32, vp]),
+    "dvq_conv2d_fwd": (i32, [C.POINTER(ConvDesc), vp, vp, vp, vp, vp, vp, vp, i32, i32, vp, i64, vp]),
     "dvq_conv3x3_fused_ok": (i32, [C.POINTER(ConvDesc)]),
     "dvq_conv3x3_subpixel_ok": (i32, [C.POINTER(ConvDesc)]),
     "dvq_split_bf16_planes": (i32, [vp, vp, vp, i64, i64, i64, vp]),
-    "dvq_conv3x3_x3_ok": (i32, [C.POINTER(ConvDesc), i32]),
-    "dvq_conv3x3_x3_scratch_bytes": (i64, [C.POINTER(ConvDesc), i32]),
-    "dvq_conv2d_fwd_x3": (i32, [C.POINTER(ConvDesc), vp, vp, vp, vp, vp, i32, vp, i64, vp]),
-    "dvq_conv2d_dgrad_x3": (i32, [C.POINTER(ConvDesc), vp, vp, vp, vp, vp, i32, vp, i64, vp]),
-    "dvq_conv2d_wgrad_x3_scratch_bytes": (i64, [C.POINTER(ConvDesc)]),
-    "dvq_conv2d_wgrad_oihw_x3": (i32, [C.POINTER(ConvDesc), vp, vp, i64, i64, vp, vp, i32, vp, i64, vp]),
+    "dvq_conv2d_scratch_bytes": (i64, [C.POINTER(ConvDesc), i32]),
     "dvq_gn_scale_shift": (i32, [vp, vp, vp, i64, i64, i64, i32, f32, vp, vp, vp]),
-    "dvq_conv2d_dgrad": (i32, [C.POINTER(ConvDesc), vp, vp, vp, vp, vp, i32, vp]),
+    "dvq_conv2d_dgrad": (i32, [C.POINTER(ConvDesc), vp, vp, vp, vp, vp, i32, vp, i64, vp]),
     "dvq_set_workspace": (i32, [vp, i64]),
     "dvq_workspace_release": (i32, [vp]),
     "dvq_cmdlist_create": (i32, [vp, C.POINTER(vp)]),
@@ -131,7 +126,7 @@ SIGNATURES = {
     "dvq_maxpool2x2_relu_bwd": (i32, [vp, vp, vp, i32, i64, i64, i64, i64, vp, vp]),
     "dvq_lpips_head": (i32, [vp, vp, vp, i32, i64, i64, i64, vp, f32, vp, vp]),
     "dvq_lpips_head_drop": (i32, [vp, vp, vp, i32, i64, i64, i64, vp, f32, vp, f32, C.c_uint64, vp]),
-    "dvq_conv2d_wgrad": (i32, [C.POINTER(ConvDesc), vp, vp, i64, i64, vp, vp, i32, vp, vp]),
+    "dvq_conv2d_wgrad": (i32, [C.POINTER(ConvDesc), vp, vp, i64, i64, vp, vp, i32, vp, vp, i64, vp]),
     "dvq_pack_weights_multi": (i32, [vp, i64, i64, vp]),
     "dvq_linear_pack_multi": (i32, [vp, i64, i64, vp]),
     "dvq_pack_weight": (i32, [vp, i64, i64, i64, i64, i64, i64, i32, vp, vp, vp]),

@@ -86,7 +86,7 @@ constexpr int VOFF_OOB = 0x7ffffff0;            // beyond every descriptor's ran
 //
 // OUT32 (round 5, fp32x3): Y and R are FP32 tensors; the accumulators leave the kernel unrounded.  The bf16 input then carries the three
 // products of the split scheme side by side on the channel axis -- x' = [x_hi | x_lo | x_hi], w' = [w_hi | w_hi | w_lo], 3 Cin channels --
-// so one launch forms x_hi.w_hi + x_lo.w_hi + x_hi.w_lo in its fp32 accumulators (dvq_conv2d_fwd_x3 / dvq_conv2d_dgrad_x3, igemm.hip).
+// so one launch forms x_hi.w_hi + x_lo.w_hi + x_hi.w_lo in its fp32 accumulators (conv_x3_halo, igemm.hip).
 // Only the epilogue differs: the 256 px x CO_T tile is staged 64 channels (256-B fp32 rows) at a time through the same 64 KiB.
 //
 // SUB (nearest x2 upsample + 3x3, Upsample of model.py:38-53): the upsampled image holds every source pixel four times, so an output pixel

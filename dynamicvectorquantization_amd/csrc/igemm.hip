@@ -12,11 +12,13 @@
 //
 // Map of the files:
 //   igemm.h       host-side contract: NtParams / TnParams, MODE_*, launch_nt<T>, launch_tn<T>, launch_nt_skinny
-//   igemm_dev.h   device pieces both sides use: tile constants, swizzles, MFMA stage loops, fp32x3 split, zero page
+//   igemm_dev.h   device pieces the three .hip files use: tile constants, swizzles, MFMA stage loops, fp32x3 split (split8_bf16), zero page
 //   igemm_nt.hip  every NT kernel with its epilogues, predicates and launchers; launch_nt
 //   igemm_tn.hip  every TN kernel with the deterministic fold, predicates and launchers; launch_tn
-//   igemm.hip     this file, the front end: descriptor checks, params builders, the extern "C" entry points, the fp32x3 launch-level schemes
+//   igemm.hip     this file, the front end: descriptor checks, params builders, the fp32x3 launch-level schemes (plane kernels, the scratch
+//                 rule, the routes) and the extern "C" entry points that pick between them and the kernels of the two files above
 #include "igemm.h"
+#include "igemm_dev.h"
 
 using namespace igemm;
 
@@ -74,8 +76,31 @@ int dvq_conv3x3_halo_out32_try(const void* x, const void* w, const float* bias, 
                                int64_t H, int64_t W, int64_t Cin, int64_t Cout, int flip, int up, float act_slope, int res_mask,
                                float mask_slope, hipStream_t stream);
 
-// fp32x3 on the halo kernel (dvq_conv2d_fwd_x3 below): bf16 planes side by side on the channel axis
-// MODE 0 (activations): [hi | lo | hi]; MODE 1 (weights, rows = Cout x 9): [hi | hi | lo].  c % 8 == 0.
+// -------------------------------------------------------------------------------------------------
+// fp32x3 at LAUNCH level (round 5): the three products of the split scheme -- lo.hi + hi.lo + hi.hi, see split8_bf16 -- on the bf16
+// kernels, from bf16 PLANES of the fp32 operands (hi = RNE(x), lo = RNE(x - hi)) that an HBM-bound pass writes once per operand into
+// caller-provided scratch, instead of the fp32 kernels that split at every fragment read.  dvq_conv2d_fwd / _dgrad / _wgrad take these
+// routes when the caller hands them scratch (x3_route); dvq_conv2d_scratch_bytes is the size rule (x3_scratch_need).
+//
+// Forward / input gradient of the 3 x 3 / stride 1 / pad 1 convolutions on the HALO kernel (conv_x3_halo).  The three products are laid
+// side by side on the channel axis of bf16 operands -- x' = [x_hi | x_lo | x_hi] and, per tap, w' = [w_hi | w_hi | w_lo], 3 Cin channels --
+// so ONE launch of the bf16 halo kernel forms x_hi.w_hi + x_lo.w_hi + x_hi.w_lo in its fp32 accumulators, and its fp32-output
+// instantiation (conv_halo.hip, OUT32) stores them unrounded, after the fp32 residual / gate / activation.  Same products, same
+// accumulation type as the in-kernel split of igemm_nt_glds_kernel<float, S3>, on a kernel that stages every activation once for all 9
+// taps (the fp32 kernel: 200 - 250 TFLOP/s nominal, bound by its 2-us stages, section 3 of DESIGN.md).  Costs: one pass writes x' (4 B
+// read + 6 B written per element), the weights are re-laid per call (Cout x 9 x Cin elements).
+//
+// Weight gradients (conv_wgrad_x3).  A weight gradient is accumulated in fp32 whatever the operand type (atomics or partials + fold into
+// the fp32 gradient), so the three products can be three launches of the bf16 weight-gradient kernels (halo / patch / transpose-read:
+// 600 - 1200 TFLOP/s) instead of one launch of the register-staged fp32 kernel (140 - 190 TFLOP/s nominal, and 9 passes over the
+// activations for a 3 x 3 kernel).  Planes cost 4 B read, 4 B written per element; channels are padded from the fp32 layout's multiple
+// of 4 to the bf16 kernels' multiple of 8 on the way.
+// -------------------------------------------------------------------------------------------------
+namespace {
+
+// Both plane kernels: one thread per 8 channels, two 16-B loads, split8_bf16, 16-B stores.
+// split_concat3_kernel: planes side by side on the channel axis.  MODE 0 (activations): [hi | lo | hi]; MODE 1 (weights, rows = Cout x 9):
+// [hi | hi | lo].  c % 8 == 0.
 template <int MODE>
 __global__ __launch_bounds__(256) void split_concat3_kernel(const float* __restrict__ x, bf16_t* __restrict__ out, int64_t rows, int c) {
     const int cpr = c >> 3;
@@ -84,25 +109,35 @@ __global__ __launch_bounds__(256) void split_concat3_kernel(const float* __restr
         const int64_t r = i / cpr;
         const int c0 = (int)(i - r * cpr) << 3;
         const float* src = x + r * c + c0;
-        const float4 a = *reinterpret_cast<const float4*>(src), b = *reinterpret_cast<const float4*>(src + 4);
-        const float v[8] = {a.x, a.y, a.z, a.w, b.x, b.y, b.z, b.w};
-        uint4 h, l;
-        unsigned* hp = &h.x;
-        unsigned* lp = &l.x;
-#pragma unroll
-        for (int e = 0; e < 4; ++e) {
-            const unsigned ph = pack_bf16x2(v[2 * e], v[2 * e + 1]);
-            hp[e] = ph;
-            lp[e] = pack_bf16x2(v[2 * e] - __uint_as_float(ph << 16), v[2 * e + 1] - __uint_as_float(ph & 0xffff0000u));
-        }
+        bf16x8 h, l;
+        split8_bf16(*reinterpret_cast<const f32x4*>(src), *reinterpret_cast<const f32x4*>(src + 4), h, l);
         bf16_t* dst = out + r * 3 * c + c0;
-        *reinterpret_cast<uint4*>(dst) = h;
-        *reinterpret_cast<uint4*>(dst + c) = MODE == 0 ? l : h;
-        *reinterpret_cast<uint4*>(dst + 2 * c) = MODE == 0 ? h : l;
+        *reinterpret_cast<bf16x8*>(dst) = h;
+        *reinterpret_cast<bf16x8*>(dst + c) = MODE == 0 ? l : h;
+        *reinterpret_cast<bf16x8*>(dst + 2 * c) = MODE == 0 ? h : l;
     }
 }
 
-static int split_concat3(const float* x, void* out, int64_t rows, int64_t c, int mode, hipStream_t s) {
+// separate planes of `cout` channels each; channels >= cin are zero
+__global__ __launch_bounds__(256) void split_planes_kernel(const float* __restrict__ x, bf16_t* __restrict__ hi, bf16_t* __restrict__ lo,
+                                                           int64_t rows, int cin, int cout) {
+    const int cpr = cout >> 3;                          // 8-channel chunks per output row
+    const int64_t total = rows * cpr;
+    for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < total; i += (int64_t)gridDim.x * 256) {
+        const int64_t r = i / cpr;
+        const int c0 = (int)(i - r * cpr) << 3;
+        const float* src = x + r * cin + c0;
+        f32x4 a = {0.f, 0.f, 0.f, 0.f}, b = a;
+        if (c0 < cin) a = *reinterpret_cast<const f32x4*>(src);            // cin % 4 == 0
+        if (c0 + 4 < cin) b = *reinterpret_cast<const f32x4*>(src + 4);
+        bf16x8 h, l;
+        split8_bf16(a, b, h, l);
+        *reinterpret_cast<bf16x8*>(hi + r * cout + c0) = h;
+        *reinterpret_cast<bf16x8*>(lo + r * cout + c0) = l;
+    }
+}
+
+int split_concat3(const float* x, void* out, int64_t rows, int64_t c, int mode, hipStream_t s) {
     const int64_t total = rows * (c / 8);
     int64_t blocks = cdiv64(total, 256);
     if (blocks > 256 * 64) blocks = 256 * 64;
@@ -111,6 +146,39 @@ static int split_concat3(const float* x, void* out, int64_t rows, int64_t c, int
     DVQ_CHECK_LAUNCH("split_concat3");
     return DVQ_OK;
 }
+
+inline int64_t pad8(int64_t c) { return (c + 7) & ~(int64_t)7; }
+inline int64_t up256(int64_t v) { return (v + 255) & ~(int64_t)255; }
+
+// shapes conv_x3_halo takes.  cs: channels of the streamed operand (x: Cin / dy: Cout), co: channels produced
+bool x3_halo_shape_ok(const dvq_conv_desc* d, int64_t cs, int64_t co) {
+    return d->KH == 3 && d->KW == 3 && d->stride == 1 && d->pad_t == 1 && d->pad_l == 1 && d->OH == d->H && d->OW == d->W && d->H % 8 == 0 &&
+           d->W % 32 == 0 && cs % 64 == 0 && co >= 4 && co % 4 == 0 && d->N * d->H * d->W * (3 * cs > co ? 3 * cs : co) < (1ll << 31) &&
+           co * 27 * cs < (1ll << 31) && d->H * d->W * co * 4 < (1ll << 31);
+}
+
+// dvq_conv2d_scratch_bytes: what the launch-level route of `pass` wants for this descriptor, 0 when there is no such route
+int64_t x3_scratch_need(const dvq_conv_desc* d, int pass) {
+    if (d->dtype != DVQ_F32 || d->impl != DVQ_IMPL_AUTO || !dvq_fp32_split()) return 0;
+    const int64_t xrows = d->N * (d->H >> d->upsample) * (d->W >> d->upsample), yrows = d->N * d->OH * d->OW;
+    if (pass == DVQ_PASS_WGRAD)
+        return 4 * (xrows * pad8(d->Cin) + yrows * pad8(d->Cout)) + 1024;       // two bf16 planes per operand, 256-B aligned starts
+    const bool dgrad = pass == DVQ_PASS_DGRAD;
+    const int64_t cs = dgrad ? d->Cout : d->Cin, co = dgrad ? d->Cin : d->Cout;
+    if (!x3_halo_shape_ok(d, cs, co)) return 0;
+    return up256((dgrad ? d->N * d->H * d->W : xrows) * 3 * cs * 2) + up256(co * 9 * 3 * cs * 2);
+}
+
+// 1: this call takes the launch-level route of `pass` (it wants scratch and got some); 0: it does not; DVQ_EWORKSPACE: bad scratch
+int x3_route(const dvq_conv_desc* d, int pass, const void* scratch, int64_t scratch_bytes, const char* who) {
+    const int64_t need = x3_scratch_need(d, pass);
+    if (need == 0 || scratch == nullptr) return 0;
+    DVQ_REQUIRE(scratch_bytes >= need && ((uintptr_t)scratch & 15) == 0, DVQ_EWORKSPACE,
+                "%s: scratch smaller than dvq_conv2d_scratch_bytes or not 16-B aligned", who);
+    return 1;
+}
+
+}  // namespace
 
 static bool halo_eligible(const dvq_conv_desc* d) {
     return d->dtype == DVQ_BF16 && d->KH == 3 && d->KW == 3 && d->stride == 1 && d->pad_t == 1 && d->pad_l == 1 &&
@@ -203,6 +271,74 @@ static TnParams gemm_tn_params(const void* A, const void* B, float* C, float* co
     return p;
 }
 
+int dvq_sumpool2x2(const void* in, int dtype, int64_t N, int64_t h, int64_t w, int64_t C, void* out, dvq_stream_t stream);
+
+// fp32x3 forward (dgrad = 0: a = x, wgt = w) / input gradient (dgrad = 1: a = dy, wgt = wt, res = the mask, out at the logical input
+// resolution) on the halo kernel: concatenated planes into scratch, one OUT32 launch
+static int conv_x3_halo(const dvq_conv_desc* d, int dgrad, const void* a, const void* wgt, const float* bias, const void* res, void* out,
+                        float act_slope, int res_mask, float mask_slope, void* scratch, hipStream_t stream) {
+    const int64_t cs = dgrad ? d->Cout : d->Cin, co = dgrad ? d->Cin : d->Cout;
+    const int64_t rows = dgrad ? d->N * d->H * d->W : d->N * (d->H >> d->upsample) * (d->W >> d->upsample);
+    char* as = (char*)scratch;
+    char* ws = as + up256(rows * 3 * cs * 2);
+    if (int e = split_concat3((const float*)a, as, rows, cs, 0, stream)) return e;
+    if (int e = split_concat3((const float*)wgt, ws, co * 9, cs, 1, stream)) return e;
+    const int rc = dvq_conv3x3_halo_out32_try(as, ws, bias, (const float*)res, (float*)out, d->N, d->H, d->W, 3 * cs, co, dgrad,
+                                              dgrad ? 0 : d->upsample, act_slope, res_mask, mask_slope, stream);
+    if (rc < 0) return rc;
+    DVQ_REQUIRE(rc == 1, DVQ_ESHAPE, "fp32x3 convolution: the halo kernel refused the shape");
+    dvq_note_kernel("conv_x3_halo");              // the route's label, over the halo kernel's own note
+    return DVQ_OK;
+}
+
+// the weight gradient behind dvq_conv2d_wgrad's argument checks
+static int conv_wgrad(const dvq_conv_desc* d, const void* x, const void* dy, int64_t cin_real, int64_t cout_real, float* grad, float* dbias,
+                      int ohwi, const float* gn_scale_shift, hipStream_t stream) {
+    if (halo_eligible(d)) {
+        const int rc = dvq_conv3x3_halo_wgrad_try(x, dy, grad, dbias, d->N, d->H, d->W, d->Cin, d->Cout, cin_real,
+                                                  cout_real, ohwi ? 0 : 1, d->upsample, gn_scale_shift, stream);
+        if (rc != 0) return rc < 0 ? rc : DVQ_OK;
+    }
+    DVQ_REQUIRE(gn_scale_shift == nullptr, DVQ_ESHAPE, "dvq_conv2d_wgrad: fused GroupNorm needs a shape accepted by dvq_conv3x3_fused_ok");
+    DVQ_REQUIRE(d->impl != DVQ_IMPL_HALO, DVQ_ESHAPE, "dvq_conv2d_wgrad: shape not eligible for the halo kernel");
+    const TnParams p = conv_tn_params(d, x, dy, cin_real, cout_real, grad, dbias, ohwi);
+    if (d->dtype == DVQ_F32) return launch_tn<float>(p, 1, d->impl, stream);
+    return launch_tn<bf16_t>(p, 1, d->impl, stream);
+}
+
+// fp32x3 weight gradient: bf16 planes of both operands into scratch, then the bf16 weight gradient over them
+static int conv_wgrad_x3(const dvq_conv_desc* d, const void* x, const void* dy, int64_t cin_real, int64_t cout_real, float* grad,
+                         float* dbias, int ohwi, void* scratch, hipStream_t stream) {
+    const int64_t xrows = d->N * (d->H >> d->upsample) * (d->W >> d->upsample), yrows = d->N * d->OH * d->OW;
+    const int64_t c8 = pad8(d->Cin), o8 = pad8(d->Cout);
+    char* xh = (char*)scratch;
+    char* xl = xh + up256(xrows * c8 * 2);
+    char* yh = xl + up256(xrows * c8 * 2);
+    char* yl = yh + up256(yrows * o8 * 2);
+    if (int e = dvq_split_bf16_planes((const float*)x, xh, xl, xrows, d->Cin, c8, stream)) return e;
+    if (int e = dvq_split_bf16_planes((const float*)dy, yh, yl, yrows, d->Cout, o8, stream)) return e;
+    dvq_conv_desc b = *d;
+    b.dtype = DVQ_BF16;
+    b.Cin = c8;
+    b.Cout = o8;
+    // 3 x 3 / stride 1 / pad 1 on the halo kernel: ONE launch over "3 N images" -- image n of plane triple (x_lo, dy_hi), (x_hi, dy_lo),
+    // (x_hi, dy_hi) -- instead of three launches with three folds of the partials (the planes of an operand are contiguous: eligible
+    // shapes have plane sizes that are multiples of 256 bytes).  Shapes the halo kernel does not take: three launches
+    int rc = 0;
+    if (halo_eligible(&b) && xl == xh + xrows * c8 * 2 && yl == yh + yrows * o8 * 2)
+        rc = dvq_conv3x3_halo_wgrad_planes_try(xh, yh, grad, dbias, d->N, d->H, d->W, c8, o8, cin_real, cout_real, ohwi ? 0 : 1, d->upsample,
+                                               stream);
+    if (rc < 0) return rc;
+    if (rc == 0) {
+        // small terms first; the bias gradient (column sums of dy) is the sum over BOTH dy planes, taken on the two launches that read x_hi
+        if (int e = conv_wgrad(&b, xl, yh, cin_real, cout_real, grad, nullptr, ohwi, nullptr, stream)) return e;
+        if (int e = conv_wgrad(&b, xh, yl, cin_real, cout_real, grad, dbias, ohwi, nullptr, stream)) return e;
+        if (int e = conv_wgrad(&b, xh, yh, cin_real, cout_real, grad, dbias, ohwi, nullptr, stream)) return e;
+    }
+    dvq_note_kernel("conv_wgrad_x3_planes");      // the route's label, over the note of the kernel that ran last
+    return DVQ_OK;
+}
+
 // =================================================================================================
 extern "C" {
 
@@ -220,7 +356,8 @@ int dvq_conv3x3_subpixel_ok(const dvq_conv_desc* d) {
 }
 
 int dvq_conv2d_fwd(const dvq_conv_desc* d_in, const void* x, const void* w, const float* bias, const void* residual, void* y,
-                   const float* gn_scale_shift, double* out_stats, int out_groups, int act, dvq_stream_t stream) {
+                   const float* gn_scale_shift, double* out_stats, int out_groups, int act, void* scratch, int64_t scratch_bytes,
+                   dvq_stream_t stream) {
     dvq_note_kernel("");
     DVQ_REQUIRE(d_in != nullptr, DVQ_EINVAL, "dvq_conv2d_fwd: null descriptor");
     dvq_conv_desc dd = *d_in;
@@ -231,6 +368,9 @@ int dvq_conv2d_fwd(const dvq_conv_desc* d_in, const void* x, const void* w, cons
     DVQ_REQUIRE(act == DVQ_ACT_NONE || (residual == nullptr && gn_scale_shift == nullptr && out_stats == nullptr), DVQ_EINVAL,
                 "dvq_conv2d_fwd: activation together with residual, gn_scale_shift or out_stats");
     DVQ_REQUIRE(x && w && y, DVQ_EINVAL, "dvq_conv2d_fwd: null pointer");
+    const int x3 = gn_scale_shift || out_stats ? 0 : x3_route(d, DVQ_PASS_FWD, scratch, scratch_bytes, "dvq_conv2d_fwd");
+    if (x3 < 0) return x3;
+    if (x3) return conv_x3_halo(d, 0, x, w, bias, residual, y, act_slope_of(act), 0, 0.f, scratch, (hipStream_t)stream);
     if (halo_eligible(d) && d->impl == DVQ_IMPL_AUTO && d->Cin == 8 && !d->upsample && residual == nullptr && gn_scale_shift == nullptr &&
         out_stats == nullptr) {          // image heads: 8 (padded) input channels
         const int rc = dvq_conv3x3_thin_k_try(x, w, bias, y, d->N, d->H, d->W, d->Cout, 0, act_slope_of(act), (hipStream_t)stream);
@@ -258,10 +398,8 @@ int dvq_conv2d_fwd(const dvq_conv_desc* d_in, const void* x, const void* w, cons
     return launch_nt<bf16_t>(p, 1, d->impl, (hipStream_t)stream);
 }
 
-int dvq_sumpool2x2(const void* in, int dtype, int64_t N, int64_t h, int64_t w, int64_t C, void* out, dvq_stream_t stream);
-
 int dvq_conv2d_dgrad(const dvq_conv_desc* d_in, const void* dy, const void* wt, void* dx, void* ws, const void* mask, int mask_act,
-                     dvq_stream_t stream) {
+                     void* scratch, int64_t scratch_bytes, dvq_stream_t stream) {
     dvq_note_kernel("");
     DVQ_REQUIRE(d_in != nullptr, DVQ_EINVAL, "dvq_conv2d_dgrad: null descriptor");
     dvq_conv_desc dd = *d_in;
@@ -271,6 +409,14 @@ int dvq_conv2d_dgrad(const dvq_conv_desc* d_in, const void* dy, const void* wt, 
     DVQ_REQUIRE(mask == nullptr || ((mask_act == DVQ_ACT_RELU || mask_act == DVQ_ACT_LRELU) && !d->upsample), DVQ_EINVAL,
                 "dvq_conv2d_dgrad: mask needs act in {relu, lrelu} and no folded upsample");
     DVQ_REQUIRE(dy && wt && dx && (!d->upsample || ws || sub), DVQ_EINVAL, "dvq_conv2d_dgrad: null pointer");
+    const int x3 = x3_route(d, DVQ_PASS_DGRAD, scratch, scratch_bytes, "dvq_conv2d_dgrad");
+    if (x3 < 0) return x3;
+    if (x3) {
+        if (int e = conv_x3_halo(d, 1, dy, wt, nullptr, mask, d->upsample ? ws : dx, 1.f, mask != nullptr, act_slope_of(mask_act), scratch,
+                                 (hipStream_t)stream))
+            return e;
+        return d->upsample ? dvq_sumpool2x2(ws, d->dtype, d->N, d->H / 2, d->W / 2, d->Cin, dx, stream) : DVQ_OK;
+    }
     if (sub) {
         // the low-resolution gradient straight from one fp32 accumulation: ws is not touched, no 2x2 sum pass
         const bf16_t* wsub = (const bf16_t*)wt + d->Cin * 9 * d->Cout;
@@ -310,62 +456,20 @@ int dvq_conv2d_dgrad(const dvq_conv_desc* d_in, const void* dy, const void* wt, 
 }
 
 int dvq_conv2d_wgrad(const dvq_conv_desc* d, const void* x, const void* dy, int64_t cin_real, int64_t cout_real, float* grad,
-                     float* dbias, int ohwi, const float* gn_scale_shift, dvq_stream_t stream) {
+                     float* dbias, int ohwi, const float* gn_scale_shift, void* scratch, int64_t scratch_bytes, dvq_stream_t stream) {
     if (int e = conv_check(d, "dvq_conv2d_wgrad")) return e;
     DVQ_REQUIRE(x && dy && grad && cin_real > 0 && cin_real <= d->Cin && cout_real > 0 && cout_real <= d->Cout,
                 DVQ_EINVAL, "dvq_conv2d_wgrad: bad arguments");
-    if (halo_eligible(d)) {
-        const int rc = dvq_conv3x3_halo_wgrad_try(x, dy, grad, dbias, d->N, d->H, d->W, d->Cin, d->Cout, cin_real,
-                                                  cout_real, ohwi ? 0 : 1, d->upsample, gn_scale_shift, (hipStream_t)stream);
-        if (rc != 0) return rc < 0 ? rc : DVQ_OK;
-    }
-    DVQ_REQUIRE(gn_scale_shift == nullptr, DVQ_ESHAPE, "dvq_conv2d_wgrad: fused GroupNorm needs a shape accepted by dvq_conv3x3_fused_ok");
-    DVQ_REQUIRE(d->impl != DVQ_IMPL_HALO, DVQ_ESHAPE, "dvq_conv2d_wgrad: shape not eligible for the halo kernel");
-    const TnParams p = conv_tn_params(d, x, dy, cin_real, cout_real, grad, dbias, ohwi);
-    if (d->dtype == DVQ_F32) return launch_tn<float>(p, 1, d->impl, (hipStream_t)stream);
-    return launch_tn<bf16_t>(p, 1, d->impl, (hipStream_t)stream);
+    const int x3 = gn_scale_shift ? 0 : x3_route(d, DVQ_PASS_WGRAD, scratch, scratch_bytes, "dvq_conv2d_wgrad");
+    if (x3 < 0) return x3;
+    if (x3) return conv_wgrad_x3(d, x, dy, cin_real, cout_real, grad, dbias, ohwi, scratch, (hipStream_t)stream);
+    return conv_wgrad(d, x, dy, cin_real, cout_real, grad, dbias, ohwi, gn_scale_shift, (hipStream_t)stream);
 }
 
-// -------------------------------------------------------------------------------------------------
-// fp32x3 weight gradients at LAUNCH level (round 5).  A weight gradient is accumulated in fp32 whatever the operand type (atomics or
-// partials + fold into the fp32 gradient), so the three products of the split scheme -- lo.hi + hi.lo + hi.hi, see split8_bf16 -- can be
-// three launches of the bf16 weight-gradient kernels (halo / patch / transpose-read: 600 - 1200 TFLOP/s) on bf16 PLANES of the fp32
-// operands instead of one launch of the register-staged fp32 kernel that splits at every fragment read (140 - 190 TFLOP/s nominal, and
-// 9 passes over the activations for a 3 x 3 kernel).  The planes are written once per operand by an HBM-bound pass (4 B read, 4 B
-// written per element) into caller-provided scratch; channels are padded from the fp32 layout's multiple of 4 to the bf16 kernels'
-// multiple of 8 on the way.  Same rounding as split8_bf16: hi = RNE(x), lo = RNE(x - hi).
-// -------------------------------------------------------------------------------------------------
-namespace {
-
-__global__ __launch_bounds__(256) void split_planes_kernel(const float* __restrict__ x, bf16_t* __restrict__ hi, bf16_t* __restrict__ lo,
-                                                           int64_t rows, int cin, int cout) {
-    const int cpr = cout >> 3;                          // 8-channel chunks per output row
-    const int64_t total = rows * cpr;
-    for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < total; i += (int64_t)gridDim.x * 256) {
-        const int64_t r = i / cpr;
-        const int c0 = (int)(i - r * cpr) << 3;
-        const float* src = x + r * cin + c0;
-        float4 a = make_float4(0.f, 0.f, 0.f, 0.f), b = a;
-        if (c0 < cin) a = *reinterpret_cast<const float4*>(src);            // cin % 4 == 0
-        if (c0 + 4 < cin) b = *reinterpret_cast<const float4*>(src + 4);
-        const float v[8] = {a.x, a.y, a.z, a.w, b.x, b.y, b.z, b.w};
-        uint4 h, l;
-        unsigned* hp = &h.x;
-        unsigned* lp = &l.x;
-#pragma unroll
-        for (int e = 0; e < 4; ++e) {
-            const unsigned ph = pack_bf16x2(v[2 * e], v[2 * e + 1]);
-            hp[e] = ph;
-            lp[e] = pack_bf16x2(v[2 * e] - __uint_as_float(ph << 16), v[2 * e + 1] - __uint_as_float(ph & 0xffff0000u));
-        }
-        *reinterpret_cast<uint4*>(hi + r * cout + c0) = h;
-        *reinterpret_cast<uint4*>(lo + r * cout + c0) = l;
-    }
+int64_t dvq_conv2d_scratch_bytes(const dvq_conv_desc* d, int pass) {
+    if (d == nullptr || pass < DVQ_PASS_FWD || pass > DVQ_PASS_WGRAD || d->upsample < 0 || d->upsample > 1) return 0;
+    return x3_scratch_need(d, pass);
 }
-
-inline int64_t pad8(int64_t c) { return (c + 7) & ~(int64_t)7; }
-
-}  // namespace
 
 int dvq_split_bf16_planes(const float* x, void* hi, void* lo, int64_t rows, int64_t cin, int64_t cout, dvq_stream_t stream) {
     DVQ_REQUIRE(x && hi && lo, DVQ_EINVAL, "dvq_split_bf16_planes: null pointer");
@@ -377,126 +481,6 @@ int dvq_split_bf16_planes(const float* x, void* hi, void* lo, int64_t rows, int6
     split_planes_kernel<<<dim3((unsigned)blocks), dim3(256), 0, (hipStream_t)stream>>>(x, (bf16_t*)hi, (bf16_t*)lo, rows, (int)cin, (int)cout);
     DVQ_CHECK_LAUNCH("split_planes");
     return DVQ_OK;
-}
-
-int64_t dvq_conv2d_wgrad_x3_scratch_bytes(const dvq_conv_desc* d) {
-    if (d == nullptr || d->dtype != DVQ_F32) return 0;
-    const int64_t xrows = d->N * (d->H >> d->upsample) * (d->W >> d->upsample), yrows = d->N * d->OH * d->OW;
-    return 4 * (xrows * pad8(d->Cin) + yrows * pad8(d->Cout)) + 1024;       // two bf16 planes per operand, 256-B aligned starts
-}
-
-int dvq_conv2d_wgrad_oihw_x3(const dvq_conv_desc* d, const void* x, const void* dy, int64_t cin_real, int64_t cout_real,
-                             float* grad_oihw, float* dbias, int ohwi, void* scratch, int64_t scratch_bytes, dvq_stream_t stream) {
-    if (int e = conv_check(d, "dvq_conv2d_wgrad_oihw_x3")) return e;
-    DVQ_REQUIRE(d->dtype == DVQ_F32, DVQ_EINVAL, "dvq_conv2d_wgrad_oihw_x3: fp32 operands only");
-    DVQ_REQUIRE(x && dy && grad_oihw && scratch && cin_real > 0 && cin_real <= d->Cin && cout_real > 0 && cout_real <= d->Cout,
-                DVQ_EINVAL, "dvq_conv2d_wgrad_oihw_x3: bad arguments");
-    DVQ_REQUIRE(scratch_bytes >= dvq_conv2d_wgrad_x3_scratch_bytes(d) && ((uintptr_t)scratch & 15) == 0, DVQ_EWORKSPACE,
-                "dvq_conv2d_wgrad_oihw_x3: scratch too small (dvq_conv2d_wgrad_x3_scratch_bytes) or not 16-B aligned");
-    const int64_t xrows = d->N * (d->H >> d->upsample) * (d->W >> d->upsample), yrows = d->N * d->OH * d->OW;
-    const int64_t c8 = pad8(d->Cin), o8 = pad8(d->Cout);
-    auto up256 = [](int64_t v) { return (v + 255) & ~(int64_t)255; };
-    char* base = (char*)scratch;
-    char* xh = base;
-    char* xl = xh + up256(xrows * c8 * 2);
-    char* yh = xl + up256(xrows * c8 * 2);
-    char* yl = yh + up256(yrows * o8 * 2);
-    if (int e = dvq_split_bf16_planes((const float*)x, xh, xl, xrows, d->Cin, c8, stream)) return e;
-    if (int e = dvq_split_bf16_planes((const float*)dy, yh, yl, yrows, d->Cout, o8, stream)) return e;
-    dvq_conv_desc b = *d;
-    b.dtype = DVQ_BF16;
-    b.Cin = c8;
-    b.Cout = o8;
-    // 3 x 3 / stride 1 / pad 1 on the halo kernel: ONE launch over "3 N images" -- image n of plane triple (x_lo, dy_hi), (x_hi, dy_lo),
-    // (x_hi, dy_hi) -- instead of three launches with three folds of the partials (the planes of an operand are contiguous: eligible
-    // shapes have plane sizes that are multiples of 256 bytes).  Shapes the halo kernel does not take: three launches
-    if (halo_eligible(&b) && xl == xh + xrows * c8 * 2 && yl == yh + yrows * o8 * 2) {
-        const int rc = dvq_conv3x3_halo_wgrad_planes_try(xh, yh, grad_oihw, dbias, d->N, d->H, d->W, c8, o8, cin_real, cout_real, ohwi ? 0 : 1,
-                                                         d->upsample, (hipStream_t)stream);
-        if (rc < 0) return rc;
-        if (rc == 1) return DVQ_OK;
-    }
-    // small terms first; the bias gradient (column sums of dy) is the sum over BOTH dy planes, taken on the two launches that read x_hi
-    if (int e = dvq_conv2d_wgrad(&b, xl, yh, cin_real, cout_real, grad_oihw, nullptr, ohwi, nullptr, stream)) return e;
-    if (int e = dvq_conv2d_wgrad(&b, xh, yl, cin_real, cout_real, grad_oihw, dbias, ohwi, nullptr, stream)) return e;
-    return dvq_conv2d_wgrad(&b, xh, yh, cin_real, cout_real, grad_oihw, dbias, ohwi, nullptr, stream);
-}
-
-// -------------------------------------------------------------------------------------------------
-// fp32x3 forward / input gradient of the 3 x 3 / stride 1 / pad 1 convolutions on the HALO kernel (round 5).  The three products of the
-// split scheme are laid side by side on the channel axis of bf16 operands -- x' = [x_hi | x_lo | x_hi] and, per tap,
-// w' = [w_hi | w_hi | w_lo], 3 Cin channels -- so ONE launch of the bf16 halo kernel forms x_hi.w_hi + x_lo.w_hi + x_hi.w_lo in its fp32
-// accumulators, and its fp32-output instantiation (conv_halo.hip, OUT32) stores them unrounded, after the fp32 residual / gate /
-// activation.  Same products, same accumulation type as the in-kernel split of igemm_nt_glds_kernel<float, S3>, on a kernel that stages
-// every activation once for all 9 taps (the fp32 kernel: 200 - 250 TFLOP/s nominal, bound by its 2-us stages, section 3 of DESIGN.md).
-// Costs: one HBM-bound pass writes x' (4 B read + 6 B written per element), the weights are re-laid per call (Cout x 9 x Cin elements).
-// -------------------------------------------------------------------------------------------------
-namespace {
-
-// cs: channels of the streamed operand (x: Cin / dy: Cout), co: channels produced
-bool x3_halo_shape_ok(const dvq_conv_desc* d, int64_t cs, int64_t co) {
-    return d->dtype == DVQ_F32 && d->impl == DVQ_IMPL_AUTO && d->KH == 3 && d->KW == 3 && d->stride == 1 && d->pad_t == 1 && d->pad_l == 1 &&
-           d->OH == d->H && d->OW == d->W && d->H % 8 == 0 && d->W % 32 == 0 && cs % 64 == 0 && co >= 4 && co % 4 == 0 &&
-           d->N * d->H * d->W * (3 * cs > co ? 3 * cs : co) < (1ll << 31) && co * 27 * cs < (1ll << 31) && d->H * d->W * co * 4 < (1ll << 31);
-}
-
-inline int64_t up256(int64_t v) { return (v + 255) & ~(int64_t)255; }
-
-}  // namespace
-
-/* 1: dvq_conv2d_fwd_x3 (dgrad = 0) / dvq_conv2d_dgrad_x3 (dgrad = 1) take this descriptor */
-int dvq_conv3x3_x3_ok(const dvq_conv_desc* d, int dgrad) {
-    if (d == nullptr) return 0;
-    return dgrad ? x3_halo_shape_ok(d, d->Cout, d->Cin) : x3_halo_shape_ok(d, d->Cin, d->Cout);
-}
-
-int64_t dvq_conv3x3_x3_scratch_bytes(const dvq_conv_desc* d, int dgrad) {
-    if (!dvq_conv3x3_x3_ok(d, dgrad)) return 0;
-    const int64_t cs = dgrad ? d->Cout : d->Cin, co = dgrad ? d->Cin : d->Cout;
-    const int64_t rows = dgrad ? d->N * d->H * d->W : d->N * (d->H >> d->upsample) * (d->W >> d->upsample);
-    return up256(rows * 3 * cs * 2) + up256(co * 9 * 3 * cs * 2);
-}
-
-int dvq_conv2d_fwd_x3(const dvq_conv_desc* d, const void* x, const void* w, const float* bias, const void* residual, void* y, int act,
-                      void* scratch, int64_t scratch_bytes, dvq_stream_t stream) {
-    if (int e = conv_check(d, "dvq_conv2d_fwd_x3")) return e;
-    DVQ_REQUIRE(x && w && y && scratch, DVQ_EINVAL, "dvq_conv2d_fwd_x3: null pointer");
-    DVQ_REQUIRE(dvq_conv3x3_x3_ok(d, 0), DVQ_ESHAPE, "dvq_conv2d_fwd_x3: shape not eligible (dvq_conv3x3_x3_ok)");
-    DVQ_REQUIRE(act == DVQ_ACT_NONE || act == DVQ_ACT_RELU || act == DVQ_ACT_LRELU, DVQ_EINVAL, "dvq_conv2d_fwd_x3: bad act");
-    DVQ_REQUIRE(act == DVQ_ACT_NONE || residual == nullptr, DVQ_EINVAL, "dvq_conv2d_fwd_x3: activation and residual together");
-    DVQ_REQUIRE(scratch_bytes >= dvq_conv3x3_x3_scratch_bytes(d, 0) && ((uintptr_t)scratch & 15) == 0, DVQ_EWORKSPACE,
-                "dvq_conv2d_fwd_x3: scratch too small (dvq_conv3x3_x3_scratch_bytes) or not 16-B aligned");
-    const int64_t rows = d->N * (d->H >> d->upsample) * (d->W >> d->upsample);
-    char* xs = (char*)scratch;
-    char* wsx = xs + up256(rows * 3 * d->Cin * 2);
-    if (int e = split_concat3((const float*)x, xs, rows, d->Cin, 0, (hipStream_t)stream)) return e;
-    if (int e = split_concat3((const float*)w, wsx, d->Cout * 9, d->Cin, 1, (hipStream_t)stream)) return e;
-    const int rc = dvq_conv3x3_halo_out32_try(xs, wsx, bias, (const float*)residual, (float*)y, d->N, d->H, d->W, 3 * d->Cin, d->Cout, 0,
-                                              d->upsample, act_slope_of(act), 0, 0.f, (hipStream_t)stream);
-    if (rc < 0) return rc;
-    DVQ_REQUIRE(rc == 1, DVQ_ESHAPE, "dvq_conv2d_fwd_x3: the halo kernel refused the shape");
-    return DVQ_OK;
-}
-
-int dvq_conv2d_dgrad_x3(const dvq_conv_desc* d, const void* dy, const void* wt, void* dx, void* ws, const void* mask, int mask_act,
-                        void* scratch, int64_t scratch_bytes, dvq_stream_t stream) {
-    if (int e = conv_check(d, "dvq_conv2d_dgrad_x3")) return e;
-    DVQ_REQUIRE(mask == nullptr || ((mask_act == DVQ_ACT_RELU || mask_act == DVQ_ACT_LRELU) && !d->upsample), DVQ_EINVAL,
-                "dvq_conv2d_dgrad_x3: mask needs act in {relu, lrelu} and no folded upsample");
-    DVQ_REQUIRE(dy && wt && dx && scratch && (!d->upsample || ws), DVQ_EINVAL, "dvq_conv2d_dgrad_x3: null pointer");
-    DVQ_REQUIRE(dvq_conv3x3_x3_ok(d, 1), DVQ_ESHAPE, "dvq_conv2d_dgrad_x3: shape not eligible (dvq_conv3x3_x3_ok)");
-    DVQ_REQUIRE(scratch_bytes >= dvq_conv3x3_x3_scratch_bytes(d, 1) && ((uintptr_t)scratch & 15) == 0, DVQ_EWORKSPACE,
-                "dvq_conv2d_dgrad_x3: scratch too small (dvq_conv3x3_x3_scratch_bytes) or not 16-B aligned");
-    const int64_t rows = d->N * d->H * d->W;
-    char* ys = (char*)scratch;
-    char* wsx = ys + up256(rows * 3 * d->Cout * 2);
-    if (int e = split_concat3((const float*)dy, ys, rows, d->Cout, 0, (hipStream_t)stream)) return e;
-    if (int e = split_concat3((const float*)wt, wsx, d->Cin * 9, d->Cout, 1, (hipStream_t)stream)) return e;
-    const int rc = dvq_conv3x3_halo_out32_try(ys, wsx, nullptr, (const float*)mask, (float*)(d->upsample ? ws : dx), d->N, d->H, d->W,
-                                              3 * d->Cout, d->Cin, 1, 0, 1.f, mask != nullptr, act_slope_of(mask_act), (hipStream_t)stream);
-    if (rc < 0) return rc;
-    DVQ_REQUIRE(rc == 1, DVQ_ESHAPE, "dvq_conv2d_dgrad_x3: the halo kernel refused the shape");
-    return d->upsample ? dvq_sumpool2x2(ws, d->dtype, d->N, d->H / 2, d->W / 2, d->Cin, dx, stream) : DVQ_OK;
 }
 
 int dvq_gemm_nt(const void* A, const void* B, void* C, int dtype, int64_t M, int64_t N, int64_t K, int64_t lda,

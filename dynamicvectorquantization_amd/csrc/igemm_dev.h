@@ -1,6 +1,7 @@
-// Device pieces shared by the NT kernels (igemm_nt.hip) and the TN kernels (igemm_tn.hip): tile constants, the LDS swizzles, the MFMA
-// inner loops over one LDS stage, the fp32x3 operand split and the zero page.  Everything here has internal linkage: the build is not
-// relocatable device code, so each of the two files carries its own copy (of g_zero_page: 32 bytes).
+// Device pieces shared by the NT kernels (igemm_nt.hip), the TN kernels (igemm_tn.hip) and the fp32x3 plane kernels of the front end
+// (igemm.hip: split8_bf16): tile constants, the LDS swizzles, the MFMA inner loops over one LDS stage, the fp32x3 operand split and the
+// zero page.  Everything here has internal linkage: the build is not relocatable device code, so each of the three files carries its
+// own copy (of g_zero_page: 32 bytes).
 //
 // Tile 128x128, 256 threads = 2x2 waves, each wave 2x2 MFMA 32x32 tiles (64 accumulator VGPRs).
 // LDS rows are 128 B of K-contiguous data + 16 B pad (conflict-free ds_read_b128 for the MFMA

@@ -1009,7 +1009,7 @@ int dvq_set_fp32_split(int on) {
 
 const char* dvq_last_error(void) { return g_err; }
 const char* dvq_last_kernel(void) { return dvq_kernel_note; }
-int dvq_version(void) { return 123; }
+int dvq_version(void) { return 124; }
 long long dvq_unordered_launches(void) { return g_unordered.load(std::memory_order_relaxed); }
 
 int dvq_set_workspace(void* ptr, int64_t bytes) {

@@ -504,33 +504,36 @@ def _with_subpixel(d: ConvDesc) -> ConvDesc:
 ACT_NONE, ACT_SWISH, ACT_LRELU, ACT_RELU = 0, 1, 2, 3      # include/dvq_hip.h DVQ_ACT_*
 
 
-def _x3_halo(d: ConvDesc, t, dgrad: bool) -> bool:
-    """fp32x3 forward / input gradient of this call on the halo kernel (bf16 planes on the channel axis, fp32 output)?
-    DVQ_X3_HALO=0: stay on the fp32 kernel that splits at every fragment read (A/B switch)"""
-    return (t.dtype == torch.float32 and d.KH == 3 and d.stride == 1 and rt.switch("DVQ_X3_HALO") != "0" and
-            bool(lib().dvq_fp32_split()) and bool(lib().dvq_conv3x3_x3_ok(C.byref(d), int(dgrad))))
+PASS_FWD, PASS_DGRAD, PASS_WGRAD = 0, 1, 2      # include/dvq_hip.h DVQ_PASS_*
+
+
+def conv_scratch_bytes(d: ConvDesc, pass_: int) -> int:
+    """bytes of scratch with which the library runs this pass as a launch-level fp32x3 scheme (bf16 planes of the fp32 operands on the
+    bf16 kernels); 0: it has no such route for this descriptor in the current compute mode"""
+    return int(lib().dvq_conv2d_scratch_bytes(C.byref(d), pass_))
+
+
+def _x3_scratch(d: ConvDesc, pass_: int, on: bool, device):
+    """(scratch from the caching allocator or None, its size).  `on` False (A/B switches DVQ_X3_HALO=0, DVQ_X3_WGRAD_PLANES=0): no
+    scratch is passed and the pass stays on the fp32 kernel that splits at every fragment read"""
+    need = conv_scratch_bytes(d, pass_) if on else 0
+    return (torch.empty(need, dtype=torch.uint8, device=device) if need else None), need
 
 
 def conv2d_fwd(d: ConvDesc, x, w, bias, residual=None, gn_ss=None, out_stats=None, out_groups=0, act=ACT_NONE, subpixel=False):
     """subpixel: `w` is followed by the sub-pixel pack (subpixel_pack_views) and d is accepted by conv_subpixel_ok"""
     y = torch.empty(d.N, d.OH, d.OW, d.Cout, dtype=x.dtype, device=x.device)
     fl, nb = _conv_cost(d, x.element_size())
-    if gn_ss is None and out_stats is None and _x3_halo(d, x, False):
-        _tag(d, "fwd x3 halo" + ("+res" if residual is not None else "") + ("+act" if act != ACT_NONE else ""))
-        need = int(lib().dvq_conv3x3_x3_scratch_bytes(C.byref(d), 0))
-        scratch = torch.empty(need, dtype=torch.uint8, device=x.device)
-        _timed("conv_x3_halo", fl, nb, lambda: check(
-            lib().dvq_conv2d_fwd_x3(C.byref(d), _p(x), _p(w), _p(bias), _p(residual), _p(y), act, _p(scratch), need, _s()),
-            "dvq_conv2d_fwd_x3"))
-        return y
+    scratch, need = _x3_scratch(d, PASS_FWD, rt.switch("DVQ_X3_HALO") != "0", x.device)
     if _shape_tags():     # per-shape tables split the forward by epilogue / prologue variant (tools/debug/step_shapes.py)
-        _tag(d, "fwd" + ("+res" if residual is not None else "") + ("+gn" if gn_ss is not None else "") +
+        _tag(d, ("fwd x3 halo" if need else "fwd") + ("+res" if residual is not None else "") + ("+gn" if gn_ss is not None else "") +
              ("+st" if out_stats is not None else "") + ("+act" if act != ACT_NONE else ""))
     if out_stats is not None:
         ensure_workspace(x.device)        # per-tile statistics partials of the halo kernel
     dc = _with_subpixel(d) if subpixel else d
     _timed_conv(fl, nb, "dvq_conv2d_fwd", lambda:
-        lib().dvq_conv2d_fwd(C.byref(dc), _p(x), _p(w), _p(bias), _p(residual), _p(y), _p(gn_ss), _p(out_stats), out_groups, act, _s()))
+        lib().dvq_conv2d_fwd(C.byref(dc), _p(x), _p(w), _p(bias), _p(residual), _p(y), _p(gn_ss), _p(out_stats), out_groups, act,
+                             _p(scratch), need, _s()))
     return y
 
 
@@ -542,18 +545,11 @@ def conv2d_dgrad(d: ConvDesc, dy, wt, mask=None, mask_act=ACT_NONE, subpixel=Fal
     dx = torch.empty(d.N, sh, sw, d.Cin, dtype=dy.dtype, device=dy.device)
     ws = torch.empty(d.N, d.H, d.W, d.Cin, dtype=dy.dtype, device=dy.device) if d.upsample and not subpixel else None
     fl, nb = _conv_cost(d, dy.element_size())
-    if _x3_halo(d, dy, True):
-        _tag(d, "dgrad x3 halo")
-        need = int(lib().dvq_conv3x3_x3_scratch_bytes(C.byref(d), 1))
-        scratch = torch.empty(need, dtype=torch.uint8, device=dy.device)
-        _timed("conv_x3_halo", fl, nb, lambda: check(
-            lib().dvq_conv2d_dgrad_x3(C.byref(d), _p(dy), _p(wt), _p(dx), _p(ws), _p(mask), mask_act, _p(scratch), need, _s()),
-            "dvq_conv2d_dgrad_x3"))
-        return dx
-    _tag(d, "dgrad")
+    scratch, need = _x3_scratch(d, PASS_DGRAD, rt.switch("DVQ_X3_HALO") != "0", dy.device)
+    _tag(d, "dgrad x3 halo" if need else "dgrad")
     dc = _with_subpixel(d) if subpixel else d
     _timed_conv(fl, nb, "dvq_conv2d_dgrad", lambda:
-        lib().dvq_conv2d_dgrad(C.byref(dc), _p(dy), _p(wt), _p(dx), _p(ws), _p(mask), mask_act, _s()))
+        lib().dvq_conv2d_dgrad(C.byref(dc), _p(dy), _p(wt), _p(dx), _p(ws), _p(mask), mask_act, _p(scratch), need, _s()))
     return dx
 
 
@@ -612,11 +608,6 @@ def ensure_workspace(device):
         _workspace.update(dev=device, buf=buf)
 
 
-def _wgrad_x3_planes() -> bool:
-    """DVQ_X3_WGRAD_PLANES=0: fp32x3 weight gradients stay on the fp32 kernel that splits at every fragment read (A/B switch)"""
-    return rt.switch("DVQ_X3_WGRAD_PLANES") != "0"
-
-
 def split_bf16_planes(x2d, cout=None):
     """fp32 [rows, C] -> (hi, lo) bf16 [rows, cout]: hi = RNE(x), lo = RNE(x - hi); channels >= C are zero"""
     rows, c = x2d.shape
@@ -632,19 +623,11 @@ def conv2d_wgrad_oihw(d: ConvDesc, x, dy, cin_real, cout_real, grad_oihw, db=Non
     gn_ss: the fused GroupNorm+swish of the forward is re-applied to x inside the kernel"""
     fl, nb = _conv_cost(d, x.element_size())
     ensure_workspace(x.device)
-    if gn_ss is None and _wgrad_x3_planes() and x.dtype == torch.float32 and d.impl == 0 and bool(lib().dvq_fp32_split()):
-        # fp32x3: bf16 planes of both operands (scratch from the caching allocator), three launches of the bf16 weight-gradient kernels
-        _tag(d, "wgrad x3 planes")
-        need = int(lib().dvq_conv2d_wgrad_x3_scratch_bytes(C.byref(d)))
-        scratch = torch.empty(need, dtype=torch.uint8, device=x.device)
-        _timed("conv_wgrad_x3_planes", fl, nb, lambda: check(
-            lib().dvq_conv2d_wgrad_oihw_x3(C.byref(d), _p(x), _p(dy), cin_real, cout_real, _praw(grad_oihw), _p(db),
-                                           int(is_ohwi(grad_oihw)), _p(scratch), need, _s()), "dvq_conv2d_wgrad_oihw_x3"))
-        return
-    _tag(d, "wgrad")
+    scratch, need = _x3_scratch(d, PASS_WGRAD, rt.switch("DVQ_X3_WGRAD_PLANES") != "0", x.device)
+    _tag(d, "wgrad x3 planes" if need else "wgrad")
     _timed_conv(fl, nb, "dvq_conv2d_wgrad", lambda:
         lib().dvq_conv2d_wgrad(C.byref(d), _p(x), _p(dy), cin_real, cout_real, _praw(grad_oihw), _p(db),
-                               int(is_ohwi(grad_oihw)), _p(gn_ss), _s()))
+                               int(is_ohwi(grad_oihw)), _p(gn_ss), _p(scratch), need, _s()))
 
 
 def set_deterministic(on: bool):

@@ -25,8 +25,8 @@ _impl = _lib.IMPL_AUTO
 # docs/design/03-kernels.md too; tests/test_host_cpu.py pins both.
 SWITCHES = {
     "DVQ_FUSE_GN": ("0", "1: GroupNorm+swish inside the consuming 3x3 conv on taped forwards too"),
-    "DVQ_X3_HALO": ("1", "0: fp32x3 3x3 forward / input gradient on the fp32 kernel that splits at every fragment read"),
-    "DVQ_X3_WGRAD_PLANES": ("1", "0: fp32x3 weight gradients on the fp32 kernel that splits at every fragment read"),
+    "DVQ_X3_HALO": ("1", "0: fp32x3 3x3 forward / input gradient pass no scratch: the fp32 kernel that splits at every fragment read"),
+    "DVQ_X3_WGRAD_PLANES": ("1", "0: fp32x3 weight gradients pass no scratch: the fp32 kernel that splits at every fragment read"),
     "DVQ_NO_FUSED_ATTN": ("0", "1: causal attention as per-head GEMMs + softmax instead of the fused kernels"),
     "DVQ_NO_FUSED_ATTNBLOCK": ("0", "1: AttnBlock on GEMMs + softmax (stores the [B,N,N] probabilities)"),
     "DVQ_QKV_FUSED": ("1", "0: key / query / value as three Linear layers instead of one GEMM"),

@@ -44,9 +44,14 @@ enum { DVQ_OK = 0, DVQ_EINVAL = -1, DVQ_ESHAPE = -2, DVQ_EARCH = -3, DVQ_ELAUNCH
 const char* dvq_last_error(void);
 /* Kernel family the calling thread's last dvq_conv2d_* / dvq_gemm_* call landed on: the `__global__` name of its primary kernel as
  * written in csrc ("conv3x3_halo_kernel", "conv_nt_pipe_kernel", ...; no template arguments, no fold / reduce / transpose helpers), noted
- * at the dispatch branch that launches it.  "" when nothing was noted (those entry points clear it first).  For timing labels. */
+ * at the dispatch branch that launches it.  "" when nothing was noted (those entry points clear it first).  For timing labels.
+ * Two values are ROUTE labels, not `__global__` names: "conv_x3_halo" and "conv_wgrad_x3_planes", the fp32x3 launch-level schemes of
+ * dvq_conv2d_scratch_bytes (plane passes + the bf16 kernels behind them). */
 const char* dvq_last_kernel(void);
-int dvq_version(void);     /* 123: struct dvq_token_rule, DVQ_TOKEN_RULE_MAXV: dvq_sample_constrained, dvq_sample_guided, dvq_codec_tables, dvq_codec_record and
+int dvq_version(void);     /* 124: dvq_conv2d_fwd / _dgrad / _wgrad take (scratch, scratch_bytes) and route the fp32x3 launch-level schemes themselves;
+                            * dvq_conv2d_scratch_bytes replaces dvq_conv3x3_x3_ok, dvq_conv3x3_x3_scratch_bytes and dvq_conv2d_wgrad_x3_scratch_bytes;
+                            * dvq_conv2d_fwd_x3, dvq_conv2d_dgrad_x3 and dvq_conv2d_wgrad_oihw_x3 are gone;
+                            * 123: struct dvq_token_rule, DVQ_TOKEN_RULE_MAXV: dvq_sample_constrained, dvq_sample_guided, dvq_codec_tables, dvq_codec_record and
                             * dvq_codec_decode_step take the constraint rule as one block instead of nine loose arguments;
                             * 122: dvq_attn_causal_fwd / _bwd take the row pitch ldqkv (dvq_attn_causal_fwd_ld / _bwd_ld are gone); dvq_attn_causal_scratch_bytes
                             * is what the kernels that run need (0 forward at head sizes 128 / 256: NULL scratch); dvq_attn_full_scratch_bytes is gone;
@@ -243,7 +248,8 @@ enum { DVQ_ACT_NONE = 0, DVQ_ACT_SWISH = 1, DVQ_ACT_LRELU = 2, DVQ_ACT_RELU = 3 
  * Cin % 64 == 0; DVQ_ESHAPE elsewhere): gn_scale_shift (fp32 [N][Cin][2], from dvq_gn_scale_shift) applies GroupNorm + swish to the
  * INPUT inside the kernel (ResnetBlock's norm -> swish -> conv, model.py:119-129, without materialising the activation);
  * out_stats (fp64 [N][out_groups][2], accumulated) receives sum / sum of squares of the OUTPUT per group, i.e. the
- * statistics pass of the next GroupNorm.  Either may be NULL. */
+ * statistics pass of the next GroupNorm.  Either may be NULL.
+ * scratch, scratch_bytes (here, in dvq_conv2d_dgrad and in dvq_conv2d_wgrad; NULL, 0 is always legal): see dvq_conv2d_scratch_bytes. */
 int dvq_conv3x3_fused_ok(const dvq_conv_desc* d);
 /* Nearest x2 upsample + 3x3 as four 2x2 sub-pixel convolutions.  The upsampled image holds every source pixel four times, so an output
  * pixel of parity class (py, px) reads 2 x 2 distinct source pixels: out[2i+py][2j+px] = sum_{a,b in {0,1}} Weff[py][px][a][b] .
@@ -256,29 +262,26 @@ int dvq_conv3x3_fused_ok(const dvq_conv_desc* d);
  * gradient, fp32 and fp32x3 keep upsample == 1. */
 int dvq_conv3x3_subpixel_ok(const dvq_conv_desc* d);
 int dvq_conv2d_fwd(const dvq_conv_desc* d, const void* x, const void* w, const float* bias, const void* residual, void* y,
-                   const float* gn_scale_shift, double* out_stats, int out_groups, int act, dvq_stream_t stream);
-/* fp32x3 weight gradient (dvq_set_fp32_split) at launch level: x / dy fp32 (descriptor dtype DVQ_F32, channels padded to 4) are split
- * into bf16 planes hi = RNE(v), lo = RNE(v - hi) in `scratch` (>= dvq_conv2d_wgrad_x3_scratch_bytes(d), 16-B aligned; channels re-padded
- * to 8) and the gradient is accumulated by THREE launches of the bf16 weight-gradient kernels, x_lo.dy_hi + x_hi.dy_lo + x_hi.dy_hi --
- * the same three products and fp32 accumulation the in-kernel split forms, at the bf16 kernels' speed.  Arguments as
- * dvq_conv2d_wgrad; any convolution geometry the bf16 path takes.  dvq_split_bf16_planes: x fp32 [rows][cin] -> two bf16
- * [rows][cout] tensors (cin % 4 == 0, cout % 8 == 0, cout >= cin; channels >= cin are zero). */
+                   const float* gn_scale_shift, double* out_stats, int out_groups, int act, void* scratch, int64_t scratch_bytes,
+                   dvq_stream_t stream);
+/* fp32x3 at LAUNCH level (dvq_set_fp32_split on, descriptor dtype DVQ_F32, impl DVQ_IMPL_AUTO): the three passes below take `scratch`
+ * and run the split scheme's three products on the bf16 kernels, from bf16 planes hi = RNE(v), lo = RNE(v - hi) written into it.
+ *   DVQ_PASS_FWD / DVQ_PASS_DGRAD: 3 x 3, stride 1, pad 1 with H % 8 == 0, W % 32 == 0, streamed channels % 64 == 0 and produced channels
+ *     a multiple of 4 (>= 4).  The planes lie side by side on the channel axis ([x_hi | x_lo | x_hi] against [w_hi | w_hi | w_lo]); ONE
+ *     launch of the bf16 halo kernel with fp32 residual / gate / activation and fp32 output.  Not with gn_scale_shift or out_stats.
+ *   DVQ_PASS_WGRAD: any geometry the bf16 weight gradient takes (channels re-padded from 4 to 8).  x_lo.dy_hi + x_hi.dy_lo + x_hi.dy_hi
+ *     as ONE halo launch over the planes, or three launches of the bf16 weight-gradient path.  Not with gn_scale_shift.
+ * dvq_conv2d_scratch_bytes: the bytes that route wants under the CURRENT dvq_fp32_split() state; 0 when no route wants scratch (bf16
+ * operands, the split off, impl != DVQ_IMPL_AUTO, a FWD / DGRAD shape outside the list above).  Routing, where the query is not 0:
+ *   scratch != NULL: the launch-level scheme.  scratch_bytes below the query or a pointer that is not 16-B aligned: DVQ_EWORKSPACE from
+ *     the argument check, before any launch.
+ *   scratch == NULL: the route that needs none (the fp32 kernel that splits at every fragment read).  A legal choice, not an error.
+ * Where the query is 0 both arguments are ignored.
+ * dvq_split_bf16_planes: x fp32 [rows][cin] -> two bf16 [rows][cout] tensors (cin % 4 == 0, cout % 8 == 0, cout >= cin; channels >= cin
+ * are zero). */
+enum { DVQ_PASS_FWD = 0, DVQ_PASS_DGRAD = 1, DVQ_PASS_WGRAD = 2 };
+int64_t dvq_conv2d_scratch_bytes(const dvq_conv_desc* d, int pass);
 int dvq_split_bf16_planes(const float* x, void* hi, void* lo, int64_t rows, int64_t cin, int64_t cout, dvq_stream_t stream);
-int64_t dvq_conv2d_wgrad_x3_scratch_bytes(const dvq_conv_desc* d);
-int dvq_conv2d_wgrad_oihw_x3(const dvq_conv_desc* d, const void* x, const void* dy, int64_t cin_real, int64_t cout_real,
-                             float* grad_oihw, float* dbias, int ohwi, void* scratch, int64_t scratch_bytes, dvq_stream_t stream);
-/* fp32x3 forward / input gradient of a 3 x 3, stride 1, pad 1 convolution on the halo kernel: operands fp32 (descriptor dtype DVQ_F32,
- * arguments as dvq_conv2d_fwd and dvq_conv2d_dgrad), split into bf16 planes laid side by side on the channel
- * axis ([x_hi | x_lo | x_hi] against [w_hi | w_hi | w_lo]) in `scratch`, ONE launch of the bf16 halo kernel, fp32 residual / gate /
- * activation and fp32 output -- the three products and the fp32 accumulation of dvq_set_fp32_split at the halo kernel's speed.
- * dvq_conv3x3_x3_ok(d, dgrad): shapes taken (H % 8 == 0, W % 32 == 0, streamed channels % 64 == 0, produced channels > 32);
- * scratch >= dvq_conv3x3_x3_scratch_bytes(d, dgrad), 16-B aligned.  act != DVQ_ACT_NONE excludes a residual. */
-int dvq_conv3x3_x3_ok(const dvq_conv_desc* d, int dgrad);
-int64_t dvq_conv3x3_x3_scratch_bytes(const dvq_conv_desc* d, int dgrad);
-int dvq_conv2d_fwd_x3(const dvq_conv_desc* d, const void* x, const void* w, const float* bias, const void* residual, void* y, int act,
-                      void* scratch, int64_t scratch_bytes, dvq_stream_t stream);
-int dvq_conv2d_dgrad_x3(const dvq_conv_desc* d, const void* dy, const void* wt, void* dx, void* ws, const void* mask, int mask_act,
-                        void* scratch, int64_t scratch_bytes, dvq_stream_t stream);
 /* scale_shift[n][c] = {rstd*gamma, beta - mean*rstd*gamma} from the fp64 statistics; mean_rstd (fp32 [N][G][2]) optional */
 int dvq_gn_scale_shift(const double* stats, const float* gamma, const float* beta, int64_t N, int64_t HW, int64_t C, int G,
                        float eps, float* scale_shift, float* mean_rstd, dvq_stream_t stream);
@@ -290,7 +293,7 @@ int dvq_gn_scale_shift(const double* stats, const float* gamma, const float* bet
  * mask (may be NULL): dgrad through the conv AND the activation that produced the conv's input: mask = that activation's OUTPUT
  * (same shape as dx); dx = dgrad * (mask > 0 ? 1 : slope(mask_act)), mask_act DVQ_ACT_RELU / _LRELU, no folded upsample. */
 int dvq_conv2d_dgrad(const dvq_conv_desc* d, const void* dy, const void* wt, void* dx, void* ws, const void* mask, int mask_act,
-                     dvq_stream_t stream);
+                     void* scratch, int64_t scratch_bytes, dvq_stream_t stream);
 
 /* Weight gradient, ACCUMULATED straight into the fp32 gradient of the reference-layout parameter (zero it first; no packed
  * intermediate, no unpack pass); d->Cin / d->Cout are the padded channel counts of x / dy, cin_real / cout_real those of the parameter.
@@ -300,7 +303,7 @@ int dvq_conv2d_dgrad(const dvq_conv_desc* d, const void* dy, const void* wt, voi
  * dbias: fp32 [cout_real], accumulated, may be NULL.  gn_scale_shift (may be NULL; shapes accepted by dvq_conv3x3_fused_ok): the
  * GroupNorm + swish the forward fused into its prologue, re-applied to x inside the kernel. */
 int dvq_conv2d_wgrad(const dvq_conv_desc* d, const void* x, const void* dy, int64_t cin_real, int64_t cout_real, float* grad,
-                     float* dbias, int ohwi, const float* gn_scale_shift, dvq_stream_t stream);
+                     float* dbias, int ohwi, const float* gn_scale_shift, void* scratch, int64_t scratch_bytes, dvq_stream_t stream);
 
 /* Pack every conv weight of a model in ONE launch.  table_dev: device array of n_entries records
  * { const float* master; void* w; void* wt; int64 Cout, Cin, taps, Cin_p, Cout_p, begin, dtype } where `begin` is

@@ -620,8 +620,8 @@ def test_fp32_split_weight_gradient_upsampled_input(dev, monkeypatch):
 
 
 def test_fp32_split_halo_variants(dev, monkeypatch):
-    """fp32x3 forward / input gradient on the halo kernel (bf16 planes on the channel axis, fp32 output: dvq_conv2d_fwd_x3 /
-    dvq_conv2d_dgrad_x3) against float64 and against the in-kernel split (DVQ_X3_HALO=0): residual, fused ReLU / LeakyReLU, gated input
+    """fp32x3 forward / input gradient on the halo kernel (bf16 planes on the channel axis, fp32 output: dvq_conv2d_fwd /
+    dvq_conv2d_dgrad with scratch) against float64 and against the in-kernel split (DVQ_X3_HALO=0): residual, fused ReLU / LeakyReLU, gated input
     gradient, folded nearest x2 upsample, 64- / 128- / 192-channel outputs (one and two staging rounds, a partial channel block)"""
     from dynamicvectorquantization_amd import kernels as K
     from dynamicvectorquantization_amd import runtime as rt
@@ -635,7 +635,7 @@ def test_fp32_split_halo_variants(dev, monkeypatch):
             x = torch.randn(n, h >> up, w_ >> up, cin, device=dev)
             d = conv._desc(x)
             monkeypatch.setenv("DVQ_X3_HALO", "1")
-            assert K._x3_halo(d, x, False) and K._x3_halo(d, x, True), (cin, cout, h, w_, n, up, rt.fp32_split(), d.impl, d.H, d.W, d.OH, d.OW, d.Cin, d.Cout, d.pad_t)
+            assert K.conv_scratch_bytes(d, K.PASS_FWD) > 0 and K.conv_scratch_bytes(d, K.PASS_DGRAD) > 0, (cin, cout, h, w_, n, up, rt.fp32_split(), d.impl, d.H, d.W, d.OH, d.OW, d.Cin, d.Cout, d.pad_t)
             w, wt, bias = conv.packed(torch.float32)
             res = torch.randn(n, h, w_, cout, device=dev)
             dy = torch.randn(n, h, w_, cout, device=dev)
@@ -684,7 +684,7 @@ def test_fp32_split_halo_thin_output(dev, monkeypatch):
             x = torch.randn(n, h, w_, cin, device=dev)
             d = conv._desc(x)
             monkeypatch.setenv("DVQ_X3_HALO", "1")
-            assert K._x3_halo(d, x, False), (cin, cout)
+            assert K.conv_scratch_bytes(d, K.PASS_FWD) > 0, (cin, cout)
             w, wt, bias = conv.packed(torch.float32)
             yr = F.conv2d(x.double().permute(0, 3, 1, 2), conv.weight.detach().double(), conv.bias.detach().double(), padding=1).permute(0, 2, 3, 1)
             out = {}

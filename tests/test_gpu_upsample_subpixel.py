@@ -113,7 +113,7 @@ def test_input_gradient_values_without_workspace(dev, key):
     d2 = K._with_subpixel(c["d"])
     dx2 = torch.empty_like(dx)
     s = torch.cuda.current_stream().cuda_stream
-    rc = K.lib().dvq_conv2d_dgrad(C.byref(d2), c["g"].data_ptr(), c["wtbuf"].data_ptr(), dx2.data_ptr(), None, None, 0, s)
+    rc = K.lib().dvq_conv2d_dgrad(C.byref(d2), c["g"].data_ptr(), c["wtbuf"].data_ptr(), dx2.data_ptr(), None, None, 0, None, 0, s)
     assert rc == 0, K.lib().dvq_last_error()
     assert torch.equal(dx, dx2)
 

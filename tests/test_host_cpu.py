@@ -526,7 +526,7 @@ def test_one_library_without_probe_code():
     lib = _lib.load()
     assert not hasattr(lib, "dvq_halo_trace_read")
     assert not hasattr(lib, "dvq_conv3x3_halo2_try")
-    assert lib.dvq_version() == 123
+    assert lib.dvq_version() == 124
 
 
 # the environment names the Python package reads that are paths or build inputs, not switches: read where they are used

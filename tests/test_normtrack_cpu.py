@@ -175,7 +175,7 @@ def test_library_exports_the_segment_kernels():
     for n in ("dvq_segment_stats", "dvq_segment_stats_workspace_bytes", "dvq_segment_stats_state_bytes", "dvq_segment_plan_bytes",
               "dvq_segment_plan_build", "dvq_copy_f32_armed"):
         assert n in _lib.SIGNATURES and hasattr(lib, n)
-    assert lib.dvq_version() == 123
+    assert lib.dvq_version() == 124
     from dynamicvectorquantization_amd import kernels as K
     c = K.GRAD_SQNORM_CHUNK                                          # one chunk length for both reductions
     assert lib.dvq_grad_sqnorm_workspace_bytes(c) == 8 and lib.dvq_grad_sqnorm_workspace_bytes(c + 1) == 16

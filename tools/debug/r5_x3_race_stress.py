@@ -1,5 +1,5 @@
 #!/usr/bin/env python3
-"""Determinism stress of the fp32x3 halo path (dvq_conv2d_fwd_x3 / dvq_conv2d_dgrad_x3: pre-pass, weight re-layout, halo main loop on
+"""Determinism stress of the fp32x3 halo path (dvq_conv2d_fwd / dvq_conv2d_dgrad with scratch: pre-pass, weight re-layout, halo main loop on
 3 Cin channels, fp32-output epilogue): forward (+ residual, + ReLU) and input gradient (+ gate) have no atomics, so every launch on the
 same operands must reproduce the first result bit for bit.  NPROC processes share the GPU (round 4's LDS-DMA race only showed once a
 second process competed for the CUs); full-size shapes, REPS launches each.
@@ -39,7 +39,7 @@ def worker(rank):
         dy = torch.randn(B, H, H, Cout, device=dev)
         m = torch.randn(B, H, H, Cin, device=dev)
         d = conv._desc(x)
-        assert K._x3_halo(d, x, False) and K._x3_halo(d, x, True)
+        assert K.conv_scratch_bytes(d, K.PASS_FWD) > 0 and K.conv_scratch_bytes(d, K.PASS_DGRAD) > 0
         check(f"x3 halo fwd         B{B} {H}x{H} {Cin}->{Cout}", lambda: K.conv2d_fwd(d, x, w, bias))
         check(f"x3 halo fwd+res     B{B} {H}x{H} {Cin}->{Cout}", lambda: K.conv2d_fwd(d, x, w, bias, r))
         check(f"x3 halo fwd+relu    B{B} {H}x{H} {Cin}->{Cout}", lambda: K.conv2d_fwd(d, x, w, bias, act=K.ACT_RELU))
