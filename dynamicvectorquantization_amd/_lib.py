@@ -206,8 +206,11 @@ SIGNATURES = {
     "dvq_recon_metrics_workspace_bytes": (sz, [i64, i64, i64]),
     "dvq_recon_metrics": (i32, [vp, vp, i64, i64, i64, i32, vp, vp, vp, vp, sz, vp]),
     "dvq_code_histogram": (i32, [vp, vp, i64, i64, i64, i64, i64, i64, i32, vp, vp, vp, vp]),
+    "dvq_recon_cells_workspace_bytes": (sz, [i64, i64, i64, i64, i64]),
+    "dvq_recon_cells": (i32, [vp, vp, i64, i64, i64, i64, i64, i32, vp, vp, sz, vp]),
     "dvq_token_nll": (i32, [vp, i32, i64, i64, i64, vp, i64, vp, vp, vp]),
     "dvq_nll_segment_sums": (i32, [vp, vp, i64, i64, i64, vp, vp]),
+    "dvq_nll_cell_sums": (i32, [vp, vp, vp, i64, i64, i64, i32, i32, i32, i32, vp, vp, vp]),
     "dvq_tokens_pack": (i32, [vp, vp, i64, i32, i32, i64, vp, vp, vp, vp, vp]),
     "dvq_tokens_unpack": (i32, [vp, vp, i64, i32, i32, i32, i64, i64, i64, i64, i64, i64, i64, i64, vp, vp, vp, vp, vp]),
     "dvq_vq_trained_prep_bytes": (sz, [i64, i64]),

@@ -9,6 +9,8 @@
 // moment maps, and writes its three sums (fp64) into a slab.  A fold kernel adds the slab of each image in a fixed order: no float
 // atomics, so the per-image values are bitwise reproducible and do not depend on the other images of the batch.
 // dvq_code_histogram: one workgroup per image, integer atomics only (exact, order-independent).
+// dvq_recon_cells: the same staging and moment arithmetic with tiles that follow an hg x wg cell grid; the per-pixel values are folded
+// per cell piece by one owner each, then per cell over channels and parts (docs/design/30-cell-maps.md).
 #include "dvq_common.h"
 
 #include <math.h>
@@ -170,6 +172,205 @@ __global__ __launch_bounds__(DVQ_WAVE) void recon_metrics_fold_kernel(const doub
     }
 }
 
+// ---- per-cell maps (docs/design/30-cell-maps.md) ---------------------------------------------------------------------------------
+// The image is cut into hg x wg cells of ch x cw pixels.  Per axis the tiles follow the cells: a cell no longer than the tile edge T
+// shares a tile with T / c - 1 neighbours (cpt cells per tile), a longer one is cut into `sub` parts of at most T pixels.  A tile
+// therefore holds whole cells or one part of one cell per axis, and a cell's value is the sum of sub_r * sub_c * 3 slab entries.
+struct CellAxis {
+    int cell;       // pixels per cell
+    int cpt;        // cells per tile
+    int sub;        // parts per cell
+    int ntile;      // tiles on the axis
+};
+
+struct CellGeom {
+    CellAxis r, c;
+    int hg, wg;
+};
+
+template <bool VEC>
+__global__ __launch_bounds__(NT) void recon_cells_tile_kernel(const float* __restrict__ x, const float* __restrict__ y, int64_t H,
+                                                               int64_t W, CellGeom gm, int quantize_u8, Gauss11 gw,
+                                                               double* __restrict__ slab) {
+    // the same staging and fp32 moment arithmetic as recon_metrics_tile_kernel; the per-pixel values stay in LDS and are folded per
+    // cell piece in a fixed order (row segments, then the rows of a piece) instead of per tile
+    __shared__ __attribute__((aligned(16))) float simg[2][RH][RWP];     // x and y (v01 - 0.5); later the SSIM map of the tile
+    __shared__ __attribute__((aligned(16))) float hp[5][RH][TW];        // first the fp64 error maps + row partials, then the moments
+    static_assert(sizeof(float) * 5 * RH * TW >= sizeof(double) * 4 * TH * TW, "error maps and row partials share hp");
+    static_assert(sizeof(float) * 2 * RH * RWP >= sizeof(float) * TH * TW, "the SSIM map shares the staged images");
+    float(*sx)[RWP] = simg[0];
+    float(*sy)[RWP] = simg[1];
+    double(*dsq)[TW] = reinterpret_cast<double(*)[TW]>(&hp[0][0][0]);
+    double(*dab)[TW] = dsq + TH;
+    double(*rp0)[TW] = dab + TH;                // row partials [TH][pieces per row]
+    double(*rp1)[TW] = rp0 + TH;
+    float(*ssm)[TW] = reinterpret_cast<float(*)[TW]>(&simg[0][0][0]);
+    const int64_t blk = blockIdx.x;
+    const int ntiles = gm.r.ntile * gm.c.ntile;
+    const int tile = (int)(blk % ntiles);
+    const int64_t plane = blk / ntiles;         // b * 3 + c
+    const int tr = tile / gm.c.ntile, tc = tile % gm.c.ntile;
+    // origin and owned extent of the tile on each axis
+    const int r0 = gm.r.sub == 1 ? tr * gm.r.cpt * gm.r.cell : (tr / gm.r.sub) * gm.r.cell + (tr % gm.r.sub) * TH;
+    const int c0 = gm.c.sub == 1 ? tc * gm.c.cpt * gm.c.cell : (tc / gm.c.sub) * gm.c.cell + (tc % gm.c.sub) * TW;
+    const int er = gm.r.sub == 1 ? min(gm.r.cpt * gm.r.cell, (int)H - r0) : min(TH, gm.r.cell - (tr % gm.r.sub) * TH);
+    const int ec = gm.c.sub == 1 ? min(gm.c.cpt * gm.c.cell, (int)W - c0) : min(TW, gm.c.cell - (tc % gm.c.sub) * TW);
+    const int ph = min(gm.r.cell, TH), pw = min(gm.c.cell, TW);          // piece = a cell's share of the tile
+    const int npr = (er + ph - 1) / ph, npc = (ec + pw - 1) / pw;
+    const int ppt = gm.r.cpt * gm.c.cpt;
+    double* out = slab + blk * ppt * 3;
+    const float* xp = x + plane * H * W;
+    const float* yp = y + plane * H * W;
+    const int tid = threadIdx.x;
+
+    auto stage = [&](int lr, int lc, float xv, float yv) {
+        const double ax = to01(xv, quantize_u8), ay = to01(yv, quantize_u8);
+        sx[lr][lc] = (float)(ax - 0.5);
+        sy[lr][lc] = (float)(ay - 0.5);
+        if (lr < er && lc < ec) {               // owned pixel
+            const double d = ax - ay;
+            dsq[lr][lc] = d * d;
+            dab[lr][lc] = fabs((double)xv - (double)yv);
+        }
+    };
+    if (VEC) {
+        constexpr int QW = RWP / 4;
+        for (int t = tid; t < RH * QW; t += NT) {
+            const int lr = t / QW, lc = (t % QW) * 4;
+            const int64_t gr = r0 + lr, gc = c0 + lc;
+            if (gr < H && gc < W) {             // W % 4 == 0 and c0 % 4 == 0: the whole float4 lies inside the row
+                const float4 a = *reinterpret_cast<const float4*>(xp + gr * W + gc);
+                const float4 b = *reinterpret_cast<const float4*>(yp + gr * W + gc);
+                stage(lr, lc + 0, a.x, b.x);
+                stage(lr, lc + 1, a.y, b.y);
+                stage(lr, lc + 2, a.z, b.z);
+                stage(lr, lc + 3, a.w, b.w);
+            } else {
+                *reinterpret_cast<float4*>(&sx[lr][lc]) = make_float4(0.f, 0.f, 0.f, 0.f);
+                *reinterpret_cast<float4*>(&sy[lr][lc]) = make_float4(0.f, 0.f, 0.f, 0.f);
+            }
+        }
+    } else {
+        for (int t = tid; t < RH * RW; t += NT) {
+            const int lr = t / RW, lc = t % RW;
+            const int64_t gr = r0 + lr, gc = c0 + lc;
+            if (gr < H && gc < W) {
+                stage(lr, lc, xp[gr * W + gc], yp[gr * W + gc]);
+            } else {
+                sx[lr][lc] = 0.f;
+                sy[lr][lc] = 0.f;
+            }
+        }
+    }
+    __syncthreads();
+    // squared and absolute error: row segment of every piece, then the piece's rows top to bottom
+    for (int t = tid; t < er * npc; t += NT) {
+        const int i = t / npc, q = t % npc;
+        const int j1 = min((q + 1) * pw, ec);
+        double a = 0.0, b = 0.0;
+        for (int j = q * pw; j < j1; ++j) {
+            a += dsq[i][j];
+            b += dab[i][j];
+        }
+        rp0[i][q] = a;
+        rp1[i][q] = b;
+    }
+    __syncthreads();
+    for (int t = tid; t < npr * npc; t += NT) {
+        const int p = t / npc, q = t % npc;
+        const int i1 = min((p + 1) * ph, er);
+        double a = 0.0, b = 0.0;
+        for (int i = p * ph; i < i1; ++i) {
+            a += rp0[i][q];
+            b += rp1[i][q];
+        }
+        out[(p * gm.c.cpt + q) * 3 + 0] = a;
+        out[(p * gm.c.cpt + q) * 3 + 1] = b;
+    }
+    __syncthreads();                            // hp is about to hold the moments
+    for (int t = tid; t < RH * TW; t += NT) {   // horizontal pass over every staged row
+        const int r = t / TW, j = t % TW;
+        float mx = 0.f, my = 0.f, mxx = 0.f, myy = 0.f, mxy = 0.f;
+#pragma unroll
+        for (int k = 0; k < 11; ++k) {
+            const float a = sx[r][j + k], b = sy[r][j + k], g = gw.g[k];
+            mx += g * a;
+            my += g * b;
+            mxx += g * (a * a);
+            myy += g * (b * b);
+            mxy += g * (a * b);
+        }
+        hp[0][r][j] = mx;
+        hp[1][r][j] = my;
+        hp[2][r][j] = mxx;
+        hp[3][r][j] = myy;
+        hp[4][r][j] = mxy;
+    }
+    __syncthreads();                            // the staged images are free: the SSIM map takes their place
+    const int64_t Ho = H - HALO, Wo = W - HALO;
+    constexpr float C1 = 0.01f * 0.01f, C2 = 0.03f * 0.03f;
+    for (int t = tid; t < TH * TW; t += NT) {   // vertical pass + the SSIM value of every owned valid window (0 elsewhere)
+        const int i = t / TW, j = t % TW;
+        float v = 0.f;
+        if (i < er && j < ec && r0 + i < Ho && c0 + j < Wo) {
+            float m[5] = {0.f, 0.f, 0.f, 0.f, 0.f};
+#pragma unroll
+            for (int k = 0; k < 11; ++k) {
+                const float g = gw.g[k];
+#pragma unroll
+                for (int q = 0; q < 5; ++q) m[q] += g * hp[q][i + k][j];
+            }
+            const float vx = m[2] - m[0] * m[0], vy = m[3] - m[1] * m[1], cxy = m[4] - m[0] * m[1];
+            const float ux = m[0] + 0.5f, uy = m[1] + 0.5f;
+            const float num = (2.f * ux * uy + C1) * (2.f * cxy + C2);
+            const float den = (ux * ux + uy * uy + C1) * (vx + vy + C2);
+            v = num / den;
+        }
+        ssm[i][j] = v;
+    }
+    __syncthreads();                            // every read of hp is done: the row partials return to it
+    for (int t = tid; t < er * npc; t += NT) {
+        const int i = t / npc, q = t % npc;
+        const int j1 = min((q + 1) * pw, ec);
+        double a = 0.0;
+        for (int j = q * pw; j < j1; ++j) a += (double)ssm[i][j];
+        rp0[i][q] = a;
+    }
+    __syncthreads();
+    for (int t = tid; t < npr * npc; t += NT) {
+        const int p = t / npc, q = t % npc;
+        const int i1 = min((p + 1) * ph, er);
+        double a = 0.0;
+        for (int i = p * ph; i < i1; ++i) a += rp0[i][q];
+        out[(p * gm.c.cpt + q) * 3 + 2] = a;
+    }
+}
+
+// one thread per (image, cell): its 3 * sub_r * sub_c slab entries, channel by channel, part by part
+__global__ __launch_bounds__(NT) void recon_cells_fold_kernel(const double* __restrict__ slab, int64_t B, CellGeom gm,
+                                                              double* __restrict__ cells) {
+    const int64_t e = (int64_t)blockIdx.x * NT + threadIdx.x;
+    const int64_t ncell = (int64_t)gm.hg * gm.wg;
+    if (e >= B * ncell) return;
+    const int64_t b = e / ncell;
+    const int gi = (int)((e % ncell) / gm.wg), gj = (int)(e % gm.wg);
+    const int ppt = gm.r.cpt * gm.c.cpt;
+    const int64_t ntiles = (int64_t)gm.r.ntile * gm.c.ntile;
+    double a[3] = {0.0, 0.0, 0.0};
+    for (int c = 0; c < 3; ++c)
+        for (int sr = 0; sr < gm.r.sub; ++sr)
+            for (int sc = 0; sc < gm.c.sub; ++sc) {
+                const int tr = gm.r.sub == 1 ? gi / gm.r.cpt : gi * gm.r.sub + sr;
+                const int tc = gm.c.sub == 1 ? gj / gm.c.cpt : gj * gm.c.sub + sc;
+                const int p = gm.r.sub == 1 ? gi % gm.r.cpt : 0, q = gm.c.sub == 1 ? gj % gm.c.cpt : 0;
+                const double* s = slab + (((b * 3 + c) * ntiles + (int64_t)tr * gm.c.ntile + tc) * ppt + p * gm.c.cpt + q) * 3;
+#pragma unroll
+                for (int k = 0; k < 3; ++k) a[k] += s[k];
+            }
+#pragma unroll
+    for (int k = 0; k < 3; ++k) cells[e * 3 + k] = a[k];
+}
+
 __global__ __launch_bounds__(NT) void code_histogram_kernel(const int64_t* __restrict__ idx, const int64_t* __restrict__ grain,
                                                             int64_t Hf, int64_t Wf, int64_t hg, int64_t wg, int64_t r, int64_t K,
                                                             int G, int64_t* __restrict__ counts, int64_t* __restrict__ tokens,
@@ -236,7 +437,69 @@ void tile_grid(int64_t H, int64_t W, int64_t* tiles_x, int64_t* ntiles) {
     *ntiles = cdiv64(H, TH) * *tiles_x;
 }
 
+CellAxis cell_axis(int64_t n_pix, int64_t n_cells, int T) {
+    CellAxis a;
+    a.cell = (int)(n_pix / n_cells);
+    if (a.cell <= T) {
+        a.cpt = T / a.cell;
+        a.sub = 1;
+        a.ntile = (int)cdiv64(n_cells, a.cpt);
+    } else {
+        a.cpt = 1;
+        a.sub = (int)cdiv64(a.cell, T);
+        a.ntile = (int)(n_cells * a.sub);
+    }
+    return a;
+}
+
+bool cell_grid_ok(int64_t B, int64_t H, int64_t W, int64_t hg, int64_t wg) {
+    return B > 0 && H > 0 && W > 0 && hg > 0 && wg > 0 && H < (1ll << 24) && W < (1ll << 24) && H % hg == 0 && W % wg == 0;
+}
+
+CellGeom cell_geom(int64_t H, int64_t W, int64_t hg, int64_t wg) {
+    CellGeom g;
+    g.r = cell_axis(H, hg, TH);
+    g.c = cell_axis(W, wg, TW);
+    g.hg = (int)hg;
+    g.wg = (int)wg;
+    return g;
+}
+
 }  // namespace
+
+extern "C" size_t dvq_recon_cells_workspace_bytes(int64_t B, int64_t H, int64_t W, int64_t hg, int64_t wg) {
+    if (!cell_grid_ok(B, H, W, hg, wg)) return 0;
+    const CellGeom g = cell_geom(H, W, hg, wg);
+    return (size_t)B * 3 * (size_t)g.r.ntile * g.c.ntile * (size_t)(g.r.cpt * g.c.cpt) * 3 * sizeof(double);
+}
+
+extern "C" int dvq_recon_cells(const float* x, const float* y, int64_t B, int64_t H, int64_t W, int64_t hg, int64_t wg, int quantize_u8,
+                               double* cells, void* ws, size_t ws_bytes, dvq_stream_t stream) {
+    DVQ_REQUIRE(x && y && cells && ws, DVQ_EINVAL, "dvq_recon_cells: null pointer");
+    DVQ_REQUIRE(quantize_u8 == 0 || quantize_u8 == 1, DVQ_EINVAL, "dvq_recon_cells: quantize_u8=%d is not 0 or 1", quantize_u8);
+    DVQ_REQUIRE(cell_grid_ok(B, H, W, hg, wg), DVQ_ESHAPE,
+                "dvq_recon_cells: B=%lld H=%lld W=%lld over a %lld x %lld cell grid (H %% hg == 0 and W %% wg == 0 are needed)",
+                (long long)B, (long long)H, (long long)W, (long long)hg, (long long)wg);
+    const CellGeom g = cell_geom(H, W, hg, wg);
+    const size_t need = dvq_recon_cells_workspace_bytes(B, H, W, hg, wg);
+    DVQ_REQUIRE(ws_bytes >= need, DVQ_EWORKSPACE, "dvq_recon_cells: workspace %zu bytes < %zu", ws_bytes, need);
+    const int64_t nblk = B * 3 * g.r.ntile * g.c.ntile, ncell = B * hg * wg;
+    DVQ_REQUIRE(nblk < (1ll << 31) && ncell < (1ll << 31), DVQ_ESHAPE, "dvq_recon_cells: %lld tiles / %lld cells is too many",
+                (long long)nblk, (long long)ncell);
+    hipStream_t s = (hipStream_t)stream;
+    double* slab = static_cast<double*>(ws);
+    const Gauss11 gw = gaussian11();
+    // 16-byte loads need every tile origin on a multiple of 4 columns: W % 4 == 0 and a cell width that is one
+    const bool vec = W % 4 == 0 && g.c.cell % 4 == 0 && (reinterpret_cast<uintptr_t>(x) & 15) == 0 && (reinterpret_cast<uintptr_t>(y) & 15) == 0;
+    if (vec)
+        recon_cells_tile_kernel<true><<<dim3((unsigned)nblk), dim3(NT), 0, s>>>(x, y, H, W, g, quantize_u8, gw, slab);
+    else
+        recon_cells_tile_kernel<false><<<dim3((unsigned)nblk), dim3(NT), 0, s>>>(x, y, H, W, g, quantize_u8, gw, slab);
+    DVQ_CHECK_LAUNCH("recon_cells_tile");
+    recon_cells_fold_kernel<<<dim3((unsigned)cdiv64(ncell, NT)), dim3(NT), 0, s>>>(slab, B, g, cells);
+    DVQ_CHECK_LAUNCH("recon_cells_fold");
+    return DVQ_OK;
+}
 
 extern "C" size_t dvq_recon_metrics_workspace_bytes(int64_t B, int64_t H, int64_t W) {
     if (B <= 0 || H <= 0 || W <= 0) return 0;

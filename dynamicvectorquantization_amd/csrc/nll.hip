@@ -8,6 +8,7 @@
 // exactly one lane: no atomics, no [rows, V] temporary.
 // dvq_nll_segment_sums: one workgroup per (image, segment); thread t adds rows t, t + 256, ... in fp64, then a fixed tree over the
 // 256 partial sums -- two launches on the same input give the same bits.
+// dvq_nll_cell_sums: the same sums keyed by grid cell (docs/design/30-cell-maps.md); one owner thread per cell walks the rows in order.
 #include "dvq_common.h"
 
 #include <math.h>
@@ -152,7 +153,80 @@ __global__ __launch_bounds__(NT) void nll_segment_sums_kernel(const float* __res
     if (tid < 4) out[(img * 2 + seg) * 4 + tid] = red[tid][0];
 }
 
+// Cell of a position code under the mapping of permute_dual_back_kernel (csrc/permuter.hip): a coarse code IS its cell, a fine code is
+// a raster index of the fine grid.  Anything that is no grid position (eos, pad, start tokens): ncell = "outside".
+__device__ __forceinline__ int cell_of_position(int64_t pos, bool fine, int hw1, int hw2) {
+    const int ncell = hw1 * hw1, fhw = hw1 * hw2;
+    if (!fine) return pos >= 0 && pos < ncell ? (int)pos : ncell;
+    if (pos < 0 || pos >= (int64_t)fhw * fhw) return ncell;
+    const int e = (int)pos;
+    return (e / fhw / hw2) * hw1 + (e % fhw) / hw2;
+}
+
+// one workgroup per (image, segment); thread t OWNS cells t, t + 256, ... (cell ncell = outside) and walks the segment's rows in row
+// order, 256 rows at a time through LDS (every thread reads the same entry: a broadcast).  No atomics, one writer per output element.
+__global__ __launch_bounds__(NT) void nll_cell_sums_kernel(const float* __restrict__ nll, const int* __restrict__ rank,
+                                                           const int64_t* __restrict__ pos, int64_t Tp, int64_t split, int hw1, int hw2,
+                                                           int stream0, int stream1, double* __restrict__ cells,
+                                                           double* __restrict__ outside) {
+    __shared__ int s_cell[NT];
+    __shared__ float s_nll[NT];
+    __shared__ int s_rank[NT];
+    const int64_t img = blockIdx.x >> 1;
+    const int seg = blockIdx.x & 1;
+    const int stream = seg == 0 ? stream0 : stream1;
+    if (stream < 0) return;
+    const int64_t t0 = seg == 0 ? 0 : split, t1 = seg == 0 ? split : Tp;
+    const int ncell = hw1 * hw1;
+    const int tid = threadIdx.x;
+    for (int cbase = 0; cbase <= ncell; cbase += NT) {
+        const int mine = cbase + tid;
+        double a[4] = {0.0, 0.0, 0.0, 0.0};                          // nll sum, tokens, top-1 hits, top-5 hits
+        for (int64_t base = t0; base < t1; base += NT) {
+            const int64_t t = base + tid;
+            int c = -1;
+            if (t < t1) {
+                const int rk = rank[img * Tp + t];
+                s_rank[tid] = rk;
+                s_nll[tid] = nll[img * Tp + t];
+                if (rk >= 0) c = cell_of_position(pos[img * Tp + t], seg == 1, hw1, hw2);
+            }
+            s_cell[tid] = c;                                         // -1: ignored row or past the segment
+            __syncthreads();
+            const int n = (int)(t1 - base < NT ? t1 - base : NT);
+            for (int k = 0; k < n; ++k) {
+                if (s_cell[k] == mine) {
+                    const int rk = s_rank[k];
+                    a[0] += (double)s_nll[k];
+                    a[1] += 1.0;
+                    a[2] += rk == 0 ? 1.0 : 0.0;
+                    a[3] += rk < 5 ? 1.0 : 0.0;
+                }
+            }
+            __syncthreads();
+        }
+        if (mine <= ncell) {
+            double* o = mine < ncell ? cells + ((img * 4 + stream) * ncell + mine) * 4 : outside + (img * 4 + stream) * 4;
+#pragma unroll
+            for (int k = 0; k < 4; ++k) o[k] = a[k];
+        }
+    }
+}
+
 }  // namespace
+
+int dvq_nll_cell_sums(const float* nll, const int32_t* rank, const int64_t* pos, int64_t B, int64_t Tp, int64_t split, int hw1, int hw2,
+                      int stream0, int stream1, double* cells, double* outside, dvq_stream_t stream) {
+    DVQ_REQUIRE(nll && rank && pos && cells && outside && B > 0 && B < (int64_t)1 << 30 && Tp > 0 && split >= 0 && split <= Tp, DVQ_EINVAL,
+                "dvq_nll_cell_sums: bad arguments");
+    DVQ_REQUIRE(hw1 > 0 && hw2 > 0 && (int64_t)hw1 * hw2 <= 4096 && stream0 >= -1 && stream0 < 4 && stream1 >= -1 && stream1 < 4 &&
+                    (stream0 != stream1 || stream0 < 0),
+                DVQ_ESHAPE, "dvq_nll_cell_sums: hw1=%d hw2=%d streams %d / %d", hw1, hw2, stream0, stream1);
+    nll_cell_sums_kernel<<<dim3((unsigned)(2 * B)), dim3(NT), 0, (hipStream_t)stream>>>(nll, rank, pos, Tp, split, hw1, hw2, stream0, stream1,
+                                                                                       cells, outside);
+    DVQ_CHECK_LAUNCH("nll_cell_sums");
+    return DVQ_OK;
+}
 
 int dvq_token_nll(const void* logits, int dtype, int64_t rows, int64_t V, int64_t ldl, const int64_t* target, int64_t ignore_index,
                   float* nll, int32_t* rank, dvq_stream_t stream) {

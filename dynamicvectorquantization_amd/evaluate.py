@@ -12,6 +12,12 @@ top-5 accuracy per token stream, bits per image and per pixel (docs/design/15-li
   * aggregate_likelihood     host aggregation of the per-image stream sums (pure numpy)
   * evaluate_likelihood      one model.score per batch (teacher forcing, eval mode, no gradient)
 
+  * CellMeter                accumulates per-cell error maps (dvq_recon_cells), patch entropies, grain maps and per-cell likelihood maps
+                             (dvq_nll_cell_sums) on the device; summary() makes the one host copy (docs/design/30-cell-maps.md)
+  * aggregate_cells          host aggregation of the maps: by grain, by entropy decile, Spearman rank correlations, consistency with the
+                             per-image figures (pure numpy)
+  * evaluate_cells           one ae_fwd (+ one score_cells) per batch
+
 `reference_usage` reproduces what the reference's scripts/tools/codebook_usage_dqvae.py:69 prints under the label "usage":
 1 - codes_used / K, i.e. the UNUSED fraction of the codebook.
 """
@@ -301,6 +307,280 @@ def evaluate_likelihood(model, batches, per_image: bool = False) -> dict:
                 raise ValueError(f"a conditional model needs dict batches with '{model.cond_stage_key}'")
             meter.update(model.score(x, c), pixels_per_image=int(x.shape[-2]) * int(x.shape[-1]) * 3)
     s = meter.summary(per_image=per_image)
+    s["dtype"] = dtype_name()
+    return s
+
+
+# ---- per-cell maps: where an image's error and its bits fall (docs/design/30-cell-maps.md) ------------------------------------------------
+def average_ranks(v):
+    """1-based ranks of a 1-d array, ties sharing the average of the ranks they span (fp64)"""
+    v = np.asarray(v, dtype=np.float64).reshape(-1)
+    order = np.argsort(v, kind="stable")
+    sv = v[order]
+    ranks = np.empty(v.size, dtype=np.float64)
+    start = np.flatnonzero(np.concatenate([[True], sv[1:] != sv[:-1]])) if v.size else np.zeros(0, dtype=np.int64)
+    end = np.concatenate([start[1:], [v.size]]) if v.size else start
+    for a, b in zip(start, end):
+        ranks[order[a:b]] = 0.5 * (a + 1 + b)
+    return ranks
+
+
+def spearman(a, b):
+    """Spearman rank correlation with average ranks for ties: Pearson's r of the rank vectors.  None for fewer than two points or a
+    constant vector (the coefficient is undefined)"""
+    a, b = np.asarray(a, dtype=np.float64).reshape(-1), np.asarray(b, dtype=np.float64).reshape(-1)
+    if a.size != b.size:
+        raise ValueError(f"spearman: {a.size} and {b.size} values")
+    if a.size < 2:
+        return None
+    ra, rb = average_ranks(a), average_ranks(b)
+    da, db = ra - ra.mean(), rb - rb.mean()
+    den = np.sqrt((da * da).sum() * (db * db).sum())
+    return float((da * db).sum() / den) if den > 0 else None
+
+
+def decile_index(values):
+    """-> (index in 0..9 per value, the nine inner edges): edges = the 10 %, ..., 90 % quantiles of the pooled values (linear
+    interpolation); a value belongs to the decile whose lower edge it reaches (index = number of edges <= value), so equal values always
+    share a decile and a decile can be empty when ties straddle an edge"""
+    v = np.asarray(values, dtype=np.float64).reshape(-1)
+    edges = np.quantile(v, np.arange(1, 10) / 10.0) if v.size else np.zeros(9)
+    return np.searchsorted(edges, v, side="right"), edges
+
+
+def cell_window_counts(h, w, hg, wg):
+    """int64 [hg, wg]: valid 11 x 11 SSIM windows (top-left (r, c), r <= h - 11, c <= w - 11) whose top-left pixel lies in each cell"""
+    ch, cw = h // hg, w // wg
+    rows = np.clip(np.minimum((np.arange(hg) + 1) * ch, h - 10) - np.arange(hg) * ch, 0, None)
+    cols = np.clip(np.minimum((np.arange(wg) + 1) * cw, w - 10) - np.arange(wg) * cw, 0, None)
+    return (rows[:, None] * cols[None, :]).astype(np.int64)
+
+
+def _rel_gap(a, b):
+    a, b = np.asarray(a, dtype=np.float64), np.asarray(b, dtype=np.float64)
+    den = np.maximum(np.abs(b), np.finfo(np.float64).tiny)
+    return float(np.max(np.where(a == b, 0.0, np.abs(a - b) / den))) if a.size else 0.0
+
+
+def aggregate_cells(h, w, n_grains, grain, recon=None, entropy=None, bits=None, outside=None, ref_recon=None, ref_score=None) -> dict:
+    """host aggregation (fp64, pure numpy) of N images' cell maps over an hg x wg grid of an h x w image.
+    grain int [N, hg, wg] (0 = coarsest; a cell of grain g spends 4^g content tokens); recon fp64 [N, hg, wg, 3] = dvq_recon_cells' sums
+    or None; entropy [N, hg, wg] or None; bits: dvq_nll_cell_sums' cells fp64 [N, 4, hg * wg, 4] with outside [N, 4, 4], or None;
+    ref_recon = (mse, l1, ssim) per image and ref_score [N, 4, 4]: the per-image figures the cells must add up to.
+    A cell's "bits" are its four streams' nll sums / ln 2; a cell's "error" is its squared-error sum."""
+    grain = np.asarray(grain, dtype=np.int64)
+    n, hg, wg = grain.shape
+    ncell = hg * wg
+    pix = (h // hg) * (w // wg) * 3
+    win = cell_window_counts(h, w, hg, wg)
+    g_flat = grain.reshape(-1)
+    sq = ab = ss = ent = cell_bits = None
+    if recon is not None:
+        recon = np.asarray(recon, dtype=np.float64).reshape(n, hg, wg, 3)
+        sq, ab, ss = recon[..., 0].reshape(-1), recon[..., 1].reshape(-1), recon[..., 2].reshape(-1)
+    if entropy is not None:
+        ent = np.asarray(entropy, dtype=np.float64).reshape(-1)
+    if bits is not None:
+        bits = np.asarray(bits, dtype=np.float64).reshape(n, 4, ncell, 4)
+        outside = np.asarray(outside, dtype=np.float64).reshape(n, 4, 4)
+        cell_bits = (bits[:, :, :, 0].sum(axis=1) / _LN2).reshape(-1)
+    win_flat = np.broadcast_to(win, (n, hg, wg)).reshape(-1)
+    tokens = 4.0 ** g_flat
+    by_grain = []
+    for g in range(n_grains):
+        m = g_flat == g
+        k = int(m.sum())
+        row = {"grain": g, "cells": k, "cell_share": _div(k, g_flat.size), "token_share": _div(tokens[m].sum(), tokens.sum()),
+               "sq_err_share": None, "bits_share": None, "mse": None, "psnr": None, "ssim": None, "bits_per_token": None}
+        if sq is not None:
+            row["sq_err_share"] = _div(sq[m].sum(), sq.sum())
+            row["mse"] = _div(sq[m].sum(), k * pix)
+            row["psnr"] = float(10.0 * np.log10(1.0 / row["mse"])) if row["mse"] else None
+            row["ssim"] = _div(ss[m].sum(), 3.0 * win_flat[m].sum())
+        if bits is not None:
+            row["bits_share"] = _div(cell_bits[m].sum(), cell_bits.sum())
+            mm = m.reshape(n, ncell)
+            row["bits_per_token"] = {name: _div((bits[:, i, :, 0] * mm).sum() / _LN2, (bits[:, i, :, 1] * mm).sum())
+                                     for i, name in enumerate(LIKELIHOOD_STREAMS)}
+        by_grain.append(row)
+    deciles = None
+    if ent is not None:
+        idx, edges = decile_index(ent)
+        deciles = {"edges": [float(e) for e in edges], "rows": []}
+        for d in range(10):
+            m = idx == d
+            k = int(m.sum())
+            deciles["rows"].append({"decile": d, "cells": k, "entropy": _div(ent[m].sum(), k),
+                                    "sq_err": _div(sq[m].sum(), k) if sq is not None else None,
+                                    "mse": _div(sq[m].sum(), k * pix) if sq is not None else None,
+                                    "bits": _div(cell_bits[m].sum(), k) if cell_bits is not None else None,
+                                    "fine_fraction": _div(float((g_flat[m] > 0).sum()), k)})
+    pairs = {"entropy_error": (ent, sq), "entropy_bits": (ent, cell_bits), "bits_error": (cell_bits, sq)}
+    corr = {}
+    for name, (a, b) in pairs.items():
+        if a is None or b is None:
+            corr[name] = None
+            continue
+        corr[name] = {"pooled": spearman(a, b), "by_grain": [spearman(a[g_flat == g], b[g_flat == g]) for g in range(n_grains)]}
+    cons = {"sq_err": None, "abs_err": None, "ssim": None, "nll": None, "counts_equal": None, "max": None}
+    if recon is not None and ref_recon is not None:
+        mse, l1, ssim = [np.asarray(v, dtype=np.float64).reshape(-1) for v in ref_recon]
+        cons["sq_err"] = _rel_gap(recon[..., 0].sum(axis=(1, 2)) / (3.0 * h * w), mse)
+        cons["abs_err"] = _rel_gap(recon[..., 1].sum(axis=(1, 2)) / (3.0 * h * w), l1)
+        if win.sum() > 0:
+            cons["ssim"] = _rel_gap(recon[..., 2].sum(axis=(1, 2)) / (3.0 * win.sum()), ssim)
+    if bits is not None and ref_score is not None:
+        ref_score = np.asarray(ref_score, dtype=np.float64).reshape(n, 4, 4)
+        tot = bits.sum(axis=2) + outside
+        cons["nll"] = _rel_gap(tot[:, :, 0], ref_score[:, :, 0])
+        cons["counts_equal"] = bool(np.array_equal(tot[:, :, 1:], ref_score[:, :, 1:]))
+    gaps = [cons[k] for k in ("sq_err", "abs_err", "ssim", "nll") if cons[k] is not None]
+    cons["max"] = max(gaps) if gaps else None
+    out = {"n_images": int(n), "grid": [int(hg), int(wg)], "cell_pixels": [int(h // hg), int(w // wg)], "by_grain": by_grain,
+           "by_entropy_decile": deciles, "rank_correlation": corr, "consistency": cons}
+    if bits is not None:
+        out["outside_bits_share"] = _div(outside[:, :, 0].sum(), outside[:, :, 0].sum() + bits[:, :, :, 0].sum())
+    return out
+
+
+def cell_maps(h, w, grain, recon=None, entropy=None, bits=None, outside=None) -> dict:
+    """the per-image arrays of a --maps file: sq_err / abs_err (cell sums) and ssim (cell MEAN over its windows, NaN for a cell without
+    one) [N, hg, wg]; entropy, grain [N, hg, wg]; bits [N, 4, hg, wg] (nll sums / ln 2, axis 1 = LIKELIHOOD_STREAMS), tokens
+    [N, 4, hg, wg]; outside [N, 4, 4] (dvq_nll_cell_sums' values: nats, tokens, top-1, top-5).  Absent maps are left out."""
+    grain = np.asarray(grain, dtype=np.int64)
+    n, hg, wg = grain.shape
+    out = {"grain": grain, "image_size": np.array([h, w], dtype=np.int64)}
+    if recon is not None:
+        recon = np.asarray(recon, dtype=np.float64).reshape(n, hg, wg, 3)
+        win = 3.0 * cell_window_counts(h, w, hg, wg)
+        out["sq_err"], out["abs_err"] = recon[..., 0].copy(), recon[..., 1].copy()
+        with np.errstate(divide="ignore", invalid="ignore"):
+            out["ssim"] = np.where(win > 0, recon[..., 2] / win, np.nan)
+    if entropy is not None:
+        out["entropy"] = np.asarray(entropy, dtype=np.float64).reshape(n, hg, wg)
+    if bits is not None:
+        bits = np.asarray(bits, dtype=np.float64).reshape(n, 4, hg, wg, 4)
+        out["bits"], out["tokens"] = bits[..., 0] / _LN2, bits[..., 1].copy()
+        out["outside"] = np.asarray(outside, dtype=np.float64).reshape(n, 4, 4)
+    return out
+
+
+def save_cell_maps(path: str, maps: dict) -> None:
+    if not path.endswith(".npz"):
+        raise ValueError("--maps takes a .npz path")
+    np.savez(path, **maps)
+
+
+def load_cell_maps(path: str) -> dict:
+    with np.load(path) as f:
+        return {k: f[k] for k in f.files}
+
+
+class CellMeter:
+    """Accumulates cell maps of evaluation batches on the device; nothing is copied to the host until summary().
+    update_recon(x, rec, grain, entropy=None): error cells of the pair over the grain map's grid (dvq_recon_cells), the per-image
+    figures of dvq_recon_metrics next to them, and the patch entropy at the cell size (the entropy kernel, whatever routes the model).
+    update_bits(cells, outside, score=None, grain=None): Dualformer.score_cells' pair (+ score()'s block for the consistency figure);
+    grain: only when no update_recon supplies it (token batches)."""
+
+    def __init__(self, n_grains: int = 2, quantize_u8: bool = True):
+        self.n_grains, self.quantize_u8 = int(n_grains), bool(quantize_u8)
+        self.size = None
+        self._ws = {}
+        self._recon, self._ref, self._ent, self._grain, self._bits, self._out, self._score = [], [], [], [], [], [], []
+
+    def _set_size(self, h, w):
+        if self.size not in (None, (h, w)):
+            raise ValueError("images of different sizes in one cell-map evaluation")
+        self.size = (h, w)
+
+    def update_recon(self, x, rec, grain, entropy=None):
+        b, _, h, w = x.shape
+        hg, wg = int(grain.shape[1]), int(grain.shape[2])
+        if h % hg or w % wg or h // hg != w // wg:
+            raise ValueError(f"a {hg} x {wg} grain map does not cut a {h} x {w} image into square cells")
+        self._set_size(h, w)
+        key = (b, h, w, hg, wg)
+        if key not in self._ws:
+            self._ws[key] = (K.recon_cells_workspace(b, h, w, hg, wg, x.device), K.recon_metrics_workspace(b, h, w, x.device))
+        self._recon.append(K.recon_cells(x, rec, hg, wg, self.quantize_u8, self._ws[key][0]))
+        if h >= 11 and w >= 11:
+            self._ref.append(torch.stack(K.recon_metrics(x, rec, self.quantize_u8, self._ws[key][1]), dim=1))
+        if entropy is None or tuple(entropy.shape) != (b, hg, wg):
+            entropy = K.patch_entropy_gate(x, h // hg, None)[0]
+        self._ent.append(entropy)
+        self._grain.append(grain)
+
+    def update_bits(self, cells, outside, score=None, grain=None, size=None):
+        self._bits.append(cells)
+        self._out.append(outside)
+        if score is not None:
+            self._score.append(score)
+        if grain is not None:
+            self._grain.append(grain)
+        if size is not None:
+            self._set_size(*size)
+
+    def summary(self, maps: bool = False) -> dict:
+        """the one host copy, then aggregate_cells; maps=True adds "maps" (cell_maps' dict of per-image arrays)"""
+        if not self._grain:
+            raise ValueError("CellMeter.summary(): no batch was added")
+
+        def host(lst):
+            return torch.cat(lst, dim=0).cpu().numpy() if lst else None
+        grain, recon, ent, bits, outside = host(self._grain), host(self._recon), host(self._ent), host(self._bits), host(self._out)
+        ref, score = host(self._ref), host(self._score)
+        h, w = self.size
+        if bits is not None and (bits.shape[0] != grain.shape[0] or bits.shape[2] != grain.shape[1] * grain.shape[2]):
+            raise ValueError(f"bit maps {bits.shape} do not match the grain maps {grain.shape}")
+        out = aggregate_cells(h, w, self.n_grains, grain, recon, ent, bits, outside,
+                              ref_recon=(ref[:, 0], ref[:, 1], ref[:, 2]) if ref is not None else None, ref_score=score)
+        if maps:
+            out["maps"] = cell_maps(h, w, grain, recon, ent, bits, outside)
+        return out
+
+
+def evaluate_cells(model, batches, stage2=None, quantize_u8: bool = True, maps: bool = False) -> dict:
+    """Where error and bits fall (docs/design/30-cell-maps.md).  model: a DQ-VAE, or None with stage2 (its frozen first stage is used);
+    stage2: a Dualformer / ClassDualformer, or None (error maps only).  Per image batch: one model.ae_fwd(x, None) for the
+    reconstruction and the grain map, the patch entropy at the cell size, and with stage2 one score_cells (+ one score: the per-image
+    figure the cells are checked against).  Token batches ({"tokens": ...}) give bit maps only; their grain map is read off the fine
+    stream's token counts.  Everything stays on the device until the summary.  Keys: aggregate_cells(), dtype; maps=True: "maps"."""
+    if model is None:
+        if stage2 is None:
+            raise ValueError("evaluate_cells needs a model")
+        model = stage2.first_stage_model
+    model.eval()
+    meter = CellMeter(getattr(model, "N_GRAINS", 2), quantize_u8=quantize_u8)
+    with torch.no_grad():
+        for batch in batches:
+            if isinstance(batch, dict) and "tokens" in batch:
+                if stage2 is None:
+                    raise ValueError("token batches need a stage-2 model")
+                tokens, c = stage2.get_tc(batch)
+                cells, outside = stage2.score_cells_tokens(tokens, c)
+                grain = (cells[:, 1, :, 1] > 0).long().view(-1, stage2.hw1, stage2.hw1)
+                side = int(stage2.first_stage_model.encoder.resolution)
+                meter.update_bits(cells, outside, stage2.score_tokens(tokens, c), grain=grain, size=(side, side))
+                continue
+            c = None
+            if stage2 is not None and isinstance(batch, dict):
+                x, c = stage2.get_xc(batch)
+            else:
+                x = batch[getattr(model, "image_key", "image")] if isinstance(batch, dict) else batch
+            x = x.float().contiguous() if x.dtype != torch.float32 or not x.is_contiguous() else x
+            out = model.ae_fwd(x, None)
+            meter.update_recon(x, out["rec"], out["grain"], out["entropy"])
+            if stage2 is not None:
+                if c is None:
+                    if stage2.cond_stage_key != stage2.first_stage_key:
+                        raise ValueError(f"a conditional model needs dict batches with '{stage2.cond_stage_key}'")
+                    c = x
+                # one encode for both passes: the frozen first stage's float atomics may flip a code between two encodes
+                _, z_out = stage2.encode_to_z(x)
+                cells, outside = stage2._score_streams(z_out, c, cells=True)
+                meter.update_bits(cells, outside, stage2._score_streams(z_out, c))
+    s = meter.summary(maps=maps)
     s["dtype"] = dtype_name()
     return s
 

@@ -1041,6 +1041,19 @@ def nll_segment_sums(nll, rank, b, tp, split):
     return out
 
 
+def nll_cell_sums(nll, rank, pos, b, tp, split, hw1, hw2, streams, cells, outside):
+    """the sums of nll_segment_sums keyed by grid cell (dvq_nll_cell_sums): pos int64 [b, tp] = the position code that decides each
+    row's cell (coarse codes in rows [0, split), fine codes in [split, tp)); streams = (stream index of segment 0, of segment 1), -1
+    skips a segment; written into cells fp64 [b, 4, hw1 * hw1, 4] and outside fp64 [b, 4, 4]"""
+    if nll.numel() != b * tp or rank.numel() != b * tp or pos.numel() != b * tp or pos.dtype != torch.int64:
+        raise _lib.DvqError(f"nll_cell_sums: {nll.numel()} / {rank.numel()} / {pos.numel()} rows ({pos.dtype}) for [{b}, {tp}]")
+    if (tuple(cells.shape) != (b, 4, hw1 * hw1, 4) or tuple(outside.shape) != (b, 4, 4) or cells.dtype != torch.float64
+            or outside.dtype != torch.float64 or not cells.is_contiguous() or not outside.is_contiguous()):
+        raise _lib.DvqError(f"nll_cell_sums: outputs {tuple(cells.shape)} / {tuple(outside.shape)} for b={b}, hw1={hw1}")
+    check(lib().dvq_nll_cell_sums(_p(nll), _p(rank), _p(pos), b, tp, split, hw1, hw2, int(streams[0]), int(streams[1]), _p(cells),
+                                  _p(outside), _s()), "dvq_nll_cell_sums")
+
+
 def dropout_add(x, a, p, seed):
     """x + dropout(a) in one pass (p = 0: x + a); same decisions as dropout(a, p, seed)"""
     y = torch.empty_like(x)
@@ -1561,6 +1574,26 @@ def recon_metrics(x, y, quantize_u8=False, ws=None, out=None):
     check(lib().dvq_recon_metrics(_p(x), _p(y), b, h, w, int(bool(quantize_u8)), _p(mse), _p(l1), _p(ssim), _p(ws), ws.numel(), _s()),
           "dvq_recon_metrics")
     return mse, l1, ssim
+
+
+def recon_cells_workspace(b, h, w, hg, wg, device):
+    """uint8 workspace of dvq_recon_cells_workspace_bytes(b, h, w, hg, wg) bytes (per-tile, per-cell-piece partial sums)"""
+    return torch.empty(int(lib().dvq_recon_cells_workspace_bytes(b, h, w, hg, wg)), dtype=torch.uint8, device=device)
+
+
+def recon_cells(x, y, hg, wg, quantize_u8=False, ws=None):
+    """x (target), y (reconstruction) NCHW fp32 [B,3,H,W] in [-1, 1] over an hg x wg cell grid -> fp64 [B, hg, wg, 3]: per cell the SUMS
+    of (x01 - y01)^2, of |x - y| and of the SSIM index of the windows whose top-left pixel lies in the cell (include/dvq_hip.h,
+    dvq_recon_cells).  ws: recon_cells_workspace(B, H, W, hg, wg) or None (allocated here)"""
+    b, c, h, w = x.shape
+    assert c == 3 and x.dtype == torch.float32 and y.dtype == torch.float32 and tuple(y.shape) == tuple(x.shape)
+    assert x.is_contiguous() and y.is_contiguous()
+    if ws is None:
+        ws = recon_cells_workspace(b, h, w, hg, wg, x.device)
+    cells = torch.empty(b, max(int(hg), 0), max(int(wg), 0), 3, dtype=torch.float64, device=x.device)     # (a bad grid: the library says so)
+    check(lib().dvq_recon_cells(_p(x), _p(y), b, h, w, hg, wg, int(bool(quantize_u8)), _p(cells), _p(ws), ws.numel(), _s()),
+          "dvq_recon_cells")
+    return cells
 
 
 def code_histogram(codes, grain, n_codes, n_grains, counts, invalid, tokens=None):

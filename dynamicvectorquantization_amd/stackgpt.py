@@ -839,6 +839,30 @@ class StackGPT(nn.Module):
         fpo = K.nll_segment_sums(*K.token_nll(pl, vp, tg[2][0], tg[2][1]), b, tp, 0)[:, 1]
         return torch.stack([con[:, 0], con[:, 1], cpo, fpo], dim=1)
 
+    @torch.no_grad()
+    def score_cells(self, coarse_content, fine_content, coarse_position, fine_position, coarse_seg, fine_seg, content_target,
+                    coarse_position_target, fine_position_target, hw1, hw2, **ignorekwargs):
+        """score()'s arguments + the permuter's grid (hw1 x hw1 cells of hw2 x hw2 codes) -> (cells fp64 [B, 4, hw1 * hw1, 4], outside
+        fp64 [B, 4, 4]): score()'s four values per stream keyed by grid cell, from the same forward, targets and per-row nll / rank
+        (docs/design/30-cell-maps.md).  A content row goes to the cell of the position code paired with its target in the input
+        streams (cat(coarse_position, fine_position)[:, 1:], the pairing DualGrainSeperatePermuter.forward_back scatters by), a
+        position row to the cell of its target code; a target without a grid position (eos, a counted pad, start tokens) goes to
+        `outside`.  cells.sum(2) + outside equals score() up to the order of the fp64 sums."""
+        pl, cl, b, t, tp = self.fwd(coarse_content, fine_content, coarse_position, fine_position, coarse_seg, fine_seg, None)
+        lc = coarse_position.shape[1]
+        tg = self._targets(b, t, tp, lc, content_target, coarse_position_target, fine_position_target, pl.device)
+        vp, vc = self.config.fine_position_size, self.config.vocab_size
+        paired = torch.full((b, tp), -1, dtype=torch.long, device=pl.device)
+        paired[:, :t] = torch.cat([coarse_position, fine_position], dim=1)[:, 1:]
+        cells = torch.zeros(b, 4, hw1 * hw1, 4, dtype=torch.float64, device=pl.device)
+        outside = torch.zeros(b, 4, 4, dtype=torch.float64, device=pl.device)
+        K.nll_cell_sums(*K.token_nll(cl, vc, tg[0][0], tg[0][1]), paired.view(-1), b, tp, coarse_content.shape[1] - 1, hw1, hw2, (0, 1),
+                        cells, outside)
+        # a position row's cell is that of its own target code: the target vectors are the position vectors
+        K.nll_cell_sums(*K.token_nll(pl, vp, tg[1][0], tg[1][1]), tg[1][0], b, tp, tp, hw1, hw2, (2, -1), cells, outside)
+        K.nll_cell_sums(*K.token_nll(pl, vp, tg[2][0], tg[2][1]), tg[2][0], b, tp, 0, hw1, hw2, (-1, 3), cells, outside)
+        return cells, outside
+
 
 class _StackGPTLossFn(torch.autograd.Function):
     """teacher-forced forward + the three cross entropies as one autograd node"""

@@ -288,14 +288,16 @@ class Dualformer(_SamplerMixinBase, nn.Module):
         """forward() from stored codes: `tokens` = the permuter's dict (tokens.TokenBatchLoader), no first stage, no host sync"""
         return self.transformer(**self.teacher_forcing_inputs(tokens, self.encode_to_c(c)))
 
-    def _score_streams(self, z_out, c):
-        """StackGPT.score of the permuter dict z_out under conditioning c, the transformer in eval mode (no dropout) whatever mode it is
-        in; every module's training flag is put back as found"""
+    def _score_streams(self, z_out, c, cells=False):
+        """StackGPT.score (cells: StackGPT.score_cells on the permuter's grid) of the permuter dict z_out under conditioning c, the
+        transformer in eval mode (no dropout) whatever mode it is in; every module's training flag is put back as found"""
         inputs = self.teacher_forcing_inputs(z_out, self.encode_to_c(c))
         on = [m for m in self.transformer.modules() if m.training]        # (already in eval mode, the usual case: nothing to switch)
         for m in on:
             m.training = False
         try:
+            if cells:
+                return self.transformer.score_cells(**inputs, hw1=self.hw1, hw2=self.hw2)
             return self.transformer.score(**inputs)
         finally:
             for m in on:
@@ -313,6 +315,18 @@ class Dualformer(_SamplerMixinBase, nn.Module):
     def score_tokens(self, tokens, c):
         """score() from stored codes (`tokens` = the permuter's dict of a token batch, c = what get_tc returns)"""
         return self._score_streams(tokens, c)
+
+    @torch.no_grad()
+    def score_cells(self, x, c):
+        """score() keyed by grid cell: (cells fp64 [B, 4, hw1 * hw1, 4], outside fp64 [B, 4, 4]) -- StackGPT.score_cells on the permuter's
+        grid, docs/design/30-cell-maps.md.  cells.sum(2) + outside is score(x, c)."""
+        _, z_out = self.encode_to_z(x)
+        return self._score_streams(z_out, c, cells=True)
+
+    @torch.no_grad()
+    def score_cells_tokens(self, tokens, c):
+        """score_cells() from stored codes (`tokens` = the permuter's dict of a token batch, c = what get_tc returns): no first stage"""
+        return self._score_streams(tokens, c, cells=True)
 
     # ---- lossless token codec (codec.py, docs/design/27-token-codec.md)
     def compress(self, x, c=None, batch_group=8, return_bits=False):

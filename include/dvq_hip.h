@@ -48,7 +48,8 @@ const char* dvq_last_error(void);
  * Two values are ROUTE labels, not `__global__` names: "conv_x3_halo" and "conv_wgrad_x3_planes", the fp32x3 launch-level schemes of
  * dvq_conv2d_scratch_bytes (plane passes + the bf16 kernels behind them). */
 const char* dvq_last_kernel(void);
-int dvq_version(void);     /* 124: dvq_conv2d_fwd / _dgrad / _wgrad take (scratch, scratch_bytes) and route the fp32x3 launch-level schemes themselves;
+int dvq_version(void);     /* 124 (additions since, no signature changed, no symbol removed: dvq_recon_cells (+ _workspace_bytes), dvq_nll_cell_sums: per-cell
+                            * error and likelihood maps, docs/design/30-cell-maps.md): dvq_conv2d_fwd / _dgrad / _wgrad take (scratch, scratch_bytes) and route the fp32x3 launch-level schemes themselves;
                             * dvq_conv2d_scratch_bytes replaces dvq_conv3x3_x3_ok, dvq_conv3x3_x3_scratch_bytes and dvq_conv2d_wgrad_x3_scratch_bytes;
                             * dvq_conv2d_fwd_x3, dvq_conv2d_dgrad_x3 and dvq_conv2d_wgrad_oihw_x3 are gone;
                             * 123: struct dvq_token_rule, DVQ_TOKEN_RULE_MAXV: dvq_sample_constrained, dvq_sample_guided, dvq_codec_tables, dvq_codec_record and
@@ -835,12 +836,23 @@ int dvq_png_batch_unfilter(const uint8_t* scan, const void* desc, int64_t B, uin
  *   Hf / hg == Wf / wg == 2^(G-1) (else DVQ_ESHAPE): a cell of grain g spends 4^g tokens; grain = NULL: every position is a token.
  *   counts int64 [G][K] += tokens per (grain, code) (the caller zeroes it once; accumulates over calls); tokens int64 [B] = tokens per
  *   image (overwritten; a token whose code is out of range still counts); invalid int64 [1] += codes outside [0, K) at token positions
- *   + grain cells whose value is outside [0, G) (such a cell spends no token).  Integer atomics only: exact and deterministic. */
+ *   + grain cells whose value is outside [0, G) (such a cell spends no token).  Integer atomics only: exact and deterministic.
+ * dvq_recon_cells (docs/design/30-cell-maps.md): the same pair of images cut into an hg x wg grid of (H / hg) x (W / wg) pixel cells,
+ *   H % hg == 0 and W % wg == 0 (else DVQ_ESHAPE; any H, W >= 1).  cells fp64 [B][hg][wg][3], per cell and summed over the 3 channels:
+ *   [0] sum over the cell's pixels of (x01 - y01)^2, [1] sum of |x - y| on the raw values, [2] sum of the SSIM index over the valid
+ *   11 x 11 windows whose TOP-LEFT pixel lies in the cell (a window at (r, c) is valid iff r <= H - 11 and c <= W - 11; a cell without
+ *   one reports 0, and the caller derives the window count from the geometry).  Same x01, staging (v01 - 0.5), fp32 moments and fp64
+ *   error terms as dvq_recon_metrics; sums are NOT divided.  ws: dvq_recon_cells_workspace_bytes(B, H, W, hg, wg) bytes (0 for a bad
+ *   grid).  Every partial sum has one owner and a fixed order: two launches give the same bits and an image's map does not depend on
+ *   its batch.  dvq_recon_metrics is untouched by it. */
 size_t dvq_recon_metrics_workspace_bytes(int64_t B, int64_t H, int64_t W);
 int dvq_recon_metrics(const float* x, const float* y, int64_t B, int64_t H, int64_t W, int quantize_u8, double* mse, double* l1,
                       double* ssim, void* ws, size_t ws_bytes, dvq_stream_t stream);
 int dvq_code_histogram(const int64_t* idx, const int64_t* grain, int64_t B, int64_t Hf, int64_t Wf, int64_t hg, int64_t wg, int64_t K,
                        int G, int64_t* counts, int64_t* tokens, int64_t* invalid, dvq_stream_t stream);
+size_t dvq_recon_cells_workspace_bytes(int64_t B, int64_t H, int64_t W, int64_t hg, int64_t wg);
+int dvq_recon_cells(const float* x, const float* y, int64_t B, int64_t H, int64_t W, int64_t hg, int64_t wg, int quantize_u8,
+                    double* cells, void* ws, size_t ws_bytes, dvq_stream_t stream);
 
 /* ---- likelihood scoring of the DQ-Transformer (docs/design/15-likelihood.md; no reference kernel: it logs batch-mean losses only) ------
  * dvq_token_nll: logits [rows][ldl] of `dtype`, the first V columns are used (columns V .. ldl are padding and never enter a result);
@@ -853,10 +865,19 @@ int dvq_code_histogram(const int64_t* idx, const int64_t* grain, int64_t B, int6
  *   aligned or V > 2048) and written by one lane: no atomics, no [rows, V] temporary, bitwise reproducible.  Any V >= 1.
  * dvq_nll_segment_sums: rows laid out [B][Tp]; out fp64 [B][2][4] = (sum of nll, tokens, top-1 hits (rank == 0), top-5 hits
  *   (rank < 5)) over the rows with rank >= 0 of segment 0 = [0, split) and segment 1 = [split, Tp), 0 <= split <= Tp.  One workgroup per
- *   (image, segment), fixed summation order in fp64: two launches on the same input give the same bits. */
+ *   (image, segment), fixed summation order in fp64: two launches on the same input give the same bits.
+ * dvq_nll_cell_sums (docs/design/30-cell-maps.md): the same rows and segments keyed by grid cell.  pos int64 [B][Tp]: the position code
+ *   that decides a row's cell -- a COARSE code in segment 0 (code p in [0, hw1^2) is cell p), a FINE code in segment 1 (code e in
+ *   [0, (hw1 hw2)^2) is cell (e / fhw / hw2) * hw1 + (e % fhw) / hw2, fhw = hw1 * hw2: the cell dvq_permute_dual_back writes position
+ *   e into).  A row with rank >= 0 whose code is no grid position adds to `outside`; rows with rank < 0 add nothing.  Segment s is
+ *   written to stream index stream_s in [0, 4) of cells fp64 [B][4][hw1^2][4] and outside fp64 [B][4][4] (same four values as
+ *   dvq_nll_segment_sums); stream_s = -1 skips the segment and leaves its outputs alone.  One owner thread per output cell walks the
+ *   rows in row order: no atomics, bitwise reproducible. */
 int dvq_token_nll(const void* logits, int dtype, int64_t rows, int64_t V, int64_t ldl, const int64_t* target, int64_t ignore_index,
                   float* nll, int32_t* rank, dvq_stream_t stream);
 int dvq_nll_segment_sums(const float* nll, const int32_t* rank, int64_t B, int64_t Tp, int64_t split, double* out, dvq_stream_t stream);
+int dvq_nll_cell_sums(const float* nll, const int32_t* rank, const int64_t* pos, int64_t B, int64_t Tp, int64_t split, int hw1, int hw2,
+                      int stream0, int stream1, double* cells, double* outside, dvq_stream_t stream);
 
 /* ---- token shards (docs/design/16-token-shards.md; no reference kernel: the reference re-encodes every image in every stage-2 step) ---
  * dvq_tokens_pack: indices int64 [B][fhw][fhw], grain int64 [B][hw1][hw1] (what DualGrainVQModel.encode returns; fhw = hw1 * hw2) ->
