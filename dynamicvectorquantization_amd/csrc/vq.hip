@@ -55,6 +55,7 @@ __global__ void vq_zero_tail_kernel(float* p, int n) {
 }
 static inline void vq_zero(void* p, int64_t nbytes, hipStream_t s) {
     const int64_t n16 = nbytes / 16;
+    if (n16 <= 0) return;                        // fewer than 16 bytes: a grid of zero workgroups is not a legal launch
     int64_t blocks = (n16 + 255) / 256;
     if (blocks > 2048) blocks = 2048;
     vq_zero_kernel<<<dim3((unsigned)blocks), dim3(256), 0, s>>>((uint4*)p, n16);

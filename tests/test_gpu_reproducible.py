@@ -323,7 +323,13 @@ def test_scalar_loss_sums_ordered(dev):
     idx = rs.randint(0, k, n).astype(np.int64)
     ref = float(((cb[idx].astype(np.float64) - x) ** 2).sum())
     xt, ct, it = T(x, dev), T(cb, dev), T(idx, dev)
-    _family(lambda: [K.vq_gather_loss(xt, ct, it)[1]], lambda out: np.testing.assert_allclose(float(out[0]), ref, rtol=1e-5))
+    xq_ref = x + (cb[idx] - x)                 # fp32 throughout: the straight-through value the kernel stores
+
+    def check(out):
+        np.testing.assert_allclose(float(out[0]), ref, rtol=1e-5)
+        assert np.array_equal(out[1].cpu().numpy().view(np.uint32), xq_ref.view(np.uint32)), "x_q is not fl(x + fl(e - x)) bit for bit"
+
+    _family(lambda: list(K.vq_gather_loss(xt, ct, it)[::-1]), check)
     a, b = T(rs.standard_normal(2 * 3 * 64 * 64).astype(np.float32), dev), T(rs.standard_normal(2 * 3 * 64 * 64).astype(np.float32), dev)
     _family(lambda: [K.l1_loss(a, b)[0]])
     f0 = T(np.abs(rs.standard_normal((2, 32, 32, 64))).astype(np.float32), dev)
