@@ -235,6 +235,9 @@ SIGNATURES = {
     "dvq_codec_record": (i32, [vp, i32, i64, i64, i64, C.POINTER(TokenRule), vp, vp, i64, i64, vp, vp, vp]),
     "dvq_codec_encode": (i32, [vp, i64, i64, i64, vp, vp, vp, i64, vp, vp, vp]),
     "dvq_codec_decode_step": (i32, [vp, i32, i64, i64, i64, C.POINTER(TokenRule), vp, vp, i64, vp, vp, vp]),
+    "dvq_feat_moments": (i32, [vp, i64, i64, i64, vp, vp, vp, vp, vp]),
+    "dvq_pair_scan_workspace_bytes": (sz, [i64, i64, i32]),
+    "dvq_pair_scan": (i32, [vp, i64, vp, i64, i64, i64, i64, vp, i32, i32, vp, vp, vp, vp, sz, vp]),
 }
 
 

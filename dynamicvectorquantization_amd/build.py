@@ -19,7 +19,7 @@ HERE = os.path.dirname(os.path.abspath(__file__))
 CSRC = os.path.join(HERE, "csrc")
 OBJ = os.path.join(CSRC, "_obj")
 LIB = os.path.join(HERE, "libdvq_hip.so")
-SOURCES = ["vq.hip", "vq_trained.hip", "entropy.hip", "groupnorm.hip", "igemm.hip", "igemm_nt.hip", "igemm_tn.hip", "conv_halo.hip", "misc.hip", "lossnet.hip", "router.hip", "permuter.hip", "transformer.hip", "attention.hip", "attention2.hip", "imgproc.hip", "decode.hip", "cmdlist.hip", "metrics.hip", "nll.hip", "tokens.hip", "imagelog.hip", "trainlog.hip", "normtrack.hip", "jpeg.hip", "jpeg_host.cpp", "codec.hip", "png.hip"]
+SOURCES = ["vq.hip", "vq_trained.hip", "entropy.hip", "groupnorm.hip", "igemm.hip", "igemm_nt.hip", "igemm_tn.hip", "conv_halo.hip", "misc.hip", "lossnet.hip", "router.hip", "permuter.hip", "transformer.hip", "attention.hip", "attention2.hip", "imgproc.hip", "decode.hip", "cmdlist.hip", "metrics.hip", "nll.hip", "tokens.hip", "imagelog.hip", "trainlog.hip", "normtrack.hip", "jpeg.hip", "jpeg_host.cpp", "codec.hip", "png.hip", "sampleset.hip"]
 FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-munsafe-fp-atomics", "-Wno-unused-result"]
 # a .cpp source is host code with no HIP in it (jpeg_host.cpp: the Huffman pass, which also builds with g++ alone)
 HOST_FLAGS = ["-O3", "-std=c++17", "-fPIC"]

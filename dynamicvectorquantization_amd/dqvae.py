@@ -479,6 +479,21 @@ class Decoder(HipModule):
 
 
 # ---------------------------------------------------------------------------------------------
+def _merged_map(model, x, tape):
+    """x NCHW fp32 -> (h, mask, grain, gate, entropy): h = the quant_conv output the quantiser receives (NHWC, compute dtype,
+    channels padded to the kernels' granularity), before the codebook decides anything"""
+    if model.feature_routed:
+        ent = None
+        h_dual, mask, routing = model.encoder.fwd(x, None, _child(tape, "enc"))
+        grain, gate_out = routing.indices, routing.gate.detach()          # gate: fp32 [B,S,hc,wc], differentiable
+    else:
+        ent, gate = K.patch_entropy_gate(x, model.entropy_patch_size, model._threshold())
+        grain = gate[..., 1].contiguous()
+        gate_out = gate.permute(0, 3, 1, 2)
+        h_dual, mask, _ = model.encoder.fwd(x, grain, _child(tape, "enc"))
+    return model.quant_conv.fwd(h_dual, _child(tape, "qc")), mask, grain, gate_out, ent
+
+
 class DualGrainVQModel(nn.Module):
     """dqvae_dual_entropy.py:65-262.  The Lightning surface (training_step / validation_step /
     configure_optimizers / log / attributes set by train.py) is kept; the trainer is
@@ -536,18 +551,38 @@ class DualGrainVQModel(nn.Module):
     def _threshold(self):
         return self.encoder.router.fine_grain_threshold
 
+    @torch.no_grad()
+    def pooled_features(self, x, grid=2):
+        """x NCHW [B,3,H,W] in [-1, 1] -> fp32 [B, grid * grid * D]: the merged map the quantiser receives (the quant_conv output,
+        D = its channels), average-pooled onto a grid x grid layout and flattened (cell row, cell column, channel).  Eval mode, no
+        gradient; nothing the codebook decides is read.  The feature space of evaluate.evaluate_samples
+        (docs/design/32-sample-set-metrics.md).  The map's side over `grid` must be a power of two (pooling runs as x4 / x2 steps
+        of dvq_avgpool_slice, fp32)."""
+        was_training = self.training
+        self.eval()
+        try:
+            x = x.float().contiguous() if x.dtype != torch.float32 or not x.is_contiguous() else x
+            h = _merged_map(self, x, None)[0]
+        finally:
+            self.train(was_training)
+        b, hh, ww, cp = h.shape
+        grid = int(grid)
+        r = hh // grid if grid > 0 else 0
+        if grid < 1 or hh != ww or hh % grid != 0 or r & (r - 1) != 0:
+            raise ValueError(f"pooled_features: a {hh} x {ww} map does not pool onto a {grid} x {grid} grid in x4 / x2 steps")
+        h = h.float()
+        if cp % 8 != 0:                                      # the pooling kernel moves 8 channels at a time
+            h = torch.nn.functional.pad(h, (0, 8 - cp % 8))
+        while r > 1:
+            k = 4 if r % 4 == 0 else 2
+            out = torch.empty(b, h.shape[1] // k, h.shape[2] // k, h.shape[3], dtype=torch.float32, device=h.device)
+            K.avgpool_slice(h.contiguous(), k, out, 0)
+            h, r = out, r // k
+        return h[..., : self.quant_conv.out_channels].reshape(b, -1).contiguous()
+
     def ae_fwd(self, x, tape):
         """x NCHW fp32 -> dict(rec NCHW fp32, qloss, codes, grain, gate, entropy)"""
-        if self.feature_routed:
-            ent = None
-            h_dual, mask, routing = self.encoder.fwd(x, None, _child(tape, "enc"))
-            grain, gate_out = routing.indices, routing.gate.detach()          # gate: fp32 [B,S,hc,wc], differentiable
-        else:
-            ent, gate = K.patch_entropy_gate(x, self.entropy_patch_size, self._threshold())
-            grain = gate[..., 1].contiguous()
-            gate_out = gate.permute(0, 3, 1, 2)
-            h_dual, mask, _ = self.encoder.fwd(x, grain, _child(tape, "enc"))
-        h = self.quant_conv.fwd(h_dual, _child(tape, "qc"))
+        h, mask, grain, gate_out, ent = _merged_map(self, x, tape)
         if getattr(self.quantize, "takes_temperature", False):      # quantisers that sample their code (MaskVectorQuantize)
             xq, qloss, codes = self.quantize.fwd(h, mask, _child(tape, "vq"), temp=self.quant_sample_temperature)
         else:

@@ -18,6 +18,11 @@ top-5 accuracy per token stream, bits per image and per pixel (docs/design/15-li
                              per-image figures (pure numpy)
   * evaluate_cells           one ae_fwd (+ one score_cells) per batch
 
+  * sample_set_metrics       Frechet distance, improved precision / recall, density / coverage of a fake feature set against a real one:
+                             two dvq_feat_moments passes and four dvq_pair_scan scans on the device, the reduction on the host
+                             (docs/design/32-sample-set-metrics.md); frechet_distance / moments_from_sums are its host half (pure numpy)
+  * evaluate_samples         the same on the frozen DQ-VAE's pooled encoder features (model.pooled_features) of two image streams
+
 `reference_usage` reproduces what the reference's scripts/tools/codebook_usage_dqvae.py:69 prints under the label "usage":
 1 - codes_used / K, i.e. the UNUSED fraction of the codebook.
 """
@@ -582,6 +587,114 @@ def evaluate_cells(model, batches, stage2=None, quantize_u8: bool = True, maps: 
                 meter.update_bits(cells, outside, stage2._score_streams(z_out, c))
     s = meter.summary(maps=maps)
     s["dtype"] = dtype_name()
+    return s
+
+
+# ---- sample-set metrics on feature vectors (docs/design/32-sample-set-metrics.md) -----------------------------------------------------
+SAMPLE_NOTES = {
+    "dqvae": "feature space: the frozen DQ-VAE's pooled merged map; the values compare runs of this tree and are NOT the published FID / "
+             "precision / recall (those are defined on Inception pool3 features)",
+    "npy": "feature space: the caller's feature rows; with Inception pool3 rows these are the published quantities",
+    "fd": "the Frechet term is biased upwards at small N (the covariance estimates' trace term): compare runs at equal N only",
+}
+
+
+def moments_from_sums(total, gram, n, shift=None) -> dict:
+    """dvq_feat_moments' outputs (sum and upper-triangle Gram matrix of x - shift over n rows; arrays or tensors) ->
+    {"n", "mean" fp64 [D], "cov" fp64 [D, D]}: the host mirrors the triangle; the covariance divides by n - 1"""
+    to_np = lambda t: t.detach().cpu().numpy() if torch.is_tensor(t) else np.asarray(t)     # noqa: E731
+    s, g, n = to_np(total).astype(np.float64).reshape(-1), to_np(gram).astype(np.float64), int(to_np(n).reshape(-1)[0])
+    if n < 2:
+        raise ValueError(f"a covariance needs at least 2 rows, got {n}")
+    g = np.triu(g) + np.triu(g, 1).T
+    mean = s / n
+    cov = (g - n * np.outer(mean, mean)) / (n - 1)
+    if shift is not None:
+        mean = mean + to_np(shift).astype(np.float64).reshape(-1)
+    return {"n": n, "mean": mean, "cov": cov}
+
+
+def frechet_distance(moments_r: dict, moments_f: dict) -> float:
+    """|mu_r - mu_f|^2 + tr S_r + tr S_f - 2 tr (S_r^1/2 S_f S_r^1/2)^1/2 in fp64 through two symmetric eigendecompositions (negative
+    eigenvalues of either are rounding and clamp to 0, as do those of the product below D eps of its largest; the value is clamped at 0): stable on rank-deficient covariances, where the square root of the unsymmetric
+    product S_r S_f is not"""
+    mr, mf = np.asarray(moments_r["mean"], np.float64), np.asarray(moments_f["mean"], np.float64)
+    sr, sf = np.asarray(moments_r["cov"], np.float64), np.asarray(moments_f["cov"], np.float64)
+    w, v = np.linalg.eigh((sr + sr.T) * 0.5)
+    root = (v * np.sqrt(np.maximum(w, 0.0))) @ v.T
+    m = root @ ((sf + sf.T) * 0.5) @ root
+    ev = np.linalg.eigvalsh((m + m.T) * 0.5)
+    # rank-deficient covariances (fewer rows than columns): the exact zeros come out as +-D eps |M|, and the square roots of the positive
+    # half would take ~1e-7 tr S off the value (FD(X, X) < 0).  Eigenvalues below D eps max(ev) are those zeros
+    ev = np.where(ev > ev.size * np.finfo(np.float64).eps * max(float(ev.max()), 0.0), ev, 0.0)
+    d = mr - mf
+    return max(float(d @ d + np.trace(sr) + np.trace(sf) - 2.0 * np.sqrt(ev).sum()), 0.0)
+
+
+def _finite_features(name, x):
+    if not torch.is_tensor(x) or x.dim() != 2 or not x.is_floating_point():
+        raise TypeError(f"{name}: expected a floating-point [N, D] device tensor")
+    bad = int((~torch.isfinite(x).all(dim=1)).sum())
+    if bad:
+        raise ValueError(f"{name}: {bad} of {x.shape[0]} feature rows hold a non-finite value")
+
+
+def sample_set_metrics(real, fake, k: int = 5, neighbors: int = 0) -> dict:
+    """Fidelity and diversity of a generated set against a real one, on device feature tensors real [Nr, D], fake [Nf, D]:
+    fd (Frechet distance of the two Gaussians), improved precision / recall, density / coverage, all with k-th-neighbour radii.
+    Both sets are centred on the REAL set's mean and cast to fp32 (part of the definition: it keeps dvq_pair_scan's GEMM-form distance
+    accurate); two moment passes and four scans (R|R, F|F, F|R, R|F) run on the device, the reduction on the host in integers / fp64.
+    neighbors > 0 adds "neighbor_idx" int64 [Nf, neighbors] and "neighbor_dist" fp32 (squared, centred fp32 features): each fake's
+    nearest reals -- the memorisation check, from the F|R scan."""
+    _finite_features("real", real)
+    _finite_features("fake", fake)
+    k, neighbors = int(k), int(neighbors)
+    nr, d = int(real.shape[0]), int(real.shape[1])
+    nf = int(fake.shape[0])
+    if fake.shape[1] != d:
+        raise ValueError(f"real features have {d} columns, fake {fake.shape[1]}")
+    if not 1 <= k <= 16 or not 0 <= neighbors <= 16:
+        raise ValueError(f"k={k} / neighbors={neighbors}: the scan keeps 1..16 neighbours")
+    if min(nr, nf) <= k:
+        raise ValueError(f"k={k} needs more than k rows in both sets (real {nr}, fake {nf})")
+    mean = real.double().mean(dim=0)
+    xr = (real.double() - mean).float().contiguous()
+    xf = (fake.double() - mean).float().contiguous()
+    zero = torch.zeros(d, dtype=torch.float32, device=xr.device)
+    mom_r, mom_f = K.feat_moments(xr, zero), K.feat_moments(xf, zero)
+    rad_r = K.pair_scan(xr, xr, k, exclude_diag=True)[0][:, k - 1].contiguous()
+    rad_f = K.pair_scan(xf, xf, k, exclude_diag=True)[0][:, k - 1].contiguous()
+    d_fr, i_fr, c_fr = K.pair_scan(xf, xr, max(neighbors, 1), rad2_b=rad_r)
+    d_rf, _, c_rf = K.pair_scan(xr, xf, 1, rad2_b=rad_f)
+    c_fr, c_rf = c_fr.cpu().numpy(), c_rf.cpu().numpy()
+    out = {
+        "fd": frechet_distance(moments_from_sums(*mom_r), moments_from_sums(*mom_f)),
+        "precision": float(np.mean(c_fr > 0)),
+        "recall": float(np.mean(c_rf > 0)),
+        "density": float(int(c_fr.sum()) / (k * nf)),
+        "coverage": float(np.mean(d_rf[:, 0].cpu().numpy() <= rad_r.cpu().numpy())),
+        "k": k, "n_real": nr, "n_fake": nf, "dim": d,
+    }
+    if neighbors > 0:
+        out["neighbor_idx"], out["neighbor_dist"] = i_fr.cpu().numpy(), d_fr.cpu().numpy()
+    return out
+
+
+def evaluate_samples(model, real_batches, fake_batches, k: int = 5, grid: int = 2, neighbors: int = 0) -> dict:
+    """sample_set_metrics in the frozen DQ-VAE's own feature space: both image streams (NCHW [-1, 1] batches, or dicts holding one
+    under model.image_key) go through model.pooled_features(x, grid); the features stay on the device (50 000 x 1024 fp32: 200 MB
+    per set).  Keys: sample_set_metrics(), plus grid, features, dtype and the notes."""
+    def features(batches):
+        rows = []
+        for batch in batches:
+            x = batch[getattr(model, "image_key", "image")] if isinstance(batch, dict) else batch
+            rows.append(model.pooled_features(x, grid))
+        if not rows:
+            raise ValueError("evaluate_samples: an image stream is empty")
+        return torch.cat(rows, dim=0)
+
+    s = sample_set_metrics(features(real_batches), features(fake_batches), k=k, neighbors=neighbors)
+    s.update(grid=int(grid), features="dqvae", dtype=dtype_name(), note=SAMPLE_NOTES["dqvae"], fd_note=SAMPLE_NOTES["fd"])
     return s
 
 

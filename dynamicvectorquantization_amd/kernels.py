@@ -1614,6 +1614,61 @@ def code_histogram(codes, grain, n_codes, n_grains, counts, invalid, tokens=None
 
 
 # ---------------------------------------------------------------------------------------------
+# sample-set metrics (csrc/sampleset.hip, docs/design/32-sample-set-metrics.md)
+# ---------------------------------------------------------------------------------------------
+def _feature_rows(name, t):
+    """fp32 [N, D] rows of any pitch (a column slice of a wider contiguous matrix passes) -> (N, D, pitch)"""
+    if not torch.is_tensor(t) or t.dtype != torch.float32 or t.dim() != 2:
+        raise TypeError(f"{name}: expected an fp32 [N, D] tensor")
+    n, d = int(t.shape[0]), int(t.shape[1])
+    if n and d and (t.stride(1) != 1 or (n > 1 and t.stride(0) < d)):
+        raise _lib.DvqError(f"{name}: rows must be contiguous (strides {t.stride()})")
+    return n, d, int(t.stride(0)) if n > 1 else max(d, 1)
+
+
+def feat_moments(x, shift, out=None):
+    """x fp32 [N, D] (rows of any pitch), shift fp32 [D] -> (sum fp64 [D], gram fp64 [D, D] upper triangle, n int64 [1]) of
+    fl32(x - shift), ACCUMULATED into `out` (the three tensors of an earlier call) or into fresh zeros (include/dvq_hip.h,
+    dvq_feat_moments).  The lower triangle of gram is never written: mirror it on the host."""
+    n, d, ld = _feature_rows("feat_moments: x", x)
+    assert shift.dtype == torch.float32 and shift.numel() == d
+    if out is None:
+        out = (torch.zeros(d, dtype=torch.float64, device=x.device), torch.zeros(d, d, dtype=torch.float64, device=x.device),
+               torch.zeros(1, dtype=torch.int64, device=x.device))
+    s, g, cnt = out
+    assert s.dtype == torch.float64 and g.dtype == torch.float64 and cnt.dtype == torch.int64 and tuple(g.shape) == (d, d) and s.numel() == d
+    check(lib().dvq_feat_moments(_praw(x), n, d, ld, _p(shift), _p(s), _p(g), _p(cnt), _s()), "dvq_feat_moments")
+    return s, g, cnt
+
+
+def pair_scan_workspace(na, nb, k, device):
+    """uint8 workspace of dvq_pair_scan_workspace_bytes(na, nb, k) bytes (per-split candidate lists; empty when b is not split)"""
+    return torch.empty(int(lib().dvq_pair_scan_workspace_bytes(na, nb, k)), dtype=torch.uint8, device=device)
+
+
+def pair_scan(a, b, k, rad2_b=None, exclude_diag=False, ws=None, count=None):
+    """a fp32 [Na, D], b fp32 [Nb, D] (rows of any pitch; CENTRED features) -> (kth2 fp32 [Na, k], idx int64 [Na, k], count int64 [Na] or
+    None): per row of a its k smallest squared distances to rows of b, their indices, and with rad2_b fp32 [Nb] the number of j with
+    d2(i, j) <= rad2_b[j] (include/dvq_hip.h, dvq_pair_scan).  ws: pair_scan_workspace(Na, Nb, k) or None (allocated here)"""
+    na, d, lda = _feature_rows("pair_scan: a", a)
+    nb, db, ldb = _feature_rows("pair_scan: b", b)
+    if d != db:
+        raise _lib.DvqError(f"pair_scan: a has {d} columns, b has {db}")
+    k = int(k)
+    if ws is None:
+        ws = pair_scan_workspace(na, nb, k, a.device)
+    kth2 = torch.empty(na, max(k, 0), dtype=torch.float32, device=a.device)
+    idx = torch.empty(na, max(k, 0), dtype=torch.int64, device=a.device)
+    if rad2_b is not None:
+        assert rad2_b.dtype == torch.float32 and rad2_b.numel() == nb
+        if count is None:
+            count = torch.empty(na, dtype=torch.int64, device=a.device)
+    check(lib().dvq_pair_scan(_praw(a), lda, _praw(b), ldb, na, nb, d, _p(rad2_b), k, int(bool(exclude_diag)), _p(kth2), _p(idx),
+                              _p(count), _p(ws) if ws.numel() else None, ws.numel(), _s()), "dvq_pair_scan")
+    return kth2, idx, count
+
+
+# ---------------------------------------------------------------------------------------------
 # token shards (csrc/tokens.hip, docs/design/16-token-shards.md)
 # ---------------------------------------------------------------------------------------------
 def _tokens_arg(name, t, dtype, shape):

@@ -49,7 +49,8 @@ const char* dvq_last_error(void);
  * dvq_conv2d_scratch_bytes (plane passes + the bf16 kernels behind them). */
 const char* dvq_last_kernel(void);
 int dvq_version(void);     /* 124 (additions since, no signature changed, no symbol removed: dvq_recon_cells (+ _workspace_bytes), dvq_nll_cell_sums: per-cell
-                            * error and likelihood maps, docs/design/30-cell-maps.md): dvq_conv2d_fwd / _dgrad / _wgrad take (scratch, scratch_bytes) and route the fp32x3 launch-level schemes themselves;
+                            * error and likelihood maps, docs/design/30-cell-maps.md; dvq_feat_moments, dvq_pair_scan (+ _workspace_bytes): sample-set
+                            * metrics, docs/design/32-sample-set-metrics.md): dvq_conv2d_fwd / _dgrad / _wgrad take (scratch, scratch_bytes) and route the fp32x3 launch-level schemes themselves;
                             * dvq_conv2d_scratch_bytes replaces dvq_conv3x3_x3_ok, dvq_conv3x3_x3_scratch_bytes and dvq_conv2d_wgrad_x3_scratch_bytes;
                             * dvq_conv2d_fwd_x3, dvq_conv2d_dgrad_x3 and dvq_conv2d_wgrad_oihw_x3 are gone;
                             * 123: struct dvq_token_rule, DVQ_TOKEN_RULE_MAXV: dvq_sample_constrained, dvq_sample_guided, dvq_codec_tables, dvq_codec_record and
@@ -991,6 +992,34 @@ int dvq_codec_encode(const uint32_t* records, int64_t B, int64_t T, int64_t rec_
                      uint32_t* words, int64_t cap, int64_t* nwords, double* bits, dvq_stream_t stream);
 int dvq_codec_decode_step(const void* logits, int dtype, int64_t B, int64_t V, int64_t ldl, const dvq_token_rule* rule, int64_t* state,
                           const uint32_t* words, int64_t total_words, int64_t* token, uint32_t* err, dvq_stream_t stream);
+
+/* ---- sample-set metrics on feature vectors (csrc/sampleset.hip, docs/design/32-sample-set-metrics.md; no reference kernel: its
+ * samplers stop at an .npz for an external tool) -----------------------------------------------------------------------------------
+ * dvq_feat_moments: x fp32 [N][ld], the first D columns are used (columns D .. ld are never read); shift fp32 [D].  With
+ *   y = fl32(x - shift):  sum fp64 [D] += sum_n y,  gram fp64 [D][D] += sum_n y y^T on the UPPER triangle (row <= column; the lower
+ *   triangle is never touched: the caller mirrors it),  n int64 [1] += N.  The caller zeroes the three once and streams a set through
+ *   in batches.  Every product of two fp32 values is formed exactly in fp64 and added in fp64, one owner per output walking the rows in
+ *   order (plain fp64 FMAs): no atomics, the same batches give the same bits.  D in [1, 4096], N >= 1 (else DVQ_ESHAPE).
+ * dvq_pair_scan: a fp32 [Na][lda], b fp32 [Nb][ldb], first D columns used (the rest never read).  With
+ *   d2(i, j) = max(fl32(fl32(|a_i|^2 + |b_j|^2) - 2 a_i.b_j), 0): the norms summed in fp64 from exact squares and rounded once to fp32,
+ *   the inner product fp32 fmaf chains on the fp32 matrix instruction (one per block of 64 columns, per 8 columns in the order 0, 4,
+ *   1, 5, 2, 6, 3, 7; the block sums added in order -- blocked summation, a quarter of one long chain's error at D = 1024).  The form
+ *   is accurate for CENTRED features only (error ~ 1e-7 (|a|^2 + |b|^2)): the caller subtracts a common mean first.  Per row i of a:
+ *   kth2 fp32 [Na][k] = the k smallest d2(i, j), ascending, +inf where fewer than k candidates exist;  idx int64 [Na][k] = their j
+ *   (equal distances: the lower j first), -1 at the padding;  count int64 [Na] = #{j : d2(i, j) <= rad2_b[j]} on the same d2 values
+ *   (rad2_b fp32 [Nb]; NULL: count is not touched and may be NULL).  exclude_diag = 1 skips the pair j == i (a set against itself).
+ *   k in [1, 16] and exclude_diag in {0, 1} (else DVQ_EINVAL); Na, Nb, D >= 1, Nb < 2^31, pitches >= D (else DVQ_ESHAPE).
+ *   ws: dvq_pair_scan_workspace_bytes(Na, Nb, k) bytes, 8-byte aligned (per-split candidate lists when a has too few rows to fill the
+ *   chip; 0 when b is not split, ws may then be NULL; 0 for bad arguments too; smaller: DVQ_EWORKSPACE, nothing is launched).  No
+ *   Na x Nb array exists anywhere.  One owner per output and no float atomics: two launches give the same bits, and a row's result
+ *   depends on that row of a and on b only -- not on the other rows of a, their number, or the split.
+ *   Non-finite inputs: a pair whose d2 comes out NaN or +inf is neither selected nor counted (a row of a holding a NaN reports +inf / -1
+ *   / 0 throughout); every idx written is -1 or in [0, Nb). */
+int dvq_feat_moments(const float* x, int64_t N, int64_t D, int64_t ld, const float* shift, double* sum, double* gram, int64_t* n,
+                     dvq_stream_t stream);
+size_t dvq_pair_scan_workspace_bytes(int64_t Na, int64_t Nb, int k);
+int dvq_pair_scan(const float* a, int64_t lda, const float* b, int64_t ldb, int64_t Na, int64_t Nb, int64_t D, const float* rad2_b, int k,
+                  int exclude_diag, float* kth2, int64_t* idx, int64_t* count, void* ws, size_t ws_bytes, dvq_stream_t stream);
 
 #ifdef __cplusplus
 }
